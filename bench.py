@@ -17,6 +17,13 @@ exchange) before the ordered overlap average.  The N=1 line carries the same
 meeting's 1-GPU time (`c4_60min_ms`), so every point of the series reads against
 one workload.  `--workload c2 --gpus N` runs the headline model on that meeting;
 `--scaling weak` gives N x 10-min meetings.
+
+A plain run sets up, runs `--warmup` untimed and `--steps` timed steps, and prints the headline
+line (metric, value, unit, ms_per_step, dtype, config).  `--full` adds everything measured
+in runs of their own: end-to-end RTTM timing, the live per-kernel table and rooflines, the CPU
+baseline, posterior / DER parity against the oracle and the 1-GPU C4 time.  `--dump-outputs DIR`
+writes what the last timed step returned as DIR/<name>.npy; inputs and weights are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -81,6 +88,13 @@ def parse(argv=None):
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS) + ["dist_check"],
                     help="default: c2 on one GPU, c4 (the 60-min strong-scaling meeting) on N > 1; "
                          "dist_check = CPU/gloo launcher self-test (no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can carry: end-to-end RTTM timing, "
+                         "live per-kernel timing and rooflines, the CPU baseline, posterior / DER parity and the "
+                         "1-GPU time of the C4 60-min meeting (each with its own --no-* switch); a plain run sets up, "
+                         "warms up, times the steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float32)")
     ap.add_argument("--no-c4-ref", action="store_true",
                     help="N=1 C2 line: skip the 1-GPU time of the C4 60-min meeting the N>1 lines run")
     ap.add_argument("--minutes", type=float, default=None,
@@ -382,6 +396,49 @@ def timed(step, warmup, steps, world, dev):
     return elapsed, out
 
 
+DUMP_LIMIT = 64 << 20     # bytes over all the arrays of one --dump-outputs
+
+
+def _leaves(name, out, acc):
+    """(name, float array) for every tensor / array / number in a step's return value (lists, tuples and
+    dicts are walked, their index or key appended to the name)."""
+    if out is None:
+        return
+    if isinstance(out, dict):
+        for k, v in out.items():
+            _leaves(f"{name}_{k}", v, acc)
+    elif isinstance(out, (list, tuple)):
+        for i, v in enumerate(out):
+            _leaves(f"{name}_{i}", v, acc)
+    else:
+        if hasattr(out, "detach"):
+            out = out.detach().cpu()
+            out = (out if out.dtype.is_floating_point and out.element_size() >= 4 else out.float()).numpy()
+        arr = np.asarray(out)
+        if arr.dtype.kind in "fiub":
+            acc.append((name, arr if arr.dtype == np.float64 else arr.astype(np.float32)))
+
+
+def dump_outputs(path, name, out, rank=0):
+    """--dump-outputs: what the last timed step returned, as <path>/<name>[_<i>...].npy (float32; float64
+    where the path computes in it), written by rank 0.  At most DUMP_LIMIT bytes in all: an array over its
+    share is cut to a fixed seeded sample of its flattened elements (indices drawn from seed 0 and its size,
+    sorted), so two builds run with the same arguments dump the same elements."""
+    if not path or rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    acc = []
+    _leaves(name, out, acc)
+    if sum(arr.nbytes for _, arr in acc) > DUMP_LIMIT:
+        share = DUMP_LIMIT // len(acc)
+        for i, (n, arr) in enumerate(acc):
+            if arr.nbytes > share:
+                idx = np.sort(np.random.default_rng(0).integers(0, arr.size, share // arr.itemsize))
+                acc[i] = (n, arr.reshape(-1)[idx])
+    for n, arr in acc:
+        np.save(os.path.join(path, n + ".npy"), arr)
+
+
 def main_dist_check(a):
     """CPU self-test of the launcher (tests/test_bench_launcher.py): the same rank setup,
     timing and line as the TS-VAD strong-scaling path, with gloo instead of RCCL and the
@@ -403,11 +460,13 @@ def main_dist_check(a):
         return gather_windows(local, plan, a.batch, world) if world > 1 else local
     elapsed, got = timed(step, a.warmup, a.steps, world, dev)
     ok = bool(torch.equal(got, full))
+    dump_outputs(a.dump_outputs, "window_logits", got, rank)
     if rank == 0:
         print(json.dumps({"metric": "launcher self-test (window-logit all-gather)", "value": round(
             plan.n_win * a.steps / elapsed, 1), "unit": "windows/s", "n_gpus": world, "rccl_ranks": None,
             "ranks_joined": joined, "backend": "gloo", "gather_matches_global_order": ok,
-            "shard": [w0, w1], "n_win": plan.n_win, "steps": a.steps, "warmup": a.warmup}))
+            "shard": [w0, w1], "n_win": plan.n_win, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(elapsed / a.steps * 1e3, 3)}))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()
@@ -608,27 +667,28 @@ def main(a, wl):
     elapsed, post = timed(step, a.warmup, a.steps, world, dev)
     ms_per_step = elapsed / a.steps * 1000.0
     value = frames_per_step * a.steps / elapsed
+    dump_outputs(a.dump_outputs, "posteriors", post, rank)
 
-    # End-to-end (wav in HBM -> RTTM text at the 10 recipe thresholds): median of 3.
-    keys = [f"{meeting.name}-{i + 1}" for i in range(4)]
+    t_e2e, kernels, cpu, der, parity, c4 = None, None, None, None, None, None
+    if a.full:
+        # End-to-end (wav in HBM -> RTTM text at the 10 recipe thresholds): median of 3.
+        keys = [f"{meeting.name}-{i + 1}" for i in range(4)]
 
-    def e2e():
-        p = pipe.posteriors(job["wav"], job["ts"], job["n_lab"])
-        return posteriors_to_rttm_gpu(keys, p) if rank == 0 else None
-    e2e()
-    t_e2e, _, _ = median3(e2e)
+        def e2e():
+            p = pipe.posteriors(job["wav"], job["ts"], job["n_lab"])
+            return posteriors_to_rttm_gpu(keys, p) if rank == 0 else None
+        e2e()
+        t_e2e, _, _ = median3(e2e)
 
-    kernels = None if a.no_kernel_timing else live_kernels(step)
+        kernels = None if a.no_kernel_timing else live_kernels(step)
 
-    cpu, der, parity = None, None, None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        cpu, cpu_post, n_cpu = cpu_baseline(job["cfg"], job["sd_np"], meeting, job["ts_np"], a.cpu_seconds)
-        der = der_parity(meeting, post, cpu_post, float(n_cpu))
-        parity = posterior_parity(post.cpu().numpy(), cpu_post, n_cpu * 25)
-        der["dynamic"] = variant_der(job, a, dev, meeting, n_cpu)
-    c4 = None
-    if world == 1 and a.workload == "c2" and not a.no_c4_ref:
-        c4 = c4_reference(a, dev)
+        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+            cpu, cpu_post, n_cpu = cpu_baseline(job["cfg"], job["sd_np"], meeting, job["ts_np"], a.cpu_seconds)
+            der = der_parity(meeting, post, cpu_post, float(n_cpu))
+            parity = posterior_parity(post.cpu().numpy(), cpu_post, n_cpu * 25)
+            der["dynamic"] = variant_der(job, a, dev, meeting, n_cpu)
+        if world == 1 and a.workload == "c2" and not a.no_c4_ref:
+            c4 = c4_reference(a, dev)
 
     if rank == 0:
         plan = pipe.plan(job["n_lab"])
@@ -652,20 +712,21 @@ def main(a, wl):
                        "global_batch": a.batch, "device_batch": max(a.batch, a.device_batch),
                        "parallelism": (f"window-shard x{world} on the 64-window batch grid + RCCL all-gather of "
                                        f"window logits" if world > 1 else "1 GPU")},
-            "end_to_end": {"ms_per_step": round(t_e2e * 1e3, 3), "value": round(frames_per_step / t_e2e, 1),
-                           "what": "wav in HBM -> posteriors -> GPU medfilt/threshold/run-length -> RTTM lines "
-                                   "(10 thresholds), median of 3"},
         }
-        if c4 is not None:
-            line["c4_60min_ms"] = c4["ms_per_step"]
-            line["c4_60min"] = c4
-        line.update(kernel_report(kernels, a.workload, ms_per_step, a.precision))
-        line["cpu_baseline"] = cpu
-        line["parity"] = parity
-        line["der"] = der
-        if cpu:
-            line["speedup_vs_cpu"] = round(value / cpu["value"], 1)
-            line["end_to_end"]["speedup_vs_cpu"] = round(frames_per_step / t_e2e / cpu["end_to_end_value"], 1)
+        if a.full:
+            line["end_to_end"] = {"ms_per_step": round(t_e2e * 1e3, 3), "value": round(frames_per_step / t_e2e, 1),
+                                  "what": "wav in HBM -> posteriors -> GPU medfilt/threshold/run-length -> RTTM lines "
+                                          "(10 thresholds), median of 3"}
+            if c4 is not None:
+                line["c4_60min_ms"] = c4["ms_per_step"]
+                line["c4_60min"] = c4
+            line.update(kernel_report(kernels, a.workload, ms_per_step, a.precision))
+            line["cpu_baseline"] = cpu
+            line["parity"] = parity
+            line["der"] = der
+            if cpu:
+                line["speedup_vs_cpu"] = round(value / cpu["value"], 1)
+                line["end_to_end"]["speedup_vs_cpu"] = round(frames_per_step / t_e2e / cpu["end_to_end_value"], 1)
         print(json.dumps(line))
     if world > 1:
         import torch.distributed as dist
@@ -865,10 +926,12 @@ def main_eend(a, wl):
         def parity_fn():
             return fseend_oracle_parity(meeting, sd_np, step()[0][0], frames=1000)
     elapsed, out = timed(step, a.warmup, a.steps, world, dev)
-    if kind == "eda":
+    dump_outputs(a.dump_outputs, {"eda": "chunks", "embed": "embeddings", "tsvad_stream": "posteriors"}.get(kind, "test"),
+                 out, rank)
+    if kind == "eda" and a.full:
         after(out)
     ms_per_step = elapsed / a.steps * 1000.0
-    kernels = None if a.no_kernel_timing else live_kernels(step)
+    kernels = None if a.no_kernel_timing or not a.full else live_kernels(step)
     if rank == 0:
         line = {"metric": "diarized frames/sec (10 ms hop)", "value": round(frames * a.steps / elapsed, 1),
                 "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -880,7 +943,7 @@ def main_eend(a, wl):
                                            "replicas x%d" % world) if world > 1 else "1 GPU"}}
         line.update(extra)
         line.update(kernel_report(kernels, a.workload, ms_per_step, prec))
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_fn()
             line["speedup_vs_cpu"] = round(line["value"] / line["cpu_baseline"]["value"], 1)
             if parity_fn is not None:
@@ -1037,22 +1100,24 @@ def main_stream(a, wl):
     elapsed, _ = timed(lambda: step(True), 0, a.steps, world, dev)
     st1 = stats()
     lat[:] = lat[-(len(lat) // a.steps) * a.steps:]   # timed steps only
-    # every step streams the whole recording from reset: a push attends over (T + 1) / 2 history rows on average
-    latency_model = stream_latency_model(sd_np, st0, st1, len(lat), float(np.percentile(np.array(lat) * 1e6, 50)),
-                                         audio, a.precision, kv=dict(rows=(T + 1) / 2, enc_layers=4, dec_layers=2,
-                                                                     slots=6, d=256)) if a.steps else None
-    # parity of this very run: against the whole-recording GPU test() on the same features, and against
-    # the fp32 CPU oracle (oracle/fseend_ref.py test() on oracle/eend_ref.py features) over the first frames
-    Tc = min(T, 2000)
-    m2 = OnlineTransformerDADiarization(None, 345, 256, 4, 4, 2, 0.1, True, 10000, 2048, precision=a.precision,
-                                        max_seqs=1, max_frames=Tc, max_nspks=6)
-    m2.load_state_dict(to_torch(sd_np))
-    full, _, _ = m2.test_device(feats[None, :Tc], [Tc], 6, want_emb=False, want_attractors=False)
-    nc = Tc - 9 if Tc < T else Tc     # the truncated reference sees no look-ahead for its last 9 frames
-    err = float((full[0, :nc] - preds[:nc]).abs().max())
-    parity = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        parity = fseend_oracle_parity(meeting, sd_np, preds[:T], frames=min(T, 1000))
+    dump_outputs(a.dump_outputs, "scores", preds[:T], rank)
+    latency_model, err, parity = None, None, None
+    if a.full:
+        # every step streams the whole recording from reset: a push attends over (T + 1) / 2 history rows on average
+        latency_model = stream_latency_model(sd_np, st0, st1, len(lat), float(np.percentile(np.array(lat) * 1e6, 50)),
+                                             audio, a.precision, kv=dict(rows=(T + 1) / 2, enc_layers=4, dec_layers=2,
+                                                                         slots=6, d=256)) if a.steps else None
+        # parity of this very run: against the whole-recording GPU test() on the same features, and against
+        # the fp32 CPU oracle (oracle/fseend_ref.py test() on oracle/eend_ref.py features) over the first frames
+        Tc = min(T, 2000)
+        m2 = OnlineTransformerDADiarization(None, 345, 256, 4, 4, 2, 0.1, True, 10000, 2048, precision=a.precision,
+                                            max_seqs=1, max_frames=Tc, max_nspks=6)
+        m2.load_state_dict(to_torch(sd_np))
+        full, _, _ = m2.test_device(feats[None, :Tc], [Tc], 6, want_emb=False, want_attractors=False)
+        nc = Tc - 9 if Tc < T else Tc     # the truncated reference sees no look-ahead for its last 9 frames
+        err = float((full[0, :nc] - preds[:nc]).abs().max())
+        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+            parity = fseend_oracle_parity(meeting, sd_np, preds[:T], frames=min(T, 1000))
     lib.sd_fseend_stream_destroy(s)
     L = np.array(lat) * 1e3
     frames = meeting.wav.size // 80 * world
@@ -1074,10 +1139,10 @@ def main_stream(a, wl):
                                "p90": round(float(np.percentile(L, 90)), 4),
                                "p99": round(float(np.percentile(L, 99)), 4),
                                "max": round(float(L.max()), 4), "mean": round(float(L.mean()), 4)},
-                "real_time_factor": round(float(L.mean()) / unit_ms, 5),
-                "roofline": latency_model,
-                "max_abs_diff_vs_test": err, "parity": parity}
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+                "real_time_factor": round(float(L.mean()) / unit_ms, 5)}
+        if a.full:
+            line.update({"roofline": latency_model, "max_abs_diff_vs_test": err, "parity": parity})
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = fseend_cpu_baseline(meeting, sd_np, a.cpu_seconds)
             line["speedup_vs_cpu"] = round(line["value"] / line["cpu_baseline"]["value"], 1)
         print(json.dumps(line))

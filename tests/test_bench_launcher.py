@@ -58,3 +58,41 @@ def test_failed_rank_stops_the_job():
     (instead of hanging in a collective)."""
     r, _ = _run("--gpus", "2", "--workload", "dist_check", "--steps", "1", "--warmup", "0", "--batch", "0")
     assert r.returncode != 0
+
+
+def test_dump_outputs_repeats(tmp_path):
+    """--dump-outputs: the same arguments give the same arrays, in float32, and the line holds ms_per_step."""
+    import numpy as np
+    got = []
+    for d in ("a", "b"):
+        r, lines = _run("--gpus", "1", "--workload", "dist_check", "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads(lines[0])["ms_per_step"] > 0
+        got.append(np.load(tmp_path / d / "window_logits.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (3600, 4, 100)
+    np.testing.assert_array_equal(got[0], got[1])
+
+
+def test_dump_outputs_samples_large_outputs(tmp_path, monkeypatch):
+    """Outputs over the byte limit are cut to the same seeded sample on every call; small ones stay whole."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096)
+    big = np.arange(5000, dtype=np.float64).reshape(50, 100)
+    out = (torch.arange(6, dtype=torch.bfloat16).reshape(2, 3), [big, None], {"n": 7})
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), "out", out)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["out_0.npy", "out_1_0.npy", "out_2_n.npy"]
+    arrs = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert sum(x.nbytes for x in arrs.values()) <= 4096
+    assert arrs["out_0.npy"].dtype == np.float32 and arrs["out_0.npy"].tolist() == [[0, 1, 2], [3, 4, 5]]
+    s = arrs["out_1_0.npy"]
+    assert s.dtype == np.float64 and s.ndim == 1 and 0 < s.size < big.size and np.isin(s, big).all()
+    for f in files:
+        np.testing.assert_array_equal(arrs[f], np.load(tmp_path / "b" / f))
+    bench.dump_outputs(str(tmp_path / "c"), "out", out, rank=1)      # rank 0 writes
+    assert not os.path.exists(tmp_path / "c")

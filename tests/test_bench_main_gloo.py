@@ -12,7 +12,7 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--workload", "c4", "--minutes", "0.35", "--batch", "4", "--steps", "1", "--warmup", "0",
-        "--no-cpu-baseline", "--no-kernel-timing", "--precision", "fp32"]
+        "--no-cpu-baseline", "--no-kernel-timing", "--precision", "fp32", "--full"]
 
 
 def _port():
@@ -24,14 +24,14 @@ def _port():
     return p
 
 
-def _run(world, out):
+def _run(world, out, args=ARGS):
     port = str(_port())
     procs = []
     for r in range(world):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=port, OMP_NUM_THREADS="2")
         procs.append(subprocess.Popen([sys.executable, os.path.join(REPO, "tests", "bench_main_standin.py"), out,
-                                       *ARGS], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                                       *args], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                                       cwd=REPO))
     outs = []
     for p in procs:
@@ -67,3 +67,19 @@ def test_bench_main_two_ranks_matches_one(tmp_path):
     for r in range(2):       # every rank holds the gathered meeting posteriors
         np.testing.assert_array_equal(np.load(d2 / f"post_rank{r}.npy"), p1)
     assert np.isfinite(p1).all()
+
+
+def test_plain_run_times_and_dumps_only(tmp_path):
+    """Without --full the line carries the headline fields and none of the legs that take runs of their own,
+    and --dump-outputs holds the posteriors of the last timed step."""
+    args = [x for x in ARGS if x != "--full"] + ["--dump-outputs", str(tmp_path / "dump")]
+    args[args.index("--minutes") + 1] = "0.2"
+    args[args.index("--steps") + 1] = "2"
+    line = _run(1, str(tmp_path), args)
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["metric"] and line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "fp32"
+    for leg in ("end_to_end", "cpu_baseline", "parity", "der", "kernels", "roofline", "c4_60min"):
+        assert leg not in line, leg
+    dumped = np.load(tmp_path / "dump" / "posteriors.npy")
+    assert dumped.dtype == np.float32
+    np.testing.assert_array_equal(dumped, np.load(tmp_path / "post_rank0.npy"))

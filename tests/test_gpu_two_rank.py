@@ -15,7 +15,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--workload", "c4", "--minutes", "13", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-        "--no-kernel-timing"]
+        "--no-kernel-timing", "--full"]
 
 
 def _port():

@@ -8,7 +8,7 @@ mkdir -p gpurun_out/ab
 for i in $(seq 1 "$R"); do
   for tag in A B; do
     lib=$A; [ "$tag" = B ] && lib=$B
-    SDIAR_LIB=$lib timeout -k 10 300 python3 bench.py --workload "$WL" --steps 5 --warmup 2 --no-cpu-baseline \
+    SDIAR_LIB=$lib timeout -k 10 300 python3 bench.py --full --workload "$WL" --steps 5 --warmup 2 --no-cpu-baseline \
       --no-c4-ref > "gpurun_out/ab/${tag}_$i.json" 2> "gpurun_out/ab/${tag}_$i.err"
     python3 - "$tag" "gpurun_out/ab/${tag}_$i.json" <<'PY'
 import json, sys

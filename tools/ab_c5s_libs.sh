@@ -9,7 +9,7 @@ for i in $(seq 1 "$R"); do
     tag=${spec%%=*}; rest=${spec#*=}; lib=${rest%%,*}; envs=""
     [ "$rest" != "$lib" ] && envs=${rest#*,}
     out="gpurun_out/ab/c5s_${tag}_$i.json"
-    env SDIAR_LIB="$lib" $envs timeout -k 10 300 python3 bench.py --workload c5s --steps 2 --warmup 1 \
+    env SDIAR_LIB="$lib" $envs timeout -k 10 300 python3 bench.py --full --workload c5s --steps 2 --warmup 1 \
       --no-cpu-baseline > "$out" 2> "${out%.json}.err"
     python3 - "$tag" "$out" <<'PY'
 import json, sys

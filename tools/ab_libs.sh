@@ -8,7 +8,7 @@ mkdir -p "$O"
 for i in $(seq 1 "$R"); do
   for lib in "$@"; do
     tag=$(basename "$lib" .so)
-    SDIAR_LIB=$lib timeout -k 10 300 python3 bench.py --workload "$WL" --steps 10 --warmup 2 --no-cpu-baseline \
+    SDIAR_LIB=$lib timeout -k 10 300 python3 bench.py --full --workload "$WL" --steps 10 --warmup 2 --no-cpu-baseline \
       --no-c4-ref > "$O/${tag}_$i.json" 2> "$O/${tag}_$i.err" || { echo "$tag failed"; tail -3 "$O/${tag}_$i.err"; exit 1; }
     python3 - "$tag" "$O/${tag}_$i.json" <<'PY'
 import json, sys

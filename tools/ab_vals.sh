@@ -8,7 +8,7 @@ for i in $(seq 1 "$R"); do
   for val in "$@"; do
     if [ "$val" = "-" ]; then unset "$V"; else export "$V"="$val"; fi
     out="gpurun_out/ab/${V}_${val}_$i.json"
-    timeout -k 10 300 python3 bench.py --workload "$WL" --steps 5 --warmup 2 --no-cpu-baseline --no-c4-ref > "$out" 2> "${out%.json}.err"
+    timeout -k 10 300 python3 bench.py --full --workload "$WL" --steps 5 --warmup 2 --no-cpu-baseline --no-c4-ref > "$out" 2> "${out%.json}.err"
     python3 - "$V=$val" "$out" <<'PY'
 import json, sys
 d = json.loads([x for x in open(sys.argv[2]) if x.startswith("{")][-1])

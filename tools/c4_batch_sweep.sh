@@ -3,7 +3,7 @@
 set -euo pipefail
 mkdir -p gpurun_out/c4b
 for db in "$@"; do
-  timeout -k 10 300 python3 bench.py --workload c4 --steps 3 --warmup 1 --no-cpu-baseline --no-c4-ref --device-batch "$db" \
+  timeout -k 10 300 python3 bench.py --full --workload c4 --steps 3 --warmup 1 --no-cpu-baseline --no-c4-ref --device-batch "$db" \
     > "gpurun_out/c4b/db_$db.json" 2> "gpurun_out/c4b/db_$db.err"
   python3 - "$db" "gpurun_out/c4b/db_$db.json" <<'PY'
 import json, sys

@@ -7,7 +7,8 @@
 #   tests[:<pytest -k expr>]           the -m gpu suite (or the selected tests) -> <outdir>/tests*.log
 #   file:<test file>[:<-k expr>]       one test file -> <outdir>/<file stem>.log
 #   smoke                              __graft_entry__.smoke()
-#   bench:<name>:<bench.py args>       one bench line -> <outdir>/<name>.json (+ .err)
+#   bench:<name>:<bench.py args>       one bench line -> <outdir>/<name>.json (+ .err); give --full for the
+#                                      roofline and parity figures the step prints
 #   prof:<name>:<bench.py args>        rocprofv3 --kernel-trace --stats of a bench command (one stream)
 #                                      -> <outdir>/kernel_stats_<name>.csv
 #   pmc:<name>:<counters>:<bench args> one rocprofv3 --pmc pass -> <outdir>/pmc_<name>.csv

@@ -11,7 +11,7 @@ WL=${WL:-c2}
 MFMA_PMC=${MFMA_PMC:-"SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU_MFMA_BF16 GRBM_GUI_ACTIVE"}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-BENCH="bench.py --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing --no-c4-ref"
+BENCH="bench.py --full --workload $WL --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing --no-c4-ref"
 # per-kernel evidence on ONE stream (the TS-VAD forward otherwise runs the CAM++ trunk and the conformer stack
 # as two concurrent window slices, whose kernels share the GPU): matches bench.py's single-stream profiled step
 export SDIAR_CAM_ONE_STREAM=1
