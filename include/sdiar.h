@@ -61,7 +61,9 @@ typedef struct sd_tsvad sd_tsvad;
 
 typedef struct {
   int variant;                    /* 0: speech_encoder_type "CAM++", single/multi_backend "transformer"
-                                     1: "CAM++_ots_vad", "conformer_ots_vad", "lstm_ots_vad", ots_vad_style "v1" */
+                                     1: "CAM++_ots_vad", "conformer_ots_vad", "lstm_ots_vad", ots_vad_style "v1"
+                                     2: "resnet34_wespeaker" (ResNet34 trunk + SpeechFeatUpsample2 transposed-conv
+                                        upsampler, model.py:114-134, 584-606), single/multi_backend "transformer" */
   int max_num_speaker;            /* TSVADDataConfig.max_num_speaker (4)                     */
   int rs_len;                     /* seconds; PositionalEncoding max_len = rs_len * 25       */
   int max_batch;                  /* workspace sizing                                        */
@@ -104,7 +106,8 @@ int64_t sd_tsvad_device_bytes(const sd_tsvad* h);
 /* Diagnostics only (not on the product path, which launches directly): capture sd_tsvad_forward once into a
  * hipGraph, optionally write its DOT dump to `dot_path`, replay it `replays` times on `stream` (each replay
  * rewrites logits) and wait; and the device buffers of the forward's stages (which: 0 mix, 1 mixg, 2 X2,
- * 3 H, 4 Y) for stage-by-stage comparisons. */
+ * 3 H, 4 Y) for stage-by-stage comparisons.  Variant 2: which 0 is the upsampler output (B, 2 T', speaker_embed_dim)
+ * channel-last, the transposed conv + bias before its BatchNorm1D + ReLU, T' the trunk's frame count. */
 int sd_tsvad_forward_graph(sd_tsvad* h, const float* ref_speech, const float* target_speech, int B, int T_fbank,
                            int T_label, float* logits, int replays, const char* dot_path, void* stream);
 int sd_tsvad_debug_buffer(const sd_tsvad* h, int which, void** ptr, int64_t* bytes);
@@ -457,6 +460,14 @@ int sd_op_conv1d(const float* x, int B, int T, int Cin, const float* w, const fl
 /* nn.Conv2d (Cin % 32 == 0) on NHWC x (B, H, W, Cin), weight (Cout, Cin, kh, kw) -> NHWC out. */
 int sd_op_conv2d(const float* x, int B, int H, int W, int Cin, const float* w, int Cout, int kh,
                  int kw, int sh, int sw, int ph, int pw, float* out, int precision, void* stream);
+/* One 3x3, pad-1 convolution of the ResNet34 trunk on a bf16 NHWC map x (B, H, W, Cin), weight fp32 (Cout, Cin, 3, 3)
+ * (rounded to bf16), Cin and Cout in {32, 64, 128, 256}, stride 1 or 2 (both axes): out bf16 NHWC (B, Ho, Wo, Cout) =
+ * relu(conv * alpha + beta [+ res]), res bf16 NHWC like out or NULL.  sc_w (Cout, Cin, 1, 1) or NULL: the block's
+ * 1x1 shortcut at the same stride, sc_out bf16 = conv1x1 * sc_alpha + sc_beta (no ReLU).  use_generic 0: res_conv.hip
+ * (the shortcut from the centre tap of the same launch); 1: the same arguments through conv_gemm. */
+int sd_op_res_conv(const void* x, int B, int H, int W, int Cin, const float* w, int Cout, int stride,
+                   const float* alpha, const float* beta, const void* res, const float* sc_w, const float* sc_alpha,
+                   const float* sc_beta, void* out, void* sc_out, int use_generic, void* stream);
 /* Attention core on packed qkv (S*T, 3D) -> out (S*T, D). */
 int sd_op_attention(const float* qkv, int S, int T, int D, int nh, int causal, int causal_delay,
                     const int* key_len, float* out, int precision, void* stream);

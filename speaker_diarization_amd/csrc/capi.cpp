@@ -136,7 +136,7 @@ int sd_probe_lstm_handoff(int steps, float* us_per_step, void* stream) {
 int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
-    SD_CHECK(c->variant == 0 || c->variant == 1, sd::kErrInvalid, "unknown TS-VAD variant");
+    SD_CHECK(c->variant >= 0 && c->variant <= 2, sd::kErrInvalid, "unknown TS-VAD variant");
     SD_CHECK(c->precision >= 0 && c->precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
     SD_CHECK(c->max_batch > 0 && c->max_fbank_frames > 0, sd::kErrInvalid, "bad workspace sizes");
     SD_CHECK(c->max_num_speaker > 0 && c->num_transformer_layer >= 1 && c->transformer_ffn_embed_dim > 0 &&
@@ -829,6 +829,43 @@ int sd_op_conv2d(const float* x, int B, int H, int W, int Cin, const float* w, i
     p.out = out; p.o_sb = (int64_t)p.Ho * p.Wo * Cout; p.o_sh = (int64_t)p.Wo * Cout; p.o_sw = Cout;
     p.o_sn = 1;
     sd::conv_gemm(p, bf, st);
+  });
+}
+
+int sd_op_res_conv(const void* x, int B, int H, int W, int Cin, const float* w, int Cout, int stride,
+                   const float* alpha, const float* beta, const void* res, const float* sc_w, const float* sc_alpha,
+                   const float* sc_beta, void* out, void* sc_out, int use_generic, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && w && out && B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2), sd::kErrInvalid,
+             "res_conv: bad argument");
+    SD_CHECK(!sc_w || (sc_alpha && sc_beta && sc_out), sd::kErrInvalid, "res_conv: incomplete shortcut");
+    Scratch wt((size_t)Cout * Cin * 9 * 2, st), swt((size_t)Cout * Cin * 2, st);
+    sd::pack_weight(w, Cout, Cin, 9, wt.p, true, st);
+    if (sc_w) sd::pack_weight(sc_w, Cout, Cin, 1, swt.p, true, st);
+    sd::ConvGemmArgs p;
+    p.A = x; p.a_bf16 = true; p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.lda = Cin;
+    p.kh = 3; p.kw = 3; p.sh = stride; p.sw = stride; p.ph = 1; p.pw = 1;
+    p.Ho = (H - 1) / stride + 1;
+    p.Wo = (W - 1) / stride + 1;
+    p.Wt = wt.p; p.N = Cout; p.K = 9 * Cin;
+    p.alpha = alpha; p.beta = beta; p.act = sd::kActRelu;
+    p.res = res; p.res_bf16 = true; p.res_ld = Cout;
+    p.out = out; p.out_bf16 = true;
+    p.o_sb = (int64_t)p.Ho * p.Wo * Cout; p.o_sh = (int64_t)p.Wo * Cout; p.o_sw = Cout; p.o_sn = 1;
+    if (!use_generic) {
+      sd::ResFuse f;
+      if (sc_w) { f.sc_w = swt.p; f.sc_alpha = sc_alpha; f.sc_beta = sc_beta; f.sc_out = sc_out; }
+      sd::res_conv3x3(p, f, st);   // raises on arguments the kernel cannot compute
+      return;
+    }
+    sd::conv_gemm(p, true, st);
+    if (sc_w) {
+      sd::ConvGemmArgs q = p;
+      q.kh = 1; q.kw = 1; q.ph = 0; q.pw = 0; q.Wt = swt.p; q.K = Cin;
+      q.alpha = sc_alpha; q.beta = sc_beta; q.act = sd::kActNone; q.res = nullptr; q.out = sc_out;
+      sd::conv_gemm(q, true, st);
+    }
   });
 }
 

@@ -111,6 +111,18 @@ struct FcmFuse {
 };
 bool fcm_fused_supported(const ConvGemmArgs& p, const FcmFuse& f);
 void conv_fcm3x3_fused(const ConvGemmArgs& p, const FcmFuse& f, hipStream_t st);
+// ResNet34 trunk 3x3 convs (res_conv.hip): bf16 NHWC in, pad 1, stride 1 or 2 in BOTH axes, Cin / Cout in
+// {32, 64, 128, 256}, folded BN + optional bf16 residual + ReLU (NaN kept), bf16 out (NHWC as 16-B stores, or any
+// o_s* strides per element).  ResFuse: the block's 1x1 shortcut at the same stride (+ its BN, no ReLU) from the
+// centre tap's staged pixels, stored NHWC to sc_out.
+struct ResFuse {
+  const void* sc_w = nullptr;                 // packed bf16 Wt[Cout][Cin]
+  const float *sc_alpha = nullptr, *sc_beta = nullptr;
+  void* sc_out = nullptr;                     // bf16 NHWC (B, Ho, Wo, Cout)
+};
+bool res_conv_runs(const ConvGemmArgs& p);        // the kernel can compute p
+bool res_conv_supported(const ConvGemmArgs& p);   // ... and measured faster than conv_gemm on p's shape class
+void res_conv3x3(const ConvGemmArgs& p, const ResFuse& f, hipStream_t st);
 void conv_gemm_dma(const ConvGemmArgs& p, hipStream_t st);     // LDS-DMA fed variant
 bool gemm_areg_supported(const ConvGemmArgs& p);             // bf16 A linear, K in {192,256,384}, N % 64 == 0, N >= 768
 void conv_gemm_areg(const ConvGemmArgs& p, hipStream_t st);

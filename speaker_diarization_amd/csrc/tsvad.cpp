@@ -9,6 +9,9 @@
 //   variant 1 (forward_common_ots_vad, model.py:669-756):
 //     -> GSP + gsp_fc -> [ts_embed | mix] -> 6-layer Conformer per speaker
 //     -> BiLSTM(1536 -> 2x256) -> fc
+//   variant 2 (speech_encoder_type resnet34_wespeaker, model.py:584-606): the speech encoder is the ResNet34
+//     trunk (resnet.h) -> SpeechFeatUpsample2 transposed conv + BN + ReLU (model.py:114-134); then variant 0's
+//     back end
 //   -> logits (B, NS, T_lab)
 // All activations are fp32 channel-last; every contraction is conv_gemm (bf16 or
 // exact-f32 MFMA), eval BatchNorms are folded into GEMM prologues/epilogues.
@@ -28,11 +31,15 @@ void TsvadModel::finalize() {
   SD_CHECK(cfg_.speaker_embed_dim * 2 == cfg_.embed_dim, kErrInvalid,
            "proj_layer (speaker_embed_dim*2 != transformer_embed_dim) is not supported");
   const std::string se = "speech_encoder.";
-  cam_.load(ps_, arena_, se, cfg_.bf16);   // cam_pplus_wespeaker.py:271-372
-  // The pooled embedding head (stats + dense) is not on the get_time_out path.
-  for (const char* k : {"xvector.dense.linear.weight", "xvector.dense.nonlinear.batchnorm.running_mean",
-                        "xvector.dense.nonlinear.batchnorm.running_var"})
-    ps_.mark(se + k);
+  if (cfg_.variant == 2) {
+    res_.load(ps_, arena_, se, cfg_.bf16);   // resnet_wespeaker.py:108-171
+  } else {
+    cam_.load(ps_, arena_, se, cfg_.bf16);   // cam_pplus_wespeaker.py:271-372
+    // The pooled embedding head (stats + dense) is not on the get_time_out path.
+    for (const char* k : {"xvector.dense.linear.weight", "xvector.dense.nonlinear.batchnorm.running_mean",
+                          "xvector.dense.nonlinear.batchnorm.running_var"})
+      ps_.mark(se + k);
+  }
   // ---- speech_down_or_up (model.py:385-395)
   // BatchNorm1D (model.py:161-171) is not folded into the conv: a batch holding a NaN skips it, so the conv
   // stores conv + bias and its consumer applies BN + ReLU, or ReLU alone for such a batch (BnRelu)
@@ -44,12 +51,39 @@ void TsvadModel::finalize() {
     r.b = arena_.upload(sh);
     return r;
   };
-  down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
-  down_bn_ = bn_only("speech_down_or_up.1.bn");
-  down_.pre_s = cam_.out_s();
-  down_.pre_h = cam_.out_h();
+  if (cfg_.variant == 2) {
+    // SpeechFeatUpsample2.up (model.py:118-125), weight (2560, D, 5): output o = 2 i - 2 + k, so
+    //   even y[2j]   = w[..4] x[j-1] + w[..2] x[j] + w[..0] x[j+1]
+    //   odd  y[2j+1] =                 w[..3] x[j] + w[..1] x[j+1]
+    // i.e. taps (x[j-1], x[j], x[j+1]) of a k-3 pad-1 conv with the phases stacked on the output channels
+    const HostTensor& w = ps_.get("speech_down_or_up.up.weight");
+    const HostTensor& ub = ps_.get("speech_down_or_up.up.bias");
+    const int C = ResTrunk::kChannels, D = cfg_.speaker_embed_dim;
+    SD_CHECK(w.shape.size() == 3 && w.shape[0] == C && w.shape[1] == D && w.shape[2] == 5, kErrParam,
+             "speech_down_or_up.up.weight must be (2560, speaker_embed_dim, 5)");
+    SD_CHECK(ub.numel() == D, kErrParam, "speech_down_or_up.up.bias size");
+    std::vector<float> wt((size_t)2 * D * 3 * C, 0.f), bias((size_t)2 * D);
+    const int even_k[3] = {4, 2, 0}, odd_k[3] = {-1, 3, 1};
+    for (int n = 0; n < D; ++n) {
+      for (int t = 0; t < 3; ++t)
+        for (int c = 0; c < C; ++c) {
+          const float* wc = w.data.data() + ((size_t)c * D + n) * 5;
+          wt[((size_t)n * 3 + t) * C + c] = wc[even_k[t]];
+          if (odd_k[t] >= 0) wt[((size_t)(D + n) * 3 + t) * C + c] = wc[odd_k[t]];
+        }
+      bias[n] = bias[D + n] = ub.data[n];
+    }
+    down_.w = upload_packed(arena_, wt, 2 * D, C, 1, 3, cfg_.bf16);
+    down_.beta = arena_.upload(bias);
+    down_bn_ = bn_only("speech_down_or_up.batchnorm.bn");
+  } else {
+    down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
+    down_bn_ = bn_only("speech_down_or_up.1.bn");
+    down_.pre_s = cam_.out_s();
+    down_.pre_h = cam_.out_h();
+  }
 
-  if (cfg_.variant == 0) {
+  if (cfg_.variant == 0 || cfg_.variant == 2) {
     const HostTensor& pe = ps_.get("pos_encoder.pe");
     SD_CHECK(pe.shape.size() == 3 && pe.shape[2] == cfg_.embed_dim, kErrParam, "pos_encoder.pe shape");
     pe_len_ = (int)pe.shape[0];
@@ -100,10 +134,11 @@ void TsvadModel::finalize() {
 
 void TsvadModel::alloc_workspace() {
   const int64_t Bm = cfg_.max_batch, Tf = cfg_.max_fbank_frames;
-  const int64_t T2 = (Tf - 1) / 2 + 1, T3 = (T2 - 1) / 2 + 1;
+  const int64_t T3 = mix_frames((int)Tf);
   const int64_t Tl = std::max<int64_t>(T3 + 3, (int64_t)cfg_.rs_len * 25);
   const int64_t NS = cfg_.max_num_speaker, E = cfg_.embed_dim;
-  cam_.alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
+  if (cfg_.variant == 2) res_.alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
+  else cam_.alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
   mix_ = ws(Bm * T3 * cfg_.speaker_embed_dim);
   mixg_ = ws(Bm * T3 * cfg_.speaker_embed_dim);
   const int64_t rows = Bm * NS * Tl;
@@ -159,7 +194,7 @@ void TsvadModel::forward_graph(const float* ref, const float* ts, int B, int Tf,
 }
 
 void TsvadModel::debug_buffer(int which, void** ptr, int64_t* bytes) const {
-  const int64_t Bm = cfg_.max_batch, T3 = ((CamTrunk::out_frames(cfg_.max_fbank_frames)) - 1) / 2 + 1;
+  const int64_t Bm = cfg_.max_batch, T3 = mix_frames(cfg_.max_fbank_frames);
   const int64_t Tl = std::max<int64_t>(T3 + 3, (int64_t)cfg_.rs_len * 25), E = cfg_.embed_dim, SE = cfg_.speaker_embed_dim;
   const int64_t NS = cfg_.max_num_speaker;
   switch (which) {
@@ -170,6 +205,65 @@ void TsvadModel::debug_buffer(int which, void** ptr, int64_t* bytes) const {
     case 4: *ptr = Y_; *bytes = Bm * NS * Tl * E * 4; break;
     default: throw Error{kErrInvalid, "debug_buffer: unknown buffer"};
   }
+}
+
+// forward_common's back end from the mix embeddings on (model.py:856-897), shared by variants 0 and 2: mix_ holds
+// speech_down_or_up's conv + bias (B, T3, SE); its BatchNorm1D + ReLU are applied on load (sd_bn).
+void TsvadModel::transformer_backend(const float* ts, int T3, int B, int Tl, float* logits, hipStream_t st,
+                                     const BnRelu& sd_bn, const BnRelu& bd_bn, const int* win_fb, const int* win_ts) {
+  const bool bf = cfg_.bf16;
+  const int E = cfg_.embed_dim, SE = cfg_.speaker_embed_dim, NS = cfg_.max_num_speaker, S = B * NS;
+  // Per-speaker encoder over S = B*NS sequences (model.py:869-879).
+  build_speaker_input(ts, mix_, SE, T3, B, NS, Tl, SE, pe_, X_, st, sd_bn);
+  // bf16(X) for the first layer's in-projection too (every later layer gets it from the LayerNorms): an
+  // fp32 A operand would send that GEMM to the register-staged kernel (C4: 1.5 ms per 640 windows vs 0.3)
+  if (bf) f32_to_bf16(X_, (int64_t)S * Tl * E, enc_work().AO, st);
+  for (size_t i = 0; i < single_.size(); ++i)
+    run_transformer(single_[i], X_, S, Tl, E, cfg_.num_attention_head, nullptr, enc_work(), st, 0, 0, bf || i > 0);
+  speakers_to_channels(X_, B, NS, Tl, E, X2_, bf, st);
+  ConvGemmArgs p = cam_conv1d(Tens{X2_, bf}, B, Tl, NS * E, backend_down_, 1, 2, 1, Tens{X_, false}, E);
+  conv_gemm(p, bf, st);
+  add_pe(X_, B * Tl, Tl, E, E, pe_, st, bd_bn);   // backend_down's BatchNorm1D + ReLU, then the PE
+  if (bf) f32_to_bf16(X_, (int64_t)B * Tl * E, enc_work().AO, st);
+  for (size_t i = 0; i < multi_.size(); ++i)
+    run_transformer(multi_[i], X_, B, Tl, E, cfg_.num_attention_head, nullptr, enc_work(), st, 0, 0, bf || i > 0);
+  ConvGemmArgs f = cam_conv1d(Tens{X_, false}, B, Tl, E, fc_, 1, 0, 1, Tens{logits, false}, 1);
+  f.o_sb = (int64_t)NS * Tl; f.o_sw = 1; f.o_sn = Tl;
+  conv_gemm(f, bf, st);
+  poison_windows(logits, B, (int64_t)NS * Tl, win_fb, win_ts, st);
+}
+
+// Variant 2: ResNet34 trunk (two window slices on two streams for large batches, like CAM++), the transposed-conv
+// upsampler as one conv_gemm, then the transformer back end.
+void TsvadModel::forward_resnet(const float* ref, const float* ts, int B, int Tf, int Tl, float* logits,
+                                hipStream_t st, bool two, const BnRelu& sd_bn, const BnRelu& bd_bn,
+                                const int* win_fb, const int* win_ts) {
+  const bool bf = cfg_.bf16;
+  const int SE = cfg_.speaker_embed_dim;
+  const int T4 = ResTrunk::out_frames(Tf), T3 = 2 * T4;
+  // model.py:849-854; the reference's own -1 branch raises too (its pad call is misspelt: AttributeError)
+  SD_CHECK(T3 - Tl <= 2 && T3 - Tl >= -1, kErrShape,
+           "label and ref_speech(mix speech) diff: " + std::to_string(T3 - Tl));
+  SD_CHECK(T3 - Tl != -1, kErrShape,
+           "label and ref_speech(mix speech) diff: -1 (the reference raises here: module 'torch.nn' has no "
+           "attribute 'functinal')");
+  SD_CHECK(Tl <= pe_len_, kErrShape, "label length exceeds positional-encoding max_len");
+  Tens x4;
+  if (two) {
+    const int B1 = B / 2;
+    SD_HIP(hipEventRecord(ev_fork_, st));
+    SD_HIP(hipStreamWaitEvent(side_, ev_fork_, 0));
+    x4 = res_.forward(ref, B1, Tf, st, 0);
+    (void)res_.forward(ref, B - B1, Tf, side_, B1);
+    SD_HIP(hipEventRecord(ev_join_, side_));
+    SD_HIP(hipStreamWaitEvent(st, ev_join_, 0));
+  } else {
+    x4 = res_.forward(ref, B, Tf, st);
+  }
+  // (B, T4, 2560) -> (B, T4, [y[2j] | y[2j+1]]) = (B, 2 T4, SE): conv + bias; BatchNorm1D + ReLU by the consumer
+  ConvGemmArgs up = cam_conv1d(x4, B, T4, ResTrunk::kChannels, down_, 1, 1, 1, Tens{mix_, false}, 2 * SE);
+  conv_gemm(up, bf, st);
+  transformer_backend(ts, T3, B, Tl, logits, st, sd_bn, bd_bn, win_fb, win_ts);
 }
 
 // Direct launches.  A hipGraph replay of this forward (forward_graph above) measured no faster on C2 (34.3 vs
@@ -214,12 +308,16 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   int* grp_bd = nonfinite_ + 3 * cfg_.max_batch;
   zero_fill(nonfinite_, 4 * (size_t)cfg_.max_batch * sizeof(int), st);
   nonfinite_windows(ref, B, (int64_t)Tf * 80, G, win_fb, grp_sd, grp_bd, st);
-  nonfinite_windows(ts, B, (int64_t)NS * SE, G, win_ts, nullptr, cfg_.variant == 0 ? grp_bd : nullptr, st);
+  nonfinite_windows(ts, B, (int64_t)NS * SE, G, win_ts, nullptr, cfg_.variant != 1 ? grp_bd : nullptr, st);
   if (force & 1) fill_u32(grp_sd, (size_t)cfg_.max_batch * sizeof(int), 1u, st);
   if (force & 3) fill_u32(grp_bd, (size_t)cfg_.max_batch * sizeof(int), 1u, st);
   BnRelu sd_bn = down_bn_, bd_bn = backend_bn_;
   sd_bn.grp = grp_sd; sd_bn.group = G;
   bd_bn.grp = grp_bd; bd_bn.group = G;
+  if (cfg_.variant == 2) {
+    forward_resnet(ref, ts, B, Tf, Tl, logits, st, two, sd_bn, bd_bn, win_fb, win_ts);
+    return;
+  }
   // speech_down_or_up conv geometry (its output frame count T3)
   const int T3 = cam_conv1d(Tens{nullptr, bf}, 1, T2, CamTrunk::kChannels, down_, 2, 2, 1, Tens{mix_, false}, SE).Wo;
   const bool fused_v1 = cfg_.variant == 1 && SE == 192 && E == 2 * SE && conformer_stack_fused(conf_, E, bf);
@@ -285,24 +383,7 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
     SD_CHECK(T3 - Tl <= 2 && T3 - Tl >= -1, kErrShape,
              "label and ref_speech(mix speech) diff: " + std::to_string(T3 - Tl));
     SD_CHECK(Tl <= pe_len_, kErrShape, "label length exceeds positional-encoding max_len");
-    // Per-speaker encoder over S = B*NS sequences (model.py:869-879).
-    build_speaker_input(ts, mix_, SE, T3, B, NS, Tl, SE, pe_, X_, st, sd_bn);
-    // bf16(X) for the first layer's in-projection too (every later layer gets it from the LayerNorms): an
-    // fp32 A operand would send that GEMM to the register-staged kernel (C4: 1.5 ms per 640 windows vs 0.3)
-    if (bf) f32_to_bf16(X_, (int64_t)S * Tl * E, enc_work().AO, st);
-    for (size_t i = 0; i < single_.size(); ++i)
-      run_transformer(single_[i], X_, S, Tl, E, cfg_.num_attention_head, nullptr, enc_work(), st, 0, 0, bf || i > 0);
-    speakers_to_channels(X_, B, NS, Tl, E, X2_, bf, st);
-    ConvGemmArgs p = cam_conv1d(Tens{X2_, bf}, B, Tl, NS * E, backend_down_, 1, 2, 1, Tens{X_, false}, E);
-    conv_gemm(p, bf, st);
-    add_pe(X_, B * Tl, Tl, E, E, pe_, st, bd_bn);   // backend_down's BatchNorm1D + ReLU, then the PE
-    if (bf) f32_to_bf16(X_, (int64_t)B * Tl * E, enc_work().AO, st);
-    for (size_t i = 0; i < multi_.size(); ++i)
-      run_transformer(multi_[i], X_, B, Tl, E, cfg_.num_attention_head, nullptr, enc_work(), st, 0, 0, bf || i > 0);
-    ConvGemmArgs f = cam_conv1d(Tens{X_, false}, B, Tl, E, fc_, 1, 0, 1, Tens{logits, false}, 1);
-    f.o_sb = (int64_t)NS * Tl; f.o_sw = 1; f.o_sn = Tl;
-    conv_gemm(f, bf, st);
-    poison_windows(logits, B, (int64_t)NS * Tl, win_fb, win_ts, st);
+    transformer_backend(ts, T3, B, Tl, logits, st, sd_bn, bd_bn, win_fb, win_ts);
     return;
   }
   SD_CHECK(std::abs(T3 - Tl) <= 3, kErrShape, "label and ref_speech(mix speech) diff: " + std::to_string(T3 - Tl));

@@ -2,11 +2,13 @@
 #pragma once
 #include <vector>
 #include "campp.h"
+#include "resnet.h"
 
 namespace sd {
 
 struct TsvadConfig {
-  int variant = 0;            // 0: CAM++ + transformer (model.py:758-897); 1: CAM++_ots_vad (669-756)
+  int variant = 0;            // 0: CAM++ + transformer (model.py:758-897); 1: CAM++_ots_vad (669-756);
+                              // 2: resnet34_wespeaker + SpeechFeatUpsample2 + transformer (584-606, 114-134)
   int max_num_speaker = 4;
   int rs_len = 4;
   int max_batch = 64;
@@ -59,6 +61,10 @@ class TsvadModel {
   LayerLoader loader() { return LayerLoader{ps_, arena_, cfg_.bf16}; }
   EncoderWork enc_work() const { return EncoderWork{Y_, QKV_, AO_, H_, partial_, cfg_.bf16}; }
   void alloc_workspace();
+  void transformer_backend(const float* ts, int T3, int B, int Tl, float* logits, hipStream_t st, const BnRelu& sd_bn,
+                           const BnRelu& bd_bn, const int* win_fb, const int* win_ts);
+  void forward_resnet(const float* ref, const float* ts, int B, int Tf, int Tl, float* logits, hipStream_t st,
+                      bool two, const BnRelu& sd_bn, const BnRelu& bd_bn, const int* win_fb, const int* win_ts);
   float* ws(size_t n) { return static_cast<float*>(arena_.alloc(n * sizeof(float))); }
 
   TsvadConfig cfg_;
@@ -67,8 +73,16 @@ class TsvadModel {
   PinnedFlags lstm_err_;   // poll-timeout reports of the persistent LSTMs (lstm.hip), one slot each
   bool finalized_ = false;
 
-  CamTrunk cam_;     // speech_encoder.* (CAM++ get_time_out=True)
-  ConvL down_;        // speech_down_or_up conv: epilogue = + bias only (its BatchNorm1D is down_bn_)
+  CamTrunk cam_;     // speech_encoder.* (CAM++ get_time_out=True), variants 0 and 1
+  ResTrunk res_;     // speech_encoder.* (ResNet34 get_time_out=True), variant 2
+  // frames of the speech_down_or_up output for T_fb fbank frames (the conv's stride 2, or the upsampler's 2 T')
+  int mix_frames(int Tf) const {
+    return cfg_.variant == 2 ? 2 * ResTrunk::out_frames(Tf) : (CamTrunk::out_frames(Tf) - 1) / 2 + 1;
+  }
+  // speech_down_or_up conv: epilogue = + bias only (its BatchNorm1D is down_bn_).  Variant 2: the transposed conv
+  // ConvTranspose1d(2560 -> D, k5, stride 2, pad 2, output_padding 1) as ONE k-3 pad-1 conv with 2 D outputs per
+  // input frame j, [even phase y[2j] | odd phase y[2j+1]] = two consecutive rows of the (B, 2 T', D) output.
+  ConvL down_;
   BnRelu down_bn_, backend_bn_;   // folded BatchNorms, applied (or bypassed) by the consumers
   int* nonfinite_ = nullptr;      // [win_fbank B | win_ts B | grp_speech B | grp_backend B]
   const float *gsp_w_ = nullptr, *gsp_b_ = nullptr;

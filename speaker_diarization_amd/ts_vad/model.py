@@ -123,7 +123,7 @@ class TSVADModel:
                 for g0 in range(0, B, G):
                     g1 = min(B, g0 + G)
                     force = 3 if not bool(torch.isfinite(ref[g0:g1]).all()) else 0
-                    if self.cfg.variant == 0 and not bool(torch.isfinite(ts[g0:g1]).all()):
+                    if self.cfg.variant != 1 and not bool(torch.isfinite(ts[g0:g1]).all()):
                         force |= 2
                     for s in range(g0, g1, self.max_batch):
                         e = min(g1, s + self.max_batch)

@@ -49,6 +49,9 @@ class TSVADConfig:
                     "CAM++_ots_vad", "conformer_ots_vad", "lstm_ots_vad"):
                 raise ValueError("ots_vad_style v1 is built for CAM++_ots_vad + conformer_ots_vad + lstm_ots_vad")
             return 1
+        if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) == (
+                "resnet34_wespeaker", "transformer", "transformer"):
+            return 2
         if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) != (
                 "CAM++", "transformer", "transformer"):
             raise ValueError(
@@ -121,6 +124,28 @@ def campplus_layout(prefix: str = "speech_encoder.", embedding_size: int = 192) 
     return k
 
 
+def resnet34_layout(prefix: str = "speech_encoder.") -> list:
+    """Key layout of ResNet34(feat_dim=80, embed_dim=256, speech_encoder=True) (resnet_wespeaker.py:108-154,
+    198-208): BasicBlocks [3, 4, 6, 3] at 32/64/128/256 channels, no pool / seg_1 (the TS-VAD speech encoder,
+    model.py:584-606).  The conv / BN init kinds keep the seeded activations O(1) through the 16 residual blocks."""
+    k: list = []
+    k.append((prefix + "conv1.weight", (32, 1, 3, 3), "rn_conv"))
+    _bn(k, prefix + "bn1", 32)
+    cin = 32
+    for layer, (planes, n) in enumerate(((32, 3), (64, 4), (128, 6), (256, 3)), start=1):
+        for blk in range(n):
+            q = f"{prefix}layer{layer}.{blk}."
+            k.append((q + "conv1.weight", (planes, cin, 3, 3), "rn_conv"))
+            _bn(k, q + "bn1", planes)
+            k.append((q + "conv2.weight", (planes, planes, 3, 3), "rn_conv2"))
+            _bn(k, q + "bn2", planes)
+            if blk == 0 and layer > 1:
+                k.append((q + "shortcut.0.weight", (planes, cin, 1, 1), "rn_sc"))
+                _bn(k, q + "shortcut.1", planes)
+            cin = planes
+    return k
+
+
 def _mha(k: list, p: str, e: int):
     k.append((p + "in_proj_weight", (3 * e, e), "xavier"))
     k.append((p + "in_proj_bias", (3 * e,), "small"))
@@ -136,14 +161,21 @@ def _ln(k: list, p: str, e: int):
 def tsvad_layout(cfg: TSVADConfig) -> list:
     """Key layout of TSVADModel(cfg) (ts_vad2/model.py:179-367)."""
     e, se, ns = cfg.transformer_embed_dim, cfg.speaker_embed_dim, cfg.max_num_speaker
-    k = campplus_layout()
-    if cfg.variant == 1:
-        k.append(("gsp_fc.weight", (se, 2), "linear"))
-        k.append(("gsp_fc.bias", (se,), "small"))
-    k.append(("speech_down_or_up.0.weight", (se, 512, 5), "conv1d"))
-    k.append(("speech_down_or_up.0.bias", (se,), "small"))
-    _bn(k, "speech_down_or_up.1.bn", se)
-    if cfg.variant == 0:
+    if cfg.variant == 2:
+        # ResNet34 + SpeechFeatUpsample2 (model.py:114-134, 584-606); the back end is variant 0's
+        k = resnet34_layout()
+        k.append(("speech_down_or_up.up.weight", (2560, se, 5), "convT"))
+        k.append(("speech_down_or_up.up.bias", (se,), "small"))
+        _bn(k, "speech_down_or_up.batchnorm.bn", se)
+    else:
+        k = campplus_layout()
+        if cfg.variant == 1:
+            k.append(("gsp_fc.weight", (se, 2), "linear"))
+            k.append(("gsp_fc.bias", (se,), "small"))
+        k.append(("speech_down_or_up.0.weight", (se, 512, 5), "conv1d"))
+        k.append(("speech_down_or_up.0.bias", (se,), "small"))
+        _bn(k, "speech_down_or_up.1.bn", se)
+    if cfg.variant in (0, 2):
         k.append(("pos_encoder.pe", (cfg.rs_len * cfg.label_rate, 1, e), "pe"))
         for i in range(cfg.num_transformer_layer):
             _tfm(k, f"single_backend.layers.{i}.", e, cfg.transformer_ffn_embed_dim)
@@ -207,6 +239,15 @@ def sinusoid_pe(max_len: int, d: int) -> np.ndarray:
     return pe
 
 
+# Seeded ResNet34 init (resnet34_layout): He-normal keeps the ReLU branch at its input's scale; the block's second
+# conv is damped so the residual sum grows by ~(1 + g^2) in variance per block instead of doubling over 16 blocks
+# (trunk maximum ~9 on the golden inputs), and the transposed conv is scaled so the mix embeddings it feeds the back
+# end are O(1) like the CAM++ variants' (mean ~0.5, maximum ~5): tests/golden/make_golden_resnet.py asserts the
+# reference run of the seeded model is alive.
+RN_GAIN = {"rn_conv": 1.0, "rn_conv2": 0.3, "rn_sc": 0.7}
+CONVT_GAIN = 0.5
+
+
 def _init(rng: np.random.Generator, shape: Shape, kind: str) -> np.ndarray:
     if kind == "nbt":
         return np.array(0, dtype=np.int64)
@@ -222,6 +263,10 @@ def _init(rng: np.random.Generator, shape: Shape, kind: str) -> np.ndarray:
     elif kind == "linear":
         b = 1.0 / np.sqrt(fan_in)
         v = rng.uniform(-b, b, n)
+    elif kind in RN_GAIN:                 # ResNet34 convs: He-normal times a per-role gain
+        v = rng.standard_normal(n) * (RN_GAIN[kind] * np.sqrt(2.0 / fan_in))
+    elif kind == "convT":                 # ConvTranspose1d (Cin, Cout, k), stride 2: Cin * k / 2 taps per output
+        v = rng.standard_normal(n) * (CONVT_GAIN * np.sqrt(2.0 / (shape[0] * shape[2] / 2.0)))
     elif kind == "xavier":
         b = np.sqrt(6.0 / (shape[0] / 3 + shape[1]))
         v = rng.uniform(-b, b, n)
@@ -320,7 +365,7 @@ def dynamic_weights(sd, cfg: TSVADConfig, c: Dict[str, np.ndarray], stage: int =
             return out
         mean = c["v1_logit_mean"]
     else:
-        if cfg.rs_len != 4:
+        if cfg.rs_len != 4 or cfg.variant != 0:
             raise ValueError("the dynamic variant is calibrated for the CAM++/transformer model at rs_len 4")
         mean = c["v0_logit_mean"]
     out["fc.weight"] = (f64("fc.weight") * DYN_FC_GAIN).astype(np.float32)
@@ -341,7 +386,7 @@ SPREAD = {(1, 6): (8.0, 0.0), (0, 4): (16.0, 2.0)}
 
 def spread_fc(sd, cfg: TSVADConfig, seed: int = 777):
     """logit'_s = k_s (logit_s - mean_s) + c, k_s = std / std_s: only fc.weight / fc.bias change."""
-    key = (1 if cfg.ots_vad_style == "v1" else 0, cfg.rs_len)
+    key = (cfg.variant, cfg.rs_len)
     if seed != 777 or key not in SPREAD_FC:
         raise ValueError(f"no spread calibration for variant/rs_len {key} seed {seed}")
     c = SPREAD_FC[key]
