@@ -73,7 +73,11 @@ typedef struct {
   int num_attention_head;
   int transformer_embed_dim;
   int transformer_ffn_embed_dim;
-  int speaker_embed_dim;
+  int speaker_embed_dim;          /* 192; any other multiple of 8 with 2 * speaker_embed_dim != transformer_embed_dim
+                                     (256 for ResNet34 embeddings, run_ts_vad2.sh:3684) adds proj_layer =
+                                     nn.Linear(2 * speaker_embed_dim, transformer_embed_dim) (model.py:212-217,
+                                     873-874), variants 0 and 2 only: the reference's ots_vad forward never applies
+                                     it (model.py:730-731), so variant 1 is refused at create */
 } sd_tsvad_config;
 
 int sd_tsvad_create(const sd_tsvad_config* cfg, sd_tsvad** out);
@@ -174,6 +178,41 @@ int sd_campp_finalize(sd_campp* h);
 int sd_campp_forward(sd_campp* h, const float* feats, int B, int T, float* emb, float* time_out, void* stream);
 int64_t sd_campp_device_bytes(const sd_campp* h);
 int sd_campp_destroy(sd_campp* h);
+
+/* ------------------------------------------------------------------ ResNet34 embeddings
+ * Replaces ResNet34(feat_dim=80, embed_dim, pooling_func="TSTP", two_emb_layer, speech_encoder=False)
+ * (egs/alimeeting/ts_vad2/resnet_wespeaker.py:108-183, 198-208) as the target-speaker embedding extractor of
+ * generate_chunk_speaker_embedding_from_wespeaker_for_diarization.py:
+ *   construction  :116-117 (embed_dim 256, two_emb_layer False)
+ *   forward(x)    :131-133 (the last element of the returned tuple) / resnet_wespeaker.py:156-183
+ * State-dict keys are the standalone module's (conv1.*, bn1.*, layer1..4.*, seg_1.*[, seg_bn_1.*, seg_2.*]); TSTP
+ * (pooling_layers_wespeaker.py:66-88) has no parameters, so a pool.* key is unexpected. */
+typedef struct sd_resnet34 sd_resnet34;
+
+typedef struct {
+  int feat_dim;        /* 80 */
+  int embed_dim;       /* 256 (a multiple of 8) */
+  int two_emb_layer;   /* 0: embed_a = seg_1(stats); 1: also embed_b = seg_2(seg_bn_1(relu(embed_a))) */
+  int max_batch;       /* workspace: chunks per forward (extract_embed batch_size 96)      */
+  int max_frames;      /* workspace: fbank frames per chunk (598 for 6 s)                  */
+  int precision;       /* 0: fp32 (exact-f32 MFMA), 1: bf16 trunk (TSTP and the seg layers stay fp32) */
+} sd_resnet34_config;
+
+/* resnet_wespeaker.py:109-146 */
+int sd_resnet34_create(const sd_resnet34_config* cfg, sd_resnet34** out);
+/* load_state_dict (generate_chunk_..._wespeaker_...py:125; strict here) */
+int sd_resnet34_set_param(sd_resnet34* h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+int sd_resnet34_finalize(sd_resnet34* h);
+/* resnet_wespeaker.py:156-183.  feats: device (B, T, 80) fbank; emb: device (B, embed_dim) or NULL, the last
+ * element of the reference's returned tuple (embed_b with two_emb_layer, else embed_a); emb_a: device (B, embed_dim)
+ * or NULL, seg_1's output (meaningful with two_emb_layer; without it, written only when emb is NULL); time_out:
+ * device (B, T', 2560) channel-last or NULL, T' = three times (n - 1) / 2 + 1 applied to T, channel c * 10 + f
+ * (forward(x, get_time_out=True) transposed).  T <= 8 (T' = 1) gives all-NaN embeddings like the reference;
+ * time_out needs T >= 8. */
+int sd_resnet34_forward(sd_resnet34* h, const float* feats, int B, int T, float* emb, float* emb_a, float* time_out,
+                        void* stream);
+int64_t sd_resnet34_device_bytes(const sd_resnet34* h);
+int sd_resnet34_destroy(sd_resnet34* h);
 
 /* ------------------------------------------------------------------ SSND
  * Replaces SSNDModel.infer (egs/alimeeting/ssnd/ssnd_model.py:752-776) with extractor
@@ -468,6 +507,20 @@ int sd_op_conv2d(const float* x, int B, int H, int W, int Cin, const float* w, i
 int sd_op_res_conv(const void* x, int B, int H, int W, int Cin, const float* w, int Cout, int stride,
                    const float* alpha, const float* beta, const void* res, const float* sc_w, const float* sc_alpha,
                    const float* sc_beta, void* out, void* sc_out, int use_generic, void* stream);
+/* TSTP (pooling_layers_wespeaker.py:66-88) on a channel-last map x (B, T, C), C % 64 == 0, fp32 or bf16 bits
+ * (x_bf16): stats (B, 2C) fp32 = [mean over T | sqrt(unbiased variance over T + 1e-7)].  A NaN stays in its
+ * channel; T == 1 gives NaN stds. */
+int sd_op_tstp_pool(const void* x, int x_bf16, int B, int T, int C, float* stats, void* stream);
+/* TS-VAD speaker input through proj_layer (model.py:212-217, 870-876), the stage of configurations with
+ * 2 * speaker_embed_dim != transformer_embed_dim: out[(b, spk, t), :] = w [ts[b, spk] | relu(bn(mix[b, t]))] + bias
+ * + pe[t], with w (E, 2 SE) split on its input axis (one GEMM over the B * NS embeddings, one over the B * Tmix mix
+ * frames, a combine pass).  ts (B, NS, SE); mix (B, Tmix, SE) = speech_down_or_up's conv + bias, rows t >= Tmix
+ * read as zeros; bn_a / bn_b (SE) the folded BatchNorm1D; grp (nullable) per-group bypass flags of `group`
+ * consecutive windows (ReLU only); pe (T, E) or NULL; out (B * NS * T, E) fp32; out_bf16 (nullable) its bf16
+ * copy.  SE and E multiples of 8.  precision 0 fp32, 1 bf16 operands, 2 bf16x3. */
+int sd_op_speaker_input_proj(const float* ts, const float* mix, int B, int NS, int T, int Tmix, int SE, int E,
+                             const float* w, const float* bias, const float* pe, const float* bn_a, const float* bn_b,
+                             const int* grp, int group, float* out, void* out_bf16, int precision, void* stream);
 /* Attention core on packed qkv (S*T, 3D) -> out (S*T, D). */
 int sd_op_attention(const float* qkv, int S, int T, int D, int nh, int causal, int causal_delay,
                     const int* key_len, float* out, int precision, void* stream);

@@ -85,6 +85,17 @@ class CamppConfig(ctypes.Structure):
     ]
 
 
+class Resnet34Config(ctypes.Structure):
+    _fields_ = [
+        ("feat_dim", c_int),
+        ("embed_dim", c_int),
+        ("two_emb_layer", c_int),
+        ("max_batch", c_int),
+        ("max_frames", c_int),
+        ("precision", c_int),
+    ]
+
+
 class SsndConfig(ctypes.Structure):
     _fields_ = [(n, c_int) for n in (
         "max_batch", "max_fbank_frames", "max_speakers", "feat_dim", "emb_dim", "q_det_aux_dim", "q_rep_aux_dim",
@@ -149,6 +160,12 @@ _SIGS = {
     "sd_campp_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_campp_device_bytes": (c_int64, [c_void_p]),
     "sd_campp_destroy": (c_int, [c_void_p]),
+    "sd_resnet34_create": (c_int, [POINTER(Resnet34Config), POINTER(c_void_p)]),
+    "sd_resnet34_set_param": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
+    "sd_resnet34_finalize": (c_int, [c_void_p]),
+    "sd_resnet34_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sd_resnet34_device_bytes": (c_int64, [c_void_p]),
+    "sd_resnet34_destroy": (c_int, [c_void_p]),
     "sd_eda_create": (c_int, [POINTER(EdaConfig), POINTER(c_void_p)]),
     "sd_eda_set_param": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
     "sd_eda_finalize": (c_int, [c_void_p]),
@@ -205,6 +222,10 @@ _SIGS = {
                              c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "sd_op_res_conv": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "sd_op_tstp_pool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sd_op_speaker_input_proj": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_int, c_void_p]),
     "sd_op_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                 c_void_p]),
     "sd_op_attention_grid": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,

@@ -15,6 +15,7 @@
 #include "fseend_stream.h"
 #include "tsvad.h"
 #include "campp.h"
+#include "resemb.h"
 #include "tsvad_stream.h"
 #include "ssnd.h"
 
@@ -36,6 +37,10 @@ struct sd_eda {
 
 struct sd_campp {
   std::unique_ptr<sd::CamppModel> model;
+};
+
+struct sd_resnet34 {
+  std::unique_ptr<sd::ResEmbModel> model;
 };
 
 struct sd_ssnd {
@@ -155,6 +160,7 @@ int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
     t.embed_dim = c->transformer_embed_dim;
     t.ffn_dim = c->transformer_ffn_embed_dim;
     t.speaker_embed_dim = c->speaker_embed_dim;
+    sd::TsvadModel::validate(t);   // proj_layer configurations (speaker_embed_dim * 2 != transformer_embed_dim)
     auto* h = new sd_tsvad;
     h->x3 = c->precision == 2;
     h->model.reset(new sd::TsvadModel(t));
@@ -581,6 +587,55 @@ int sd_campp_destroy(sd_campp* h) {
   return guard([&] { delete h; });
 }
 
+int sd_resnet34_create(const sd_resnet34_config* c, sd_resnet34** out) {
+  return guard([&] {
+    SD_CHECK(c && out, sd::kErrInvalid, "null argument");
+    SD_CHECK(c->precision == 0 || c->precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    SD_CHECK(c->feat_dim == 80, sd::kErrInvalid, "ResNet34 (MI355X backend) supports feat_dim 80 only");
+    SD_CHECK(c->embed_dim >= 8 && c->embed_dim % 8 == 0, sd::kErrInvalid, "embed_dim must be a positive multiple of 8");
+    SD_CHECK(c->max_batch > 0 && c->max_frames >= 8, sd::kErrInvalid, "bad workspace sizes");
+    sd::ResEmbConfig t;
+    t.feat_dim = c->feat_dim;
+    t.embed_dim = c->embed_dim;
+    t.two_emb_layer = c->two_emb_layer != 0;
+    t.max_batch = c->max_batch;
+    t.max_frames = c->max_frames;
+    t.bf16 = c->precision == 1;
+    auto* h = new sd_resnet34;
+    h->model.reset(new sd::ResEmbModel(t));
+    *out = h;
+  });
+}
+
+int sd_resnet34_set_param(sd_resnet34* h, const char* name, const float* data, const int64_t* shape, int ndim) {
+  return guard([&] {
+    SD_CHECK(h && name && (data || ndim == 0), sd::kErrInvalid, "null argument");
+    SD_CHECK(!h->model->finalized(), sd::kErrState, "set_param after finalize");
+    h->model->params().set(name, data, shape, ndim);
+  });
+}
+
+int sd_resnet34_finalize(sd_resnet34* h) {
+  return guard([&] {
+    SD_CHECK(h, sd::kErrInvalid, "null handle");
+    h->model->finalize();
+  });
+}
+
+int sd_resnet34_forward(sd_resnet34* h, const float* feats, int B, int T, float* emb, float* emb_a, float* time_out,
+                        void* stream) {
+  return guard([&] {
+    SD_CHECK(h && feats && (emb || emb_a || time_out), sd::kErrInvalid, "null argument");
+    h->model->forward(feats, B, T, emb, emb_a, time_out, S(stream));
+  });
+}
+
+int64_t sd_resnet34_device_bytes(const sd_resnet34* h) { return h ? (int64_t)h->model->device_bytes() : 0; }
+
+int sd_resnet34_destroy(sd_resnet34* h) {
+  return guard([&] { delete h; });
+}
+
 int sd_ssnd_create(const sd_ssnd_config* c, sd_ssnd** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
@@ -734,6 +789,46 @@ int sd_op_gemm_bf16(const void* x, int M, int K, int lda, int a_coff, const floa
     p.beta = beta;
     p.act = act;
     sd::conv_gemm(p, true, st);
+  });
+}
+
+int sd_op_tstp_pool(const void* x, int x_bf16, int B, int T, int C, float* stats, void* stream) {
+  return guard([&] {
+    SD_CHECK(x && stats, sd::kErrInvalid, "tstp_pool: null argument");
+    sd::tstp_pool(x, x_bf16 != 0, B, T, C, stats, nullptr, S(stream));
+  });
+}
+
+int sd_op_speaker_input_proj(const float* ts, const float* mix, int B, int NS, int T, int Tmix, int SE, int E,
+                             const float* w, const float* bias, const float* pe, const float* bn_a, const float* bn_b,
+                             const int* grp, int group, float* out, void* out_bf16, int precision, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(ts && mix && w && bias && out, sd::kErrInvalid, "speaker_input_proj: null argument");
+    SD_CHECK(precision >= 0 && precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
+    SD_CHECK(B >= 1 && NS >= 1 && T >= 1 && Tmix >= 1 && sd::speaker_input_proj_supported(SE, E), sd::kErrInvalid,
+             "speaker_input_proj: bad shape");
+    SD_CHECK((bn_a == nullptr) == (bn_b == nullptr) && group >= 1, sd::kErrInvalid, "speaker_input_proj: bn_a / bn_b");
+    const bool bf = precision == 1;
+    const sd::GemmX3Scope x3(precision == 2);
+    // proj_layer.weight (E, 2 SE) as a 2-tap weight (E, SE, 2) would interleave the halves; pack them one by one
+    Scratch wt((size_t)E * SE * (bf ? 2 : 4), st), wm((size_t)E * SE * (bf ? 2 : 4), st);
+    Scratch halves((size_t)2 * E * SE * 4, st);
+    float* h0 = static_cast<float*>(halves.p);
+    float* h1 = h0 + (size_t)E * SE;
+    SD_HIP(hipMemcpy2DAsync(h0, (size_t)SE * 4, w, (size_t)2 * SE * 4, (size_t)SE * 4, E, hipMemcpyDeviceToDevice, st));
+    SD_HIP(hipMemcpy2DAsync(h1, (size_t)SE * 4, w + SE, (size_t)2 * SE * 4, (size_t)SE * 4, E,
+                            hipMemcpyDeviceToDevice, st));
+    sd::pack_weight(h0, E, SE, 1, wt.p, bf, st);
+    sd::pack_weight(h1, E, SE, 1, wm.p, bf, st);
+    Scratch mixa((size_t)B * Tmix * SE * 4, st), pts((size_t)B * NS * E * 4, st), pmix((size_t)B * Tmix * E * 4, st);
+    sd::SpeakerProjArgs a;
+    a.ts = ts; a.mix = mix; a.ldmix = SE; a.Tmix = Tmix; a.B = B; a.NS = NS; a.T = T; a.SE = SE; a.E = E;
+    a.w_ts = wt.p; a.w_mix = wm.p; a.bias = bias; a.pe = pe;
+    a.bn.a = bn_a; a.bn.b = bn_b; a.bn.grp = grp; a.bn.group = group;
+    a.mix_a = mixa.p; a.p_ts = static_cast<float*>(pts.p); a.p_mix = static_cast<float*>(pmix.p);
+    a.out = out; a.xb = static_cast<uint16_t*>(out_bf16);
+    sd::speaker_input_proj(a, bf, st);
   });
 }
 

@@ -187,6 +187,15 @@ void cam_local_conv(const void* x, int B, int T, int dil, const void* wt, const 
 // stats (B, 2C) = [mean_t v | unbiased std_t v] (nullable); tout (B, T, C) = v (nullable).
 void stats_pool(const void* x, bool x_bf16, int B, int T, int C, const float* s, const float* h,
                 float* stats, float* tout, hipStream_t st);
+// ResNet34 TSTP (pooling_layers_wespeaker.py:66-88) over x (B, T, C) channel-last (C % 64 == 0), no BN / ReLU:
+// stats (B, 2C) = [mean_t x | sqrt(unbiased var_t x + 1e-7)] (nullable); tout (B, T, C) = x in fp32 (nullable).
+// NaN stays in its channel; T == 1 gives NaN stds (tstp_pool.hip).
+void tstp_pool(const void* x, bool x_bf16, int B, int T, int C, float* stats, float* tout, hipStream_t st);
+// y (B, N) = x (B, K) w^T + bias, fp32 FMA with a summation order fixed by K alone (a row's result does not depend
+// on B): the ResNet34 head's seg_1 / seg_2 (resnet_wespeaker.py:176-180).  w (N, K) row-major, K % 4 == 0.
+void seg_linear(const float* x, int B, int K, const float* w, const float* bias, int N, float* y, hipStream_t st);
+// y = x < 0 ? 0 : x over n floats: F.relu that keeps NaN (resnet_wespeaker.py:178).
+void relu_keep_nan(const float* x, int64_t n, float* y, hipStream_t st);
 
 // ---------------------------------------------------------------- norms
 // y = LN(x) * g + b over the last dim D; rows of x at stride ldx, y at ldy.
@@ -374,6 +383,28 @@ void poison_windows(float* x, int B, int64_t per_win, const int* win_a, const in
 // model.py:862-877 (ts_embeds repeat + cat) and :876 PositionalEncoding.
 void build_speaker_input(const float* ts, const float* mix, int ldmix, int Tmix, int B, int NS,
                          int T, int E, const float* pe, float* out, hipStream_t st, const BnRelu& mix_bn = BnRelu());
+
+// The same rows through proj_layer = nn.Linear(2 SE, E) (model.py:212-217, 873-876; configurations with
+// 2 SE != E): out[(b, spk, t), :] = W [ts[b, spk] | relu(bn(mix[b, t]))] + bias + pe[t], computed as
+// P_ts[b, spk] + P_mix[b, t] + pe[t] with W = [W_ts | W_mix] split on its input axis (ops.hip).  mix rows t >= Tmix
+// read as zeros.  The GEMMs follow conv_gemm's arithmetic for `bf16` (bf16 operands, or exact fp32 / bf16x3).
+struct SpeakerProjArgs {
+  const float* ts = nullptr;     // (B * NS, SE)
+  const float* mix = nullptr;    // (B, Tmix, ldmix): speech_down_or_up's conv + bias, columns 0 .. SE - 1
+  int ldmix = 0, Tmix = 0, B = 0, NS = 0, T = 0, SE = 0, E = 0;
+  const void* w_ts = nullptr;    // packed [E][SE]: proj_layer.weight[:, :SE] (bf16 bits in bf16 mode, else fp32)
+  const void* w_mix = nullptr;   // packed [E][SE]: proj_layer.weight[:, SE:]
+  const float* bias = nullptr;   // (E)
+  const float* pe = nullptr;     // (>= T, E), nullable
+  BnRelu bn;                     // speech_down_or_up's BatchNorm1D + ReLU, window = row / Tmix
+  void* mix_a = nullptr;         // scratch (B * Tmix, SE): the mix GEMM's A operand, bf16 in bf16 mode else fp32
+  float* p_ts = nullptr;         // scratch (B * NS, E)
+  float* p_mix = nullptr;        // scratch (B * Tmix, E)
+  float* out = nullptr;          // (B * NS * T, E)
+  uint16_t* xb = nullptr;        // nullable: bf16 copy of out
+};
+bool speaker_input_proj_supported(int SE, int E);   // both multiples of 8 (16-byte accesses)
+void speaker_input_proj(const SpeakerProjArgs& a, bool bf16, hipStream_t st);
 
 // Chunk-streaming speaker input (ts_vad2_streaming/model.py:767-777): row (b, spk, t) =
 // [ts[b, spk] | mix[b, t]] * scale + pe[pos(t)], pos(t) = start(t / C) + t % C with start(c) = 0

@@ -605,6 +605,118 @@ void build_speaker_input(const float* ts, const float* mix, int ldmix, int Tmix,
   SD_LAUNCH_CHECK();
 }
 
+// ------------------------------------------------------------------ proj_layer speaker input (model.py:212-217, 870-876)
+// proj_layer(cat(ts, mix)) = W_ts ts + W_mix mix + b with the weight split on its input axis: the ts term is one
+// row per (window, speaker), the mix term one row per (window, frame) shared by the NS speakers, so the two GEMMs
+// do (NS + T) / (2 NS T) of the unsplit Linear's multiply-adds and cat is never written.
+//
+// A operand of the mix GEMM: speech_down_or_up's BatchNorm1D + ReLU (BnRelu, NaN-bypass groups included) on the conv
+// output rows, 8 channels per thread (two 16-B loads; two 16-B fp32 stores or one 16-B bf16 store).
+template <bool OBF>
+__global__ __launch_bounds__(256) void bn_relu_rows_kernel(const float* __restrict__ x, int64_t rows, int C, int ldx,
+                                                           int rows_per_window, BnRelu bn, act_t<OBF>* __restrict__ y) {
+  const int per = C / 8;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * per) return;
+  const int64_t row = i / per;
+  const int c0 = (int)(i - row * per) * 8;
+  const float4 a = *reinterpret_cast<const float4*>(x + row * ldx + c0);
+  const float4 b = *reinterpret_cast<const float4*>(x + row * ldx + c0 + 4);
+  const int w = (int)(row / rows_per_window);
+  float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+  for (int u = 0; u < 8; ++u) v[u] = bn_relu(bn, w, c0 + u, v[u]);
+  if constexpr (OBF) {
+    *reinterpret_cast<uint4*>(y + row * C + c0) = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]),
+                                                             pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+  } else {
+    *reinterpret_cast<float4*>(y + row * C + c0) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(y + row * C + c0 + 4) = make_float4(v[4], v[5], v[6], v[7]);
+  }
+}
+
+// X[(b, s, t), :] = P_ts[b, s] + P_mix[b, t] (0 for t >= Tmix, the pad of model.py:852-854) + PE[t], 8 features per
+// thread; xb (nullable): the bf16 copy of the row for the first layer's in-projection.
+__global__ __launch_bounds__(256) void speaker_proj_combine_kernel(const float* __restrict__ p_ts,
+                                                                   const float* __restrict__ p_mix, int Tmix, int NS,
+                                                                   int T, int E, const float* __restrict__ pe,
+                                                                   int64_t rows, float* __restrict__ out,
+                                                                   uint16_t* __restrict__ xb) {
+  const int per = E / 8;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * per) return;
+  const int64_t row = i / per;   // (b, spk, t)
+  const int c0 = (int)(i - row * per) * 8;
+  const int t = (int)(row % T);
+  const int64_t bs = row / T, b = bs / NS;
+  float v[8];
+  {
+    const float4 a = *reinterpret_cast<const float4*>(p_ts + bs * E + c0);
+    const float4 c = *reinterpret_cast<const float4*>(p_ts + bs * E + c0 + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = c.x; v[5] = c.y; v[6] = c.z; v[7] = c.w;
+  }
+  if (t < Tmix) {
+    const float* m = p_mix + (b * Tmix + t) * E + c0;
+    const float4 a = *reinterpret_cast<const float4*>(m);
+    const float4 c = *reinterpret_cast<const float4*>(m + 4);
+    v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w; v[4] += c.x; v[5] += c.y; v[6] += c.z; v[7] += c.w;
+  }
+  if (pe) {
+    const float* q = pe + (int64_t)t * E + c0;
+    const float4 a = *reinterpret_cast<const float4*>(q);
+    const float4 c = *reinterpret_cast<const float4*>(q + 4);
+    v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w; v[4] += c.x; v[5] += c.y; v[6] += c.z; v[7] += c.w;
+  }
+  float* o = out + row * E + c0;
+  *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+  *reinterpret_cast<float4*>(o + 4) = make_float4(v[4], v[5], v[6], v[7]);
+  if (xb)
+    *reinterpret_cast<uint4*>(xb + row * E + c0) = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]),
+                                                              pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+}
+
+bool speaker_input_proj_supported(int SE, int E) { return SE >= 8 && SE % 8 == 0 && E >= 8 && E % 8 == 0; }
+
+void speaker_input_proj(const SpeakerProjArgs& a, bool bf16, hipStream_t st) {
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  SD_CHECK(speaker_input_proj_supported(a.SE, a.E), kErrInvalid,
+           "speaker_input_proj: speaker_embed_dim and transformer_embed_dim must be multiples of 8");
+  SD_CHECK(a.B >= 1 && a.NS >= 1 && a.T >= 1 && a.Tmix >= 1 && a.ldmix >= a.SE && a.ldmix % 4 == 0, kErrInvalid,
+           "speaker_input_proj: bad shape");
+  SD_CHECK(a.ts && a.mix && a.w_ts && a.w_mix && a.bias && a.mix_a && a.p_ts && a.p_mix && a.out, kErrInvalid,
+           "speaker_input_proj: null argument");
+  SD_CHECK(al16(a.mix) && al16(a.mix_a) && al16(a.p_ts) && al16(a.p_mix) && al16(a.out) && al16(a.pe) && al16(a.xb),
+           kErrInvalid, "speaker_input_proj: buffers must be 16-byte aligned");
+  const int64_t mrows = (int64_t)a.B * a.Tmix, rows = (int64_t)a.B * a.NS * a.T;
+  SD_CHECK(mrows * a.SE / 8 + 255 < (1ll << 39) && rows * a.E / 8 + 255 < (1ll << 39) && rows < (1ll << 31) &&
+               mrows < (1ll << 31), kErrInvalid, "speaker_input_proj: too many rows");
+  {
+    const unsigned blocks = (unsigned)((mrows * (a.SE / 8) + 255) / 256);
+    if (bf16)
+      hipLaunchKernelGGL(bn_relu_rows_kernel<true>, dim3(blocks), dim3(256), 0, st, a.mix, mrows, a.SE, a.ldmix,
+                         a.Tmix, a.bn, static_cast<uint16_t*>(a.mix_a));
+    else
+      hipLaunchKernelGGL(bn_relu_rows_kernel<false>, dim3(blocks), dim3(256), 0, st, a.mix, mrows, a.SE, a.ldmix,
+                         a.Tmix, a.bn, static_cast<float*>(a.mix_a));
+    SD_LAUNCH_CHECK();
+  }
+  // P_ts = W_ts ts + b (one row per window and speaker), P_mix = W_mix relu(bn(mix)) (one row per window and frame)
+  ConvGemmArgs pt = linear_args(a.ts, a.B * a.NS, a.SE, a.SE, a.w_ts, a.E, a.p_ts, a.E);
+  pt.beta = a.bias;
+  conv_gemm(pt, bf16, st);
+  ConvGemmArgs pm = linear_args(a.mix_a, (int)mrows, a.SE, a.SE, a.w_mix, a.E, a.p_mix, a.E);
+  pm.a_bf16 = bf16;
+  conv_gemm(pm, bf16, st);
+  {
+    ProfScope prof("speaker_proj_combine", 0.0,
+                   4.0 * (a.B * a.NS + (double)mrows) * a.E + (4.0 + (a.xb ? 2.0 : 0.0)) * rows * a.E, st);
+    const unsigned blocks = (unsigned)((rows * (a.E / 8) + 255) / 256);
+    hipLaunchKernelGGL(speaker_proj_combine_kernel, dim3(blocks), dim3(256), 0, st, a.p_ts, a.p_mix, a.Tmix, a.NS, a.T,
+                       a.E, a.pe, rows, a.out, a.xb);
+    SD_LAUNCH_CHECK();
+  }
+}
+
 __global__ void build_stream_input_kernel(const float* __restrict__ ts, const float* __restrict__ mix, int T,
                                           int NS, int E, float scale, const float* __restrict__ pe, int C,
                                           int left, float* __restrict__ out) {

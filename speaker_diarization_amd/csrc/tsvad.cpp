@@ -26,10 +26,20 @@ ConvL TsvadModel::conv_bn(const std::string& wname, const std::string& bn, const
   return load_conv_bn(ps_, arena_, cfg_.bf16, wname, bn, bias);
 }
 
+void TsvadModel::validate(const TsvadConfig& c) {
+  if (c.speaker_embed_dim * 2 == c.embed_dim) return;
+  // proj_layer = nn.Linear(2 SE, E) on cat(ts_embed, mix_embeds) (model.py:212-217, 873-874)
+  SD_CHECK(c.variant != 1, kErrInvalid,
+           "speaker_embed_dim*2 != transformer_embed_dim needs proj_layer, which the reference's ots_vad forward "
+           "never applies (model.py:730-731 is commented out; its conformer then fails on the 2*speaker_embed_dim "
+           "wide input): not supported for ots_vad_style v1");
+  SD_CHECK(speaker_input_proj_supported(c.speaker_embed_dim, c.embed_dim), kErrInvalid,
+           "proj_layer: speaker_embed_dim and transformer_embed_dim must be multiples of 8");
+}
+
 void TsvadModel::finalize() {
   SD_CHECK(!finalized_, kErrState, "finalize called twice");
-  SD_CHECK(cfg_.speaker_embed_dim * 2 == cfg_.embed_dim, kErrInvalid,
-           "proj_layer (speaker_embed_dim*2 != transformer_embed_dim) is not supported");
+  validate(cfg_);
   const std::string se = "speech_encoder.";
   if (cfg_.variant == 2) {
     res_.load(ps_, arena_, se, cfg_.bf16);   // resnet_wespeaker.py:108-171
@@ -88,6 +98,24 @@ void TsvadModel::finalize() {
     SD_CHECK(pe.shape.size() == 3 && pe.shape[2] == cfg_.embed_dim, kErrParam, "pos_encoder.pe shape");
     pe_len_ = (int)pe.shape[0];
     pe_ = arena_.upload(pe.data);
+    if (cfg_.speaker_embed_dim * 2 != cfg_.embed_dim) {
+      // proj_layer.weight (E, 2 SE) split on its input axis into [W_ts | W_mix] (speaker_input_proj)
+      const int E = cfg_.embed_dim, SE = cfg_.speaker_embed_dim;
+      const HostTensor& w = ps_.get("proj_layer.weight");
+      const HostTensor& b = ps_.get("proj_layer.bias");
+      SD_CHECK(w.shape.size() == 2 && w.shape[0] == E && w.shape[1] == 2 * SE, kErrParam,
+               "proj_layer.weight must be (transformer_embed_dim, 2 * speaker_embed_dim)");
+      SD_CHECK(b.numel() == E, kErrParam, "proj_layer.bias size");
+      std::vector<float> wt((size_t)E * SE), wm((size_t)E * SE);
+      for (int n = 0; n < E; ++n)
+        for (int k = 0; k < SE; ++k) {
+          wt[(size_t)n * SE + k] = w.data[(size_t)n * 2 * SE + k];
+          wm[(size_t)n * SE + k] = w.data[(size_t)n * 2 * SE + SE + k];
+        }
+      proj_ts_ = upload_packed(arena_, wt, E, SE, 1, 1, cfg_.bf16);
+      proj_mix_ = upload_packed(arena_, wm, E, SE, 1, 1, cfg_.bf16);
+      proj_b_ = arena_.upload(b.data);
+    }
     for (int i = 0; i < cfg_.num_transformer_layer; ++i) {
       single_.push_back(loader().transformer("single_backend.layers." + std::to_string(i)));
       multi_.push_back(loader().transformer("multi_backend.layers." + std::to_string(i)));
@@ -151,6 +179,10 @@ void TsvadModel::alloc_workspace() {
   partial_ = ws(Bm * NS * ((E + 63) / 64) * 2);
   lstm_work_ = ws(lstm_work_floats((int)Bm, cfg_.lstm_hidden, 2));
   nonfinite_ = static_cast<int*>(arena_.alloc(4 * (size_t)Bm * sizeof(int)));
+  if (proj_b_) {
+    pts_ = ws(Bm * NS * E);
+    pmix_ = ws(Bm * T3 * E);
+  }
 }
 
 TsvadModel::~TsvadModel() {
@@ -214,10 +246,21 @@ void TsvadModel::transformer_backend(const float* ts, int T3, int B, int Tl, flo
   const bool bf = cfg_.bf16;
   const int E = cfg_.embed_dim, SE = cfg_.speaker_embed_dim, NS = cfg_.max_num_speaker, S = B * NS;
   // Per-speaker encoder over S = B*NS sequences (model.py:869-879).
-  build_speaker_input(ts, mix_, SE, T3, B, NS, Tl, SE, pe_, X_, st, sd_bn);
-  // bf16(X) for the first layer's in-projection too (every later layer gets it from the LayerNorms): an
-  // fp32 A operand would send that GEMM to the register-staged kernel (C4: 1.5 ms per 640 windows vs 0.3)
-  if (bf) f32_to_bf16(X_, (int64_t)S * Tl * E, enc_work().AO, st);
+  if (proj_b_) {
+    // 2 SE != E: proj_layer on cat(ts_embed, mix_embeds) (model.py:873-874) as two small GEMMs + a combine pass that
+    // also writes bf16(X) (mixg_ holds the mix GEMM's BN-ReLU'd A operand)
+    SpeakerProjArgs a;
+    a.ts = ts; a.mix = mix_; a.ldmix = SE; a.Tmix = T3; a.B = B; a.NS = NS; a.T = Tl; a.SE = SE; a.E = E;
+    a.w_ts = proj_ts_.w; a.w_mix = proj_mix_.w; a.bias = proj_b_; a.pe = pe_; a.bn = sd_bn;
+    a.mix_a = mixg_; a.p_ts = pts_; a.p_mix = pmix_; a.out = X_;
+    a.xb = bf ? reinterpret_cast<uint16_t*>(enc_work().AO) : nullptr;
+    speaker_input_proj(a, bf, st);
+  } else {
+    build_speaker_input(ts, mix_, SE, T3, B, NS, Tl, SE, pe_, X_, st, sd_bn);
+    // bf16(X) for the first layer's in-projection too (every later layer gets it from the LayerNorms): an
+    // fp32 A operand would send that GEMM to the register-staged kernel (C4: 1.5 ms per 640 windows vs 0.3)
+    if (bf) f32_to_bf16(X_, (int64_t)S * Tl * E, enc_work().AO, st);
+  }
   for (size_t i = 0; i < single_.size(); ++i)
     run_transformer(single_[i], X_, S, Tl, E, cfg_.num_attention_head, nullptr, enc_work(), st, 0, 0, bf || i > 0);
   speakers_to_channels(X_, B, NS, Tl, E, X2_, bf, st);

@@ -31,7 +31,10 @@ class TsvadModel {
   explicit TsvadModel(const TsvadConfig& c) : cfg_(c) {}
   ParamStore& params() { return ps_; }
   void finalize();
-  // ref_speech (B, T_fb, 80) fbank, target_speech (B, NS, 192), logits out (B, NS, T_lab).
+  // Raises kErrInvalid for a configuration the runner does not build (sd_tsvad_create calls it): with
+  // speaker_embed_dim * 2 != embed_dim the reference inserts proj_layer (model.py:212-217), built for variants 0 and 2.
+  static void validate(const TsvadConfig& c);
+  // ref_speech (B, T_fb, 80) fbank, target_speech (B, NS, speaker_embed_dim), logits out (B, NS, T_lab).
   // forward_batch: windows per reference forward call, the scope of BatchNorm1D's NaN bypass (model.py:161-171),
   // i.e. the batch a NaN window disables speech_down_or_up's / backend_down's BatchNorm for; 0: the whole call.
   // force: the call is part of a larger reference batch that holds a non-finite input elsewhere: bit 0 skips
@@ -88,6 +91,10 @@ class TsvadModel {
   const float *gsp_w_ = nullptr, *gsp_b_ = nullptr;
   const float* pe_ = nullptr;
   int pe_len_ = 0;
+  // proj_layer (2 SE != E only): weight columns [0, SE) / [SE, 2 SE), bias; P_ts (B NS, E) / P_mix (B T3, E) scratch
+  PackedW proj_ts_, proj_mix_;
+  const float* proj_b_ = nullptr;
+  float *pts_ = nullptr, *pmix_ = nullptr;
   std::vector<TransformerL> single_, multi_;
   ConvL backend_down_;
   std::vector<ConformerL> conf_;

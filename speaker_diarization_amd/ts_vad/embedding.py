@@ -4,6 +4,9 @@ Drop-in for the step before TS-VAD inference:
   * `CAMPPlus` — egs/alimeeting/ts_vad2/cam_pplus_wespeaker.py:311-399 (same constructor
     arguments, same standalone state_dict keys, forward(x) -> (B, E) and
     forward(x, get_time_out=True) -> (B, 512, T')), run by libsdiar (`sd_campp_*`).
+  * `ResNet34` — egs/alimeeting/ts_vad2/resnet_wespeaker.py:108-208 (speech_encoder=False): the WeSpeaker
+    ResNet34 extractor of generate_chunk_speaker_embedding_from_wespeaker_for_diarization.py:116-133 (256-d
+    embeddings, TSTP pooling + seg_1), run by libsdiar (`sd_resnet34_*`); `extract_embed` drives either model.
   * `FBank` — the extractor's FBank (generate_chunk_speaker_embedding_from_modelscope_for_
     diarization.py:307-331): kaldi fbank with the povey window, dither 0, no 2^15 scale,
     mean_nor over the chunk.
@@ -105,6 +108,107 @@ class CAMPPlus:
     __call__ = forward
 
 
+class ResNet34:
+    """egs/alimeeting/ts_vad2/resnet_wespeaker.py:108-183, 198-208 with speech_encoder=False: the WeSpeaker
+    ResNet34 embedding extractor (TSTP pooling + seg_1 [+ seg_bn_1 + seg_2]) run by libsdiar (`sd_resnet34_*`).
+    Same constructor arguments and standalone state_dict keys; forward(x) -> (embed_a, embed_b), or
+    (tensor(0.0), embed_a) without two_emb_layer; forward(x, get_time_out=True) -> (B, 2560, T').  The encoder-only
+    form (speech_encoder=True) is TSVADModel's speech encoder, not this class."""
+
+    def __init__(self, feat_dim: int, embed_dim: int, pooling_func: str = "TSTP", two_emb_layer: bool = True,
+                 speech_encoder: bool = False, *, device=None, precision: str = "bf16", max_batch: int = 96,
+                 max_frames: int = 598):
+        import torch
+        if pooling_func != "TSTP":
+            raise ValueError(f"the MI355X ResNet34 builds TSTP pooling only, got {pooling_func}")
+        if speech_encoder:
+            raise ValueError("speech_encoder=True (no pooling head) is TSVADModel's resnet34_wespeaker speech encoder")
+        if precision not in ("bf16", "fp32"):
+            raise ValueError(f"precision must be bf16 or fp32, got {precision}")
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type != "cuda":
+            raise ValueError("ResNet34 (MI355X backend) runs on a HIP device only")
+        self.feat_dim, self.embed_dim, self.two_emb_layer = feat_dim, embed_dim, bool(two_emb_layer)
+        self.embedding_size = embed_dim      # what extract_embed sizes its output with
+        self.precision, self.max_batch, self.max_frames = precision, max_batch, max_frames
+        conf = _lib.Resnet34Config(feat_dim=feat_dim, embed_dim=embed_dim, two_emb_layer=int(self.two_emb_layer),
+                                   max_batch=max_batch, max_frames=max_frames,
+                                   precision=1 if precision == "bf16" else 0)
+        h = ctypes.c_void_p()
+        _lib.call("sd_resnet34_create", ctypes.byref(conf), ctypes.byref(h))
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and _lib._lib is not None:
+            _lib.load().sd_resnet34_destroy(h)
+            self._h = None
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        import torch
+        if not strict:
+            raise ValueError("the MI355X backend only supports strict=True loading")
+        state_dict = unwrap_checkpoint(state_dict, kind="resnet34")
+        with torch.device("cpu"):
+            for k, v in state_dict.items():
+                t = torch.as_tensor(np.asarray(v.cpu() if hasattr(v, "cpu") else v)).to(torch.float32).contiguous()
+                shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
+                _lib.call("sd_resnet34_set_param", self._h, k.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim())
+        _lib.call("sd_resnet34_finalize", self._h)
+        return self
+
+    def eval(self):
+        return self
+
+    def to(self, device):
+        import torch
+        if torch.device(device) != self.device:
+            raise ValueError("re-create the model on the target device")
+        return self
+
+    @property
+    def device_bytes(self) -> int:
+        return int(_lib.load().sd_resnet34_device_bytes(self._h))
+
+    @staticmethod
+    def out_frames(T: int) -> int:
+        for _ in range(3):
+            T = (T - 1) // 2 + 1
+        return T
+
+    def forward(self, x, get_time_out: bool = False, out=None):
+        """x (B, T, 80) -> (embed_a, embed_b) / (tensor(0.0), embed_a) (resnet_wespeaker.py:176-183), or
+        (B, 2560, T') with get_time_out (:165-171).  out: (B, embed_dim) destination of the last tuple element."""
+        import torch
+        B, T, F = x.shape
+        if F != self.feat_dim:
+            raise ValueError(f"expected {self.feat_dim}-dim fbank, got {F}")
+        x = x.to(self.device, torch.float32).contiguous()
+        if B > self.max_batch:
+            parts = [self.forward(x[s:s + self.max_batch], get_time_out,
+                                  None if out is None else out[s:s + self.max_batch])
+                     for s in range(0, B, self.max_batch)]
+            if get_time_out:
+                return torch.cat(parts)
+            first = torch.cat([p[0] for p in parts]) if self.two_emb_layer else parts[0][0]
+            return first, (out if out is not None else torch.cat([p[1] for p in parts]))
+        st = _lib.stream_ptr(self.device)
+        if get_time_out:
+            tout = torch.empty(B, self.out_frames(T), 2560, device=self.device, dtype=torch.float32)
+            _lib.call("sd_resnet34_forward", self._h, _lib.ptr(x), B, T, None, None, _lib.ptr(tout), st)
+            return tout.permute(0, 2, 1)
+        if out is None:
+            out = torch.empty(B, self.embed_dim, device=self.device, dtype=torch.float32)
+        if not self.two_emb_layer:
+            _lib.call("sd_resnet34_forward", self._h, _lib.ptr(x), B, T, _lib.ptr(out), None, None, st)
+            return torch.tensor(0.0), out
+        emb_a = torch.empty(B, self.embed_dim, device=self.device, dtype=torch.float32)
+        _lib.call("sd_resnet34_forward", self._h, _lib.ptr(x), B, T, _lib.ptr(out), _lib.ptr(emb_a), None, st)
+        return emb_a, out
+
+    __call__ = forward
+
+
 def kaldi_fbank_povey(wav, n_mels: int = 80, out=None):
     """Kaldi.fbank(wav, num_mel_bins, sample_frequency=16000, dither=0) (povey window,
     samples as read, no 2^15 scale): 1-D float32 CUDA tensor -> (n_frames, n_mels)."""
@@ -147,10 +251,13 @@ def embedding_chunks(n_samples: int, length_embedding: float = 6.0, step_embeddi
     return [(0, n_samples)]
 
 
-def extract_embed(wav, model: CAMPPlus, length_embedding: float = 6.0, step_embedding: float = 1.0,
+def extract_embed(wav, model, length_embedding: float = 6.0, step_embedding: float = 1.0,
                   batch_size: int = 96, n_mels: int = 80):
     """wav: 1-D float samples in [-1, 1) (numpy or tensor; soundfile values cast to float32
-    like torch.FloatTensor at :283) -> (n_chunks, E) float32 embeddings on the model device."""
+    like torch.FloatTensor at :283) -> (n_chunks, E) float32 embeddings on the model device.
+    model: CAMPPlus, or ResNet34 (generate_chunk_speaker_embedding_from_wespeaker_for_diarization.py:143-176, the
+    same chunk loop; the last element of the model's tuple is kept, :132-133).  A file too short for ResNet34's
+    three stride-2 stages (at most 8 fbank frames) yields the reference's all-NaN embedding."""
     import torch
     dev = model.device
     w = torch.as_tensor(np.asarray(wav) if not isinstance(wav, torch.Tensor) else wav)
@@ -158,7 +265,7 @@ def extract_embed(wav, model: CAMPPlus, length_embedding: float = 6.0, step_embe
     chunks = embedding_chunks(w.numel(), length_embedding, step_embedding)
     if any(a % FRAME_SHIFT for a, _ in chunks):
         raise ValueError("chunk starts must be whole fbank frames (step_embedding * 16000 % 160 == 0)")
-    if num_frames(chunks[0][1] - chunks[0][0]) < 8:
+    if isinstance(model, CAMPPlus) and num_frames(chunks[0][1] - chunks[0][0]) < 8:
         raise ValueError("audio shorter than CAM++'s minimum of 8 fbank frames")
     feats = kaldi_fbank_povey(w, n_mels)
     nf = num_frames(chunks[0][1] - chunks[0][0])           # every chunk has the same length

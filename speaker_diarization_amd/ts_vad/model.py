@@ -93,7 +93,7 @@ class TSVADModel:
     # ------------------------------------------------------------------ forward
     def forward(self, ref_speech, target_speech, labels, num_updates: int = 0, out=None, check: bool = True,
                 forward_batch: int = 0, _force: int = 0):
-        """ref_speech (B, T_fb, 80), target_speech (B, NS, 192), labels (B, NS, T) (only
+        """ref_speech (B, T_fb, 80), target_speech (B, NS, speaker_embed_dim), labels (B, NS, T) (only
         labels.size(-1) is read, model.py:681/770) -> logits (B, NS, T).  check: wait for the
         stream and raise RuntimeError in this call if the BiLSTM's persistent recurrence lost
         co-residency (its logits are NaN); check=False defers that to status().

@@ -156,7 +156,7 @@ class TSVADPipeline:
         return out
 
     def posteriors(self, wav, ts, n_labels: int = None, group=None):
-        """wav: (n_samples,) CUDA float32 in [-1,1); ts: (NS, 192) target-speaker
+        """wav: (n_samples,) CUDA float32 in [-1,1); ts: (NS, speaker_embed_dim) target-speaker
         embeddings (zeros for absent speakers, ts_vad_dataset.py:507-510).
         Returns (NS, n_labels) frame posteriors at 25 Hz."""
         import torch

@@ -146,6 +146,22 @@ def resnet34_layout(prefix: str = "speech_encoder.") -> list:
     return k
 
 
+def resnet34_embed_layout(embed_dim: int = 256, two_emb_layer: bool = False) -> list:
+    """Key layout of the standalone embedding extractor ResNet34(feat_dim=80, embed_dim, pooling_func="TSTP",
+    two_emb_layer, speech_encoder=False) (resnet_wespeaker.py:108-147; the extractor script builds it with
+    embed_dim 256 and two_emb_layer=False, generate_chunk_speaker_embedding_from_wespeaker_for_diarization.py:
+    116-117): the trunk of resnet34_layout("") + seg_1 on the 5120 TSTP statistics (TSTP has no parameters)
+    [+ seg_bn_1 (affine=False) + seg_2]."""
+    k = resnet34_layout("")
+    k.append(("seg_1.weight", (embed_dim, 5120), "kaiming"))
+    k.append(("seg_1.bias", (embed_dim,), "small"))
+    if two_emb_layer:
+        _bn(k, "seg_bn_1", embed_dim, affine=False)
+        k.append(("seg_2.weight", (embed_dim, embed_dim), "kaiming"))
+        k.append(("seg_2.bias", (embed_dim,), "small"))
+    return k
+
+
 def _mha(k: list, p: str, e: int):
     k.append((p + "in_proj_weight", (3 * e, e), "xavier"))
     k.append((p + "in_proj_bias", (3 * e,), "small"))
@@ -175,6 +191,11 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         k.append(("speech_down_or_up.0.weight", (se, 512, 5), "conv1d"))
         k.append(("speech_down_or_up.0.bias", (se,), "small"))
         _bn(k, "speech_down_or_up.1.bn", se)
+    if se * 2 != e:
+        # nn.Linear(2 * speaker_embed_dim, transformer_embed_dim) on cat(ts_embed, mix_embeds) (model.py:212-217,
+        # 873-874); the reference registers it for every variant, its ots_vad forward never applies it
+        k.append(("proj_layer.weight", (e, 2 * se), "linear"))
+        k.append(("proj_layer.bias", (e,), "small"))
     if cfg.variant in (0, 2):
         k.append(("pos_encoder.pe", (cfg.rs_len * cfg.label_rate, 1, e), "pe"))
         for i in range(cfg.num_transformer_layer):
@@ -454,6 +475,11 @@ def tsvad_streaming_state_dict(cfg: TSVADStreamingConfig, seed: int = 777):
 def campplus_state_dict(seed: int = 777, embedding_size: int = 192):
     """Seeded weights for a standalone CAMPPlus (keys head.*, xvector.*)."""
     return synthetic_state_dict(campplus_layout("", embedding_size), seed)
+
+
+def resnet34_embed_state_dict(seed: int = 777, embed_dim: int = 256, two_emb_layer: bool = False):
+    """Seeded weights for a standalone ResNet34 embedding extractor (keys conv1.*, layer*.*, seg_*)."""
+    return synthetic_state_dict(resnet34_embed_layout(embed_dim, two_emb_layer), seed)
 
 
 def to_torch(sd):
