@@ -11,8 +11,6 @@
 
 namespace sd {
 
-namespace {
-
 ConvGemmArgs conv2d(Tens in, int B, int H, int W, const ConvL& L, int sh, int sw, int ph, int pw, Tens out) {
   ConvGemmArgs p;
   p.A = in.p; p.a_bf16 = in.bf; p.B = B; p.H = H; p.W = W; p.Cin = L.w.Cin; p.lda = L.w.Cin; p.a_coff = 0;
@@ -27,8 +25,6 @@ ConvGemmArgs conv2d(Tens in, int B, int H, int W, const ConvL& L, int sh, int sw
   return p;
 }
 
-}  // namespace
-
 ConvGemmArgs cam_conv1d(Tens in, int B, int T, int lda, const ConvL& L, int stride, int pad, int dil, Tens out,
                         int ldo) {
   ConvGemmArgs p;
@@ -42,6 +38,12 @@ ConvGemmArgs cam_conv1d(Tens in, int B, int T, int lda, const ConvL& L, int stri
   p.out = out.p; p.out_bf16 = out.bf;
   p.o_sb = (int64_t)p.Wo * ldo; p.o_sh = 0; p.o_sw = ldo; p.o_sn = 1;
   return p;
+}
+
+ConvGemmArgs logits_fc(float* x, int B, int T, int lda, const ConvL& fc, int NS, float* logits) {
+  ConvGemmArgs f = cam_conv1d(Tens{x, false}, B, T, lda, fc, 1, 0, 1, Tens{logits, false}, 1);
+  f.o_sb = (int64_t)NS * T; f.o_sw = 1; f.o_sn = T;
+  return f;
 }
 
 ConvL load_conv_bn(ParamStore& ps, DeviceArena& arena, bool bf16, const std::string& wname, const std::string& bn,
@@ -59,6 +61,43 @@ ConvL load_conv_bn(ParamStore& ps, DeviceArena& arena, bool bf16, const std::str
     L.beta = arena.upload(ps.get(bias).data);
   }
   return L;
+}
+
+ResBlockL load_res_block(ParamStore& ps, DeviceArena& arena, bool bf16, const std::string& p, int stride, bool has_sc) {
+  ResBlockL rb;
+  rb.stride = stride;
+  rb.c1 = load_conv_bn(ps, arena, bf16, p + "conv1.weight", p + "bn1");
+  rb.c2 = load_conv_bn(ps, arena, bf16, p + "conv2.weight", p + "bn2");
+  rb.has_sc = has_sc;
+  if (has_sc) rb.sc = load_conv_bn(ps, arena, bf16, p + "shortcut.0.weight", p + "shortcut.1");
+  return rb;
+}
+
+float* run_res_block(const ResBlockL& rb, float* const bufs[3], float* cur, bool bf, int B, int& H, int& W, int sw,
+                     const std::function<bool(const ConvGemmArgs& p, float* t2)>& conv1,
+                     const std::function<void(ConvGemmArgs& r)>& conv2, hipStream_t st) {
+  float* others[2];
+  int k = 0;
+  for (int i = 0; i < 3; ++i) if (bufs[i] != cur) others[k++] = bufs[i];
+  float* const t1 = others[0];
+  float* const t2 = others[1];
+  ConvGemmArgs p = conv2d(Tens{cur, bf}, B, H, W, rb.c1, rb.stride, sw, 1, 1, Tens{t1, bf});
+  p.act = kActRelu;
+  const bool sc_done = conv1(p, t2);
+  const float* res = cur;
+  float* outb = t2;
+  if (rb.has_sc) {
+    if (!sc_done) conv_gemm(conv2d(Tens{cur, bf}, B, H, W, rb.sc, rb.stride, sw, 0, 0, Tens{t2, bf}), bf, st);
+    res = t2;
+    outb = cur;   // the block's input is no longer needed
+  }
+  ConvGemmArgs r = conv2d(Tens{t1, bf}, B, p.Ho, p.Wo, rb.c2, 1, 1, 1, 1, Tens{outb, bf});
+  r.res = res; r.res_bf16 = bf; r.res_ld = rb.c2.w.N;
+  r.act = kActRelu;
+  conv2(r);
+  H = p.Ho;
+  W = p.Wo;
+  return outb;
 }
 
 // ------------------------------------------------------------------------------ CamTrunk
@@ -80,13 +119,7 @@ void CamTrunk::load(ParamStore& ps, DeviceArena& arena, const std::string& pre, 
   for (int layer = 1; layer <= 2; ++layer)
     for (int blk = 0; blk < 2; ++blk) {
       std::string p = pre + "head.layer" + std::to_string(layer) + "." + std::to_string(blk) + ".";
-      ResBlock rb;
-      rb.stride = blk == 0 ? 2 : 1;
-      rb.c1 = conv_bn(p + "conv1.weight", p + "bn1");
-      rb.c2 = conv_bn(p + "conv2.weight", p + "bn2");
-      rb.has_sc = ps.has(p + "shortcut.0.weight");
-      if (rb.has_sc) rb.sc = conv_bn(p + "shortcut.0.weight", p + "shortcut.1");
-      fcm_blocks_.push_back(rb);
+      fcm_blocks_.push_back(load_res_block(ps, arena, bf16, p, blk == 0 ? 2 : 1, ps.has(p + "shortcut.0.weight")));
     }
   fcm_conv2_ = conv_bn(pre + "head.conv2.weight", pre + "head.bn2");
   // ---- xvector (cam_pplus_wespeaker.py:330-372)
@@ -178,50 +211,26 @@ Tens CamTrunk::forward(const float* fbank, int B, int Tf, hipStream_t st, int b0
   // bf16: layer1.0's conv1 computes the stem (head.conv1 + bn1 + relu) from the fbank in LDS, and the two
   // strided blocks' shortcuts ride on their conv1's centre tap (fcm_conv.hip FcmFuse).
   float* cur = fcmA;
-  int H = F;
-  float* bufs[3] = {fcmA, fcmB, fcmC};
-  bool stem_done = false;
+  int H = F, W = Tf;
+  float* const bufs[3] = {fcmA, fcmB, fcmC};
   for (size_t i = 0; i < fcm_blocks_.size(); ++i) {
-    const ResBlock& rb = fcm_blocks_[i];
-    float* others[2];
-    int k = 0;
-    for (float* b : bufs) if (b != cur) others[k++] = b;
-    float* t1 = others[0];
-    float* t2 = others[1];
-    ConvGemmArgs p = conv2d(Tens{cur, bf}, B, H, Tf, rb.c1, rb.stride, 1, 1, 1, Tens{t1, bf});
-    p.act = kActRelu;
-    FcmFuse fu;
-    if (rb.has_sc) {
-      fu.sc_w = rb.sc.w.w; fu.sc_alpha = rb.sc.alpha; fu.sc_beta = rb.sc.beta; fu.sc_out = t2;
-    }
-    if (i == 0) {
-      fu.fbank = ref; fu.fb_F = F;
-      fu.stem_w = fcm_conv1_.pre_s; fu.stem_alpha = fcm_conv1_.alpha; fu.stem_beta = fcm_conv1_.beta;
-    }
-    const bool fused = bf && rb.has_sc && rb.sc.w.N == 32 && rb.sc.w.K == 32 && fcm_fused_supported(p, fu);
-    if (i == 0 && !fused) {
-      fcm_conv1(ref, B, Tf, F, fcm_conv1_.pre_s, fcm_conv1_.alpha, fcm_conv1_.beta, fcmA, bf, st);
-      stem_done = true;
-    }
-    SD_CHECK(i != 0 || fused || stem_done, kErrInvalid, "FCM stem not computed");
-    if (fused) conv_fcm3x3_fused(p, fu, st);
-    else conv_gemm(p, bf, st);
-    const int Ho = p.Ho;
-    const float* res = cur;
-    float* outb;
-    if (rb.has_sc) {
-      if (!fused) conv_gemm(conv2d(Tens{cur, bf}, B, H, Tf, rb.sc, rb.stride, 1, 0, 0, Tens{t2, bf}), bf, st);
-      res = t2;
-      outb = cur;   // input no longer needed
-    } else {
-      outb = t2;
-    }
-    ConvGemmArgs r = conv2d(Tens{t1, bf}, B, Ho, Tf, rb.c2, 1, 1, 1, 1, Tens{outb, bf});
-    r.res = res; r.res_bf16 = bf; r.res_ld = 32;
-    r.act = kActRelu;
-    conv_gemm(r, bf, st);
-    cur = outb;
-    H = Ho;
+    const ResBlockL& rb = fcm_blocks_[i];
+    auto conv1 = [&](const ConvGemmArgs& p, float* t2) {
+      FcmFuse fu;
+      if (rb.has_sc) {
+        fu.sc_w = rb.sc.w.w; fu.sc_alpha = rb.sc.alpha; fu.sc_beta = rb.sc.beta; fu.sc_out = t2;
+      }
+      if (i == 0) {
+        fu.fbank = ref; fu.fb_F = F;
+        fu.stem_w = fcm_conv1_.pre_s; fu.stem_alpha = fcm_conv1_.alpha; fu.stem_beta = fcm_conv1_.beta;
+      }
+      const bool fused = bf && rb.has_sc && rb.sc.w.N == 32 && rb.sc.w.K == 32 && fcm_fused_supported(p, fu);
+      if (i == 0 && !fused) fcm_conv1(ref, B, Tf, F, fcm_conv1_.pre_s, fcm_conv1_.alpha, fcm_conv1_.beta, fcmA, bf, st);
+      if (fused) conv_fcm3x3_fused(p, fu, st);
+      else conv_gemm(p, bf, st);
+      return fused;
+    };
+    cur = run_res_block(rb, bufs, cur, bf, B, H, W, 1, conv1, [&](ConvGemmArgs& r) { conv_gemm(r, bf, st); }, st);
   }
   {
     // head.conv2 (stride (2,1)) + bn2 + relu, stored as (B, T, C*F') with channel c*F'+f.
@@ -296,17 +305,12 @@ void CamppModel::finalize() {
   // (B x 1024 x E), so it always runs on the exact-fp32 MFMA path.  Its BatchNorm is
   // affine=False ("batchnorm_", :22-23): a weight/bias key is unexpected, not a gamma/beta.
   for (const char* k : {"xvector.dense.nonlinear.batchnorm.weight", "xvector.dense.nonlinear.batchnorm.bias"})
-    SD_CHECK(!ps_.has(k), kErrParam, std::string("Unexpected key(s) in state_dict: \"") + k + "\"");
+    ps_.require_absent(k);
   dense_ = load_conv_bn(ps_, arena_, false, "xvector.dense.linear.weight", "xvector.dense.nonlinear.batchnorm");
   SD_CHECK(dense_.w.Cin == 2 * CamTrunk::kChannels && dense_.w.kw == 1, kErrParam,
            "xvector.dense.linear.weight must be (E, 1024, 1)");
   SD_CHECK(dense_.w.N == cfg_.embedding_size, kErrParam, "xvector.dense.linear.weight rows != embedding_size");
-  auto extra = ps_.unused();
-  if (!extra.empty()) {
-    std::string msg = "Unexpected key(s) in state_dict:";
-    for (size_t i = 0; i < extra.size() && i < 8; ++i) msg += " \"" + extra[i] + "\"";
-    throw Error{kErrParam, msg};
-  }
+  ps_.require_all_used();
   trunk_.alloc(arena_, cfg_.max_batch, cfg_.max_frames);
   stats_ = static_cast<float*>(arena_.alloc((size_t)cfg_.max_batch * 2 * CamTrunk::kChannels * sizeof(float)));
   finalized_ = true;

@@ -7,6 +7,7 @@
 // embeddings generate_chunk_speaker_embedding_from_modelscope_for_diarization.py:271-304
 // writes and ts_vad_dataset.py:494-537 reads back.
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 #include "encoder.h"
@@ -24,9 +25,31 @@ struct DenseL {
 // 1-D conv (channel-last rows of stride lda) as an implicit GEMM; out row stride ldo.
 ConvGemmArgs cam_conv1d(Tens in, int B, int T, int lda, const ConvL& L, int stride, int pad, int dil, Tens out,
                         int ldo);
+// TS-VAD's output layer: fc over the rows (b, t) of x (B, T, lda) fp32, written as logits (B, NS, T).
+ConvGemmArgs logits_fc(float* x, int B, int T, int lda, const ConvL& fc, int NS, float* logits);
+// 2-D conv on an NHWC map (C = L.w.Cin) as an implicit GEMM -> NHWC out.
+ConvGemmArgs conv2d(Tens in, int B, int H, int W, const ConvL& L, int sh, int sw, int ph, int pw, Tens out);
 // Conv weight + optional folded BatchNorm (alpha/beta epilogue) + optional conv bias.
 ConvL load_conv_bn(ParamStore& ps, DeviceArena& arena, bool bf16, const std::string& wname,
                    const std::string& bn, const std::string& bias = "");
+
+// BasicResBlock of the CAM++ FCM head (cam_pplus_wespeaker.py:236-268) and of the ResNet34 trunk
+// (resnet_wespeaker.py:35-67): conv3x3 + BN + ReLU, conv3x3 + BN, + (1x1 conv + BN shortcut | input), ReLU.
+struct ResBlockL {
+  ConvL c1, c2, sc;
+  bool has_sc = false;
+  int stride = 1;
+};
+// Reads `p`{conv1.weight, bn1, conv2.weight, bn2} and, with has_sc, `p`{shortcut.0.weight, shortcut.1}.
+ResBlockL load_res_block(ParamStore& ps, DeviceArena& arena, bool bf16, const std::string& p, int stride, bool has_sc);
+// One block over the (B, H, W, C) map in `cur`, one of the three rotating buffers; H / W become the output map's
+// and the buffer that holds it is returned.  sw: conv1's and the shortcut's stride along W (rb.stride along H).
+// The trunk chooses the kernels: conv1(p, t2) launches conv1 + BN + ReLU and returns whether it also wrote the
+// shortcut branch to t2 (else conv_gemm computes it); conv2(r) launches conv2 + BN + residual + ReLU and may
+// redirect r's output first.
+float* run_res_block(const ResBlockL& rb, float* const bufs[3], float* cur, bool bf, int B, int& H, int& W, int sw,
+                     const std::function<bool(const ConvGemmArgs& p, float* t2)>& conv1,
+                     const std::function<void(ConvGemmArgs& r)>& conv2, hipStream_t st);
 
 class CamTrunk {
  public:
@@ -53,8 +76,7 @@ class CamTrunk {
   float* ws(DeviceArena& a, size_t n) { return static_cast<float*>(a.alloc(n * sizeof(float))); }
   bool bf16_ = false;
   ConvL fcm_conv1_;  // fp32 3x3 Cin=1 weights (32x9) + folded bn
-  struct ResBlock { ConvL c1, c2, sc; bool has_sc; int stride; };
-  std::vector<ResBlock> fcm_blocks_;
+  std::vector<ResBlockL> fcm_blocks_;
   ConvL fcm_conv2_;
   ConvL tdnn_;
   std::vector<std::vector<DenseL>> dense_;

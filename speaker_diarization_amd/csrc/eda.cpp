@@ -73,12 +73,7 @@ void EdaModel::finalize() {
     lin_w_ = ld.up("eda.linear.weight");
     lin_b_ = ld.up("eda.linear.bias");
   }
-  auto extra = ps_.unused();
-  if (!extra.empty()) {
-    std::string msg = "Unexpected key(s) in state_dict:";
-    for (size_t i = 0; i < extra.size() && i < 8; ++i) msg += " \"" + extra[i] + "\"";
-    throw Error{kErrParam, msg};
-  }
+  ps_.require_all_used();
   // Workspace.
   const int64_t rows = (int64_t)cfg_.max_seqs * cfg_.max_frames;
   X_ = ws(rows * E);

@@ -106,12 +106,7 @@ void FsEendModel::finalize() {
     fus_.n21g = ld.up(p + "norm21.weight"); fus_.n21b = ld.up(p + "norm21.bias");
     fus_.n22g = ld.up(p + "norm22.weight"); fus_.n22b = ld.up(p + "norm22.bias");
   }
-  auto extra = ps_.unused();
-  if (!extra.empty()) {
-    std::string msg = "Unexpected key(s) in state_dict:";
-    for (size_t i = 0; i < extra.size() && i < 8; ++i) msg += " \"" + extra[i] + "\"";
-    throw Error{kErrParam, msg};
-  }
+  ps_.require_all_used();
   const int64_t rows = (int64_t)cfg_.max_seqs * cfg_.max_frames;
   const int64_t grid = rows * cfg_.max_nspks;
   X_ = ws(rows * D);

@@ -24,15 +24,25 @@ const HostTensor& ParamStore::get(const std::string& name) const {
   return it->second;
 }
 
-std::vector<std::string> ParamStore::unused() const {
-  std::vector<std::string> out;
+static void throw_unexpected(const std::vector<std::string>& keys) {
+  std::string msg = "Unexpected key(s) in state_dict:";
+  for (size_t i = 0; i < keys.size() && i < 8; ++i) msg += " \"" + keys[i] + "\"";
+  throw Error{kErrParam, msg};
+}
+
+void ParamStore::require_all_used() const {
+  std::vector<std::string> extra;
   for (auto& kv : t_) {
     const std::string& k = kv.first;
     if (used_.count(k)) continue;
     if (k.size() >= 19 && k.compare(k.size() - 19, 19, "num_batches_tracked") == 0) continue;
-    out.push_back(k);
+    extra.push_back(k);
   }
-  return out;
+  if (!extra.empty()) throw_unexpected(extra);
+}
+
+void ParamStore::require_absent(const std::string& name) const {
+  if (has(name)) throw_unexpected({name});
 }
 
 void ParamStore::bn_fold(const std::string& p, std::vector<float>& scale, std::vector<float>& shift,

@@ -92,9 +92,11 @@ class ParamStore {
   bool has(const std::string& name) const { return t_.count(name) > 0; }
   const HostTensor& get(const std::string& name) const;
   void mark(const std::string& name) const { used_[name] = true; }
-  // Keys that were provided but never consumed (reference "unexpected keys"),
-  // ignoring BatchNorm num_batches_tracked counters.
-  std::vector<std::string> unused() const;
+  // Strict loading (the reference's "unexpected keys"): kErrParam naming up to 8 keys that were provided but
+  // never consumed, ignoring BatchNorm num_batches_tracked counters ...
+  void require_all_used() const;
+  // ... or naming `name` if it was provided (a key the module does not have, e.g. an affine=False BatchNorm's weight)
+  void require_absent(const std::string& name) const;
 
   // Eval BatchNorm (eps 1e-5) as scale/shift; optional preceding conv bias folded in.
   void bn_fold(const std::string& prefix, std::vector<float>& scale, std::vector<float>& shift,

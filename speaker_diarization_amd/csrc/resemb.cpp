@@ -16,7 +16,7 @@ void ResEmbModel::finalize() {
   if (cfg_.two_emb_layer) {
     // seg_bn_1 is BatchNorm1d(affine=False) (:142): a weight / bias key is unexpected, not a gamma / beta
     for (const char* k : {"seg_bn_1.weight", "seg_bn_1.bias"})
-      SD_CHECK(!ps_.has(k), kErrParam, std::string("Unexpected key(s) in state_dict: \"") + k + "\"");
+      ps_.require_absent(k);
     // embed_b = W2 (s relu(a) + h) + b2 = (W2 diag(s)) relu(a) + (W2 h + b2)   (:178-180)
     std::vector<float> s, h;
     ps_.bn_fold("seg_bn_1", s, h);
@@ -37,12 +37,7 @@ void ResEmbModel::finalize() {
     seg2_.w = upload_packed(arena_, w, E, E, 1, 1, false);
     seg2_.beta = arena_.upload(b);
   }
-  auto extra = ps_.unused();   // pool.* (TSTP has no parameters), seg_2.* without two_emb_layer, ...
-  if (!extra.empty()) {
-    std::string msg = "Unexpected key(s) in state_dict:";
-    for (size_t i = 0; i < extra.size() && i < 8; ++i) msg += " \"" + extra[i] + "\"";
-    throw Error{kErrParam, msg};
-  }
+  ps_.require_all_used();   // pool.* (TSTP has no parameters), seg_2.* without two_emb_layer, ...
   trunk_.alloc(arena_, cfg_.max_batch, cfg_.max_frames);
   stats_ = static_cast<float*>(arena_.alloc((size_t)cfg_.max_batch * C2 * sizeof(float)));
   ea_ = static_cast<float*>(arena_.alloc((size_t)cfg_.max_batch * E * sizeof(float)));

@@ -10,7 +10,7 @@
 #pragma once
 #include <string>
 #include <vector>
-#include "encoder.h"
+#include "campp.h"
 
 namespace sd {
 
@@ -30,10 +30,9 @@ class ResTrunk {
   bool bf16() const { return bf16_; }
 
  private:
-  struct Block { ConvL c1, c2, sc; bool has_sc = false; int stride = 1; };
   bool bf16_ = false;
   ConvL stem_;   // raw 32 x 9 fp32 weights (pre_s) + folded bn1 for the direct stem kernel
-  std::vector<Block> blocks_;
+  std::vector<ResBlockL> blocks_;
   float *buf_[3] = {nullptr, nullptr, nullptr}, *out_ = nullptr;
 };
 

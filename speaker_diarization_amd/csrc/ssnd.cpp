@@ -122,12 +122,7 @@ void SsndModel::finalize() {
     // Speaker tables read by the host-side offline / online drivers (ssnd_model.py:778-900).
     for (const char* k : {"E_all", "e_pse", "e_non"}) ps_.get(k);
   }
-  auto extra = ps_.unused();
-  if (!extra.empty()) {
-    std::string msg = "Unexpected key(s) in state_dict:";
-    for (size_t i = 0; i < extra.size() && i < 8; ++i) msg += " \"" + extra[i] + "\"";
-    throw Error{kErrParam, msg};
-  }
+  ps_.require_all_used();
   // ---- workspace
   const int64_t Bm = c.max_batch;
   const int T2 = CamTrunk::out_frames(c.max_fbank_frames);

@@ -1,17 +1,19 @@
 // Native TS-VAD forward (egs/alimeeting/ts_vad2/model.py) on gfx950.
 //
+// TsvadModel::forward is one path for every variant:
 //   ref_speech fbank (B, T_fb, 80)
-//     -> CAM++ FCM head + xvector[:-2]       cam_pplus_wespeaker.py:271-399
-//     -> speech_down_or_up conv+BN+ReLU      model.py:385-395 / 406-416
-//   variant 0 (forward_common, model.py:758-897):
-//     -> [ts_embed | mix] + PE, 2-layer transformer per speaker (batched over speakers)
-//     -> backend_down conv(1536->384, k5)+BN+ReLU -> PE -> 2-layer transformer -> fc
-//   variant 1 (forward_common_ots_vad, model.py:669-756):
-//     -> GSP + gsp_fc -> [ts_embed | mix] -> 6-layer Conformer per speaker
-//     -> BiLSTM(1536 -> 2x256) -> fc
-//   variant 2 (speech_encoder_type resnet34_wespeaker, model.py:584-606): the speech encoder is the ResNet34
-//     trunk (resnet.h) -> SpeechFeatUpsample2 transposed conv + BN + ReLU (model.py:114-134); then variant 0's
-//     back end
+//     -> speech encoder trunk (trunk_forward), over the batch or as two window slices on two streams (run_sliced)
+//          variants 0, 1: CAM++ FCM head + xvector[:-2]       cam_pplus_wespeaker.py:271-399
+//          variant 2 (speech_encoder_type resnet34_wespeaker, model.py:584-606): ResNet34 trunk (resnet.h)
+//     -> speech_down_or_up (down_gemm) -> mix (B, T3, SE)
+//          variants 0, 1: conv + BN + ReLU                    model.py:385-395 / 406-416
+//          variant 2: SpeechFeatUpsample2 transposed conv + BN + ReLU (model.py:114-134)
+//     -> transformer_backend, variants 0 and 2 (forward_common, model.py:758-897):
+//          [ts_embed | mix] + PE, 2-layer transformer per speaker (batched over speakers)
+//          -> backend_down conv(1536->384, k5)+BN+ReLU -> PE -> 2-layer transformer -> fc
+//        ots_vad_backend, variant 1 (forward_common_ots_vad, model.py:669-756):
+//          GSP + gsp_fc -> [ts_embed | mix] -> 6-layer Conformer per speaker (conformer_slice: the fused stack,
+//          which runs inside each window slice) -> BiLSTM(1536 -> 2x256) -> fc
 //   -> logits (B, NS, T_lab)
 // All activations are fp32 channel-last; every contraction is conv_gemm (bf16 or
 // exact-f32 MFMA), eval BatchNorms are folded into GEMM prologues/epilogues.
@@ -42,9 +44,11 @@ void TsvadModel::finalize() {
   validate(cfg_);
   const std::string se = "speech_encoder.";
   if (cfg_.variant == 2) {
-    res_.load(ps_, arena_, se, cfg_.bf16);   // resnet_wespeaker.py:108-171
+    res_ = std::make_unique<ResTrunk>();
+    res_->load(ps_, arena_, se, cfg_.bf16);   // resnet_wespeaker.py:108-171
   } else {
-    cam_.load(ps_, arena_, se, cfg_.bf16);   // cam_pplus_wespeaker.py:271-372
+    cam_ = std::make_unique<CamTrunk>();
+    cam_->load(ps_, arena_, se, cfg_.bf16);   // cam_pplus_wespeaker.py:271-372
     // The pooled embedding head (stats + dense) is not on the get_time_out path.
     for (const char* k : {"xvector.dense.linear.weight", "xvector.dense.nonlinear.batchnorm.running_mean",
                           "xvector.dense.nonlinear.batchnorm.running_var"})
@@ -89,8 +93,8 @@ void TsvadModel::finalize() {
   } else {
     down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
     down_bn_ = bn_only("speech_down_or_up.1.bn");
-    down_.pre_s = cam_.out_s();
-    down_.pre_h = cam_.out_h();
+    down_.pre_s = cam_->out_s();
+    down_.pre_h = cam_->out_h();
   }
 
   if (cfg_.variant == 0 || cfg_.variant == 2) {
@@ -150,38 +154,40 @@ void TsvadModel::finalize() {
     if (!cfg_.bf16) lstm_hh_lo_ = upload_bf16_lo(arena_, whh);
     fc_ = loader().linear("fc");
   }
-  auto extra = ps_.unused();
-  if (!extra.empty()) {
-    std::string msg = "Unexpected key(s) in state_dict:";
-    for (size_t i = 0; i < extra.size() && i < 8; ++i) msg += " \"" + extra[i] + "\"";
-    throw Error{kErrParam, msg};
-  }
+  ps_.require_all_used();
   alloc_workspace();
   finalized_ = true;
 }
 
+TsvadModel::Geometry TsvadModel::geometry() const {
+  Geometry g;
+  g.T3 = mix_frames(cfg_.max_fbank_frames);
+  g.Tl = std::max<int64_t>(g.T3 + 3, (int64_t)cfg_.rs_len * 25);   // the longest label a forward accepts
+  g.rows = (int64_t)cfg_.max_batch * cfg_.max_num_speaker * g.Tl;
+  g.mix_elems = (int64_t)cfg_.max_batch * g.T3 * cfg_.speaker_embed_dim;
+  g.token_elems = g.rows * cfg_.embed_dim;
+  return g;
+}
+
 void TsvadModel::alloc_workspace() {
-  const int64_t Bm = cfg_.max_batch, Tf = cfg_.max_fbank_frames;
-  const int64_t T3 = mix_frames((int)Tf);
-  const int64_t Tl = std::max<int64_t>(T3 + 3, (int64_t)cfg_.rs_len * 25);
-  const int64_t NS = cfg_.max_num_speaker, E = cfg_.embed_dim;
-  if (cfg_.variant == 2) res_.alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
-  else cam_.alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
-  mix_ = ws(Bm * T3 * cfg_.speaker_embed_dim);
-  mixg_ = ws(Bm * T3 * cfg_.speaker_embed_dim);
-  const int64_t rows = Bm * NS * Tl;
-  X_ = ws(rows * E);
-  Y_ = ws(rows * E);
-  QKV_ = ws(rows * 3 * E);
-  AO_ = ws(rows * E);
-  H_ = ws(rows * std::max<int64_t>({(int64_t)cfg_.ffn_dim, 2 * E, (int64_t)cfg_.conformer_ffn}));
-  X2_ = ws(rows * E);
+  const Geometry g = geometry();
+  const int64_t Bm = cfg_.max_batch, NS = cfg_.max_num_speaker, E = cfg_.embed_dim;
+  if (res_) res_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
+  else cam_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
+  mix_ = ws(g.mix_elems);
+  mixg_ = ws(g.mix_elems);
+  X_ = ws(g.token_elems);
+  Y_ = ws(g.token_elems);
+  QKV_ = ws(g.token_elems * 3);
+  AO_ = ws(g.token_elems);
+  H_ = ws(g.rows * std::max<int64_t>({(int64_t)cfg_.ffn_dim, 2 * E, (int64_t)cfg_.conformer_ffn}));
+  X2_ = ws(g.token_elems);
   partial_ = ws(Bm * NS * ((E + 63) / 64) * 2);
   lstm_work_ = ws(lstm_work_floats((int)Bm, cfg_.lstm_hidden, 2));
   nonfinite_ = static_cast<int*>(arena_.alloc(4 * (size_t)Bm * sizeof(int)));
   if (proj_b_) {
     pts_ = ws(Bm * NS * E);
-    pmix_ = ws(Bm * T3 * E);
+    pmix_ = ws(Bm * g.T3 * E);
   }
 }
 
@@ -226,15 +232,13 @@ void TsvadModel::forward_graph(const float* ref, const float* ts, int B, int Tf,
 }
 
 void TsvadModel::debug_buffer(int which, void** ptr, int64_t* bytes) const {
-  const int64_t Bm = cfg_.max_batch, T3 = mix_frames(cfg_.max_fbank_frames);
-  const int64_t Tl = std::max<int64_t>(T3 + 3, (int64_t)cfg_.rs_len * 25), E = cfg_.embed_dim, SE = cfg_.speaker_embed_dim;
-  const int64_t NS = cfg_.max_num_speaker;
+  const Geometry g = geometry();
   switch (which) {
-    case 0: *ptr = mix_; *bytes = Bm * T3 * SE * 4; break;
-    case 1: *ptr = mixg_; *bytes = Bm * T3 * SE * 4; break;
-    case 2: *ptr = X2_; *bytes = Bm * NS * Tl * E * 4; break;
-    case 3: *ptr = H_; *bytes = Bm * NS * Tl * E * 4; break;
-    case 4: *ptr = Y_; *bytes = Bm * NS * Tl * E * 4; break;
+    case 0: *ptr = mix_; *bytes = g.mix_elems * 4; break;
+    case 1: *ptr = mixg_; *bytes = g.mix_elems * 4; break;
+    case 2: *ptr = X2_; *bytes = g.token_elems * 4; break;
+    case 3: *ptr = H_; *bytes = g.token_elems * 4; break;
+    case 4: *ptr = Y_; *bytes = g.token_elems * 4; break;
     default: throw Error{kErrInvalid, "debug_buffer: unknown buffer"};
   }
 }
@@ -242,7 +246,7 @@ void TsvadModel::debug_buffer(int which, void** ptr, int64_t* bytes) const {
 // forward_common's back end from the mix embeddings on (model.py:856-897), shared by variants 0 and 2: mix_ holds
 // speech_down_or_up's conv + bias (B, T3, SE); its BatchNorm1D + ReLU are applied on load (sd_bn).
 void TsvadModel::transformer_backend(const float* ts, int T3, int B, int Tl, float* logits, hipStream_t st,
-                                     const BnRelu& sd_bn, const BnRelu& bd_bn, const int* win_fb, const int* win_ts) {
+                                     const BnRelu& sd_bn, const BnRelu& bd_bn) {
   const bool bf = cfg_.bf16;
   const int E = cfg_.embed_dim, SE = cfg_.speaker_embed_dim, NS = cfg_.max_num_speaker, S = B * NS;
   // Per-speaker encoder over S = B*NS sequences (model.py:869-879).
@@ -270,43 +274,100 @@ void TsvadModel::transformer_backend(const float* ts, int T3, int B, int Tl, flo
   if (bf) f32_to_bf16(X_, (int64_t)B * Tl * E, enc_work().AO, st);
   for (size_t i = 0; i < multi_.size(); ++i)
     run_transformer(multi_[i], X_, B, Tl, E, cfg_.num_attention_head, nullptr, enc_work(), st, 0, 0, bf || i > 0);
-  ConvGemmArgs f = cam_conv1d(Tens{X_, false}, B, Tl, E, fc_, 1, 0, 1, Tens{logits, false}, 1);
-  f.o_sb = (int64_t)NS * Tl; f.o_sw = 1; f.o_sn = Tl;
-  conv_gemm(f, bf, st);
-  poison_windows(logits, B, (int64_t)NS * Tl, win_fb, win_ts, st);
+  conv_gemm(logits_fc(X_, B, Tl, E, fc_, NS, logits), bf, st);
 }
 
-// Variant 2: ResNet34 trunk (two window slices on two streams for large batches, like CAM++), the transposed-conv
-// upsampler as one conv_gemm, then the transformer back end.
-void TsvadModel::forward_resnet(const float* ref, const float* ts, int B, int Tf, int Tl, float* logits,
-                                hipStream_t st, bool two, const BnRelu& sd_bn, const BnRelu& bd_bn,
-                                const int* win_fb, const int* win_ts) {
+// forward_common_ots_vad's back end (model.py:669-756) over windows [b0, b0 + Bh) up to the BiLSTM, with the fused
+// conformer stack: gsp_fc on the slice's mix rows, then the stack with every buffer addressed from the slice's
+// first row (bf16 y / qkv / ao / h, fp32 X, per-sequence GroupNorm partials, the speaker streams).
+void TsvadModel::conformer_slice(const float* ts, int T3, int b0, int Bh, int Tl, hipStream_t s, const BnRelu& sd_bn) {
+  const int E = cfg_.embed_dim, SE = cfg_.speaker_embed_dim, NS = cfg_.max_num_speaker;
+  const int64_t m0 = (int64_t)b0 * T3 * SE, s0 = (int64_t)b0 * NS, r0 = s0 * Tl;
+  BnRelu sb = sd_bn;
+  sb.win0 = b0;
+  gsp_fc(mix_ + m0, Bh * T3, SE, SE, gsp_w_, gsp_b_, SE, mixg_ + m0, SE, s, sb, T3);
+  auto at = [](float* p, int64_t bytes) { return reinterpret_cast<float*>(reinterpret_cast<char*>(p) + bytes); };
+  EncoderWork w = enc_work();
+  w.Y = at(Y_, r0 * E * 2);
+  w.QKV = at(QKV_, r0 * 3 * E * 2);
+  w.AO = at(AO_, r0 * E * 2);
+  w.H = at(H_, r0 * 2 * E * 2);
+  w.partial = partial_ + s0 * ((E + 63) / 64) * 2;
+  SpeakerStreams io;
+  io.ts = ts + s0 * SE; io.mix = mixg_ + m0; io.ldmix = SE; io.Tmix = T3; io.NS = NS;
+  io.out = at(X2_, (int64_t)b0 * Tl * NS * E * 2);
+  run_conformer_stack(conf_, X_ + r0 * E, Bh * NS, Tl, E, cfg_.conformer_heads, cfg_.conformer_kernel, nullptr, w, s,
+                      &io);
+}
+
+// The rest of that back end from the mix embeddings on.  conformer_done: conformer_slice has run over every window
+// (X2_ holds the stack's output); else gsp_fc and the conformer stack run here, layer by layer over the batch.
+void TsvadModel::ots_vad_backend(const float* ts, int T3, int B, int Tl, float* logits, hipStream_t st,
+                                 const BnRelu& sd_bn, bool conformer_done) {
   const bool bf = cfg_.bf16;
-  const int SE = cfg_.speaker_embed_dim;
-  const int T4 = ResTrunk::out_frames(Tf), T3 = 2 * T4;
-  // model.py:849-854; the reference's own -1 branch raises too (its pad call is misspelt: AttributeError)
-  SD_CHECK(T3 - Tl <= 2 && T3 - Tl >= -1, kErrShape,
-           "label and ref_speech(mix speech) diff: " + std::to_string(T3 - Tl));
-  SD_CHECK(T3 - Tl != -1, kErrShape,
+  const int E = cfg_.embed_dim, SE = cfg_.speaker_embed_dim, NS = cfg_.max_num_speaker, Hh = cfg_.lstm_hidden;
+  if (!conformer_done) {
+    gsp_fc(mix_, B * T3, SE, SE, gsp_w_, gsp_b_, SE, mixg_, SE, st, sd_bn, T3);
+    build_speaker_input(ts, mixg_, SE, T3, B, NS, Tl, SE, nullptr, X_, st);
+    run_conformer_stack(conf_, X_, B * NS, Tl, E, cfg_.conformer_heads, cfg_.conformer_kernel, nullptr, enc_work(), st);
+    speakers_to_channels(X_, B, NS, Tl, E, X2_, bf, st);
+  }
+  conv_gemm(lin(Tens{X2_, bf}, B * Tl, NS * E, lstm_ih_, lstm_b_, Tens{H_, false}, 8 * Hh), bf, st);
+  // SDIAR_LSTM_FP32 (diagnostic, tools/parity_stages.py): the exact-fp32 recurrence in bf16 mode too
+  static const bool lstm_fp32 = getenv("SDIAR_LSTM_FP32") != nullptr;
+  const bool x3 = !bf && gemm_x3();   // bf16x3 (precision 2): the split recurrence; fp32: exact step kernel
+  lstm_recurrence(H_, B, Tl, Hh, 2, lstm_hh_, nullptr, nullptr, nullptr, Y_, 2 * Hh, nullptr,
+                  nullptr, lstm_work_, st, (bf && !lstm_fp32) || x3 ? lstm_hh_bf_ : nullptr, lstm_err_.get(0),
+                  x3 ? lstm_hh_lo_ : nullptr);
+  conv_gemm(logits_fc(Y_, B, Tl, 2 * Hh, fc_, NS, logits), bf, st);
+}
+
+void TsvadModel::check_label_frames(int T3, int Tl) const {
+  const std::string diff = "label and ref_speech(mix speech) diff: " + std::to_string(T3 - Tl);
+  if (cfg_.variant == 1) {
+    SD_CHECK(std::abs(T3 - Tl) <= 3, kErrShape, diff);
+    return;
+  }
+  // model.py:849-854; with the ResNet34 encoder the reference's own -1 branch raises too (its pad call is
+  // misspelt: AttributeError)
+  SD_CHECK(T3 - Tl <= 2 && T3 - Tl >= -1, kErrShape, diff);
+  SD_CHECK(cfg_.variant != 2 || T3 - Tl != -1, kErrShape,
            "label and ref_speech(mix speech) diff: -1 (the reference raises here: module 'torch.nn' has no "
            "attribute 'functinal')");
   SD_CHECK(Tl <= pe_len_, kErrShape, "label length exceeds positional-encoding max_len");
-  Tens x4;
-  if (two) {
-    const int B1 = B / 2;
-    SD_HIP(hipEventRecord(ev_fork_, st));
-    SD_HIP(hipStreamWaitEvent(side_, ev_fork_, 0));
-    x4 = res_.forward(ref, B1, Tf, st, 0);
-    (void)res_.forward(ref, B - B1, Tf, side_, B1);
-    SD_HIP(hipEventRecord(ev_join_, side_));
-    SD_HIP(hipStreamWaitEvent(st, ev_join_, 0));
-  } else {
-    x4 = res_.forward(ref, B, Tf, st);
+}
+
+void TsvadModel::run_sliced(int B, bool two, hipStream_t st,
+                            const std::function<void(int b0, int Bh, hipStream_t s)>& body) {
+  if (!two) {
+    body(0, B, st);
+    return;
   }
-  // (B, T4, 2560) -> (B, T4, [y[2j] | y[2j+1]]) = (B, 2 T4, SE): conv + bias; BatchNorm1D + ReLU by the consumer
-  ConvGemmArgs up = cam_conv1d(x4, B, T4, ResTrunk::kChannels, down_, 1, 1, 1, Tens{mix_, false}, 2 * SE);
-  conv_gemm(up, bf, st);
-  transformer_backend(ts, T3, B, Tl, logits, st, sd_bn, bd_bn, win_fb, win_ts);
+  if (!side_) {
+    SD_HIP(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
+    SD_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
+    SD_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
+  }
+  const int B1 = B / 2;
+  SD_HIP(hipEventRecord(ev_fork_, st));
+  SD_HIP(hipStreamWaitEvent(side_, ev_fork_, 0));
+  body(0, B1, st);
+  body(B1, B - B1, side_);
+  SD_HIP(hipEventRecord(ev_join_, side_));
+  SD_HIP(hipStreamWaitEvent(st, ev_join_, 0));
+}
+
+Tens TsvadModel::trunk_forward(const float* ref, int Bh, int Tf, hipStream_t s, int b0) const {
+  return res_ ? res_->forward(ref, Bh, Tf, s, b0) : cam_->forward(ref, Bh, Tf, s, b0);
+}
+
+// conv + bias, fp32 out; its BatchNorm1D + ReLU are applied by the consumer (gsp_fc / build_speaker_input)
+ConvGemmArgs TsvadModel::down_gemm(Tens x, int Bh, int Tf, float* out) const {
+  const int SE = cfg_.speaker_embed_dim;
+  // ResNet34: (Bh, T4, 2560) -> (Bh, T4, [y[2j] | y[2j+1]]) = (Bh, 2 T4, SE), the upsampler as a k3 pad-1 conv
+  if (res_) return cam_conv1d(x, Bh, ResTrunk::out_frames(Tf), ResTrunk::kChannels, down_, 1, 1, 1, Tens{out, false}, 2 * SE);
+  // CAM++: k5 stride-2 pad-2 conv, out_nonlinear's BN-ReLU fused as its prologue
+  return cam_conv1d(x, Bh, CamTrunk::out_frames(Tf), CamTrunk::kChannels, down_, 2, 2, 1, Tens{out, false}, SE);
 }
 
 // Direct launches.  A hipGraph replay of this forward (forward_graph above) measured no faster on C2 (34.3 vs
@@ -321,26 +382,18 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   SD_CHECK(finalized_, kErrState, "model not finalized");
   SD_CHECK(B >= 1 && B <= cfg_.max_batch, kErrInvalid, "batch exceeds max_batch");
   SD_CHECK(Tf >= 8 && Tf <= cfg_.max_fbank_frames, kErrInvalid, "fbank frames exceed max_fbank_frames");
-  // an earlier forward's LSTM report nobody collected with sd_tsvad_status
-  lstm_err_.raise_if_set();
-  cam_.raise_if_set();
+  raise_if_set();
+  const int T3 = mix_frames(Tf);
+  check_label_frames(T3, Tl);
   const bool bf = cfg_.bf16;
-  // CAM++ up to transit3, (B, T2, 512).  Batches of more than one round of CUs run as two window slices on
-  // two streams (bit-identical per window: every CAM++ kernel computes a window independently of the rest
-  // of the batch); so does the fused conformer stack below.  SDIAR_CAM_ONE_STREAM: one launch sequence over
-  // the whole batch.
+  const int E = cfg_.embed_dim, SE = cfg_.speaker_embed_dim, NS = cfg_.max_num_speaker;
+  // Batches of more than one round of CUs run the speech encoder as two window slices on two streams
+  // (bit-identical per window: every kernel up to the BiLSTM computes a window independently of the rest of the
+  // batch).  SDIAR_CAM_ONE_STREAM: one launch sequence over the whole batch.
   // Under the libsdiar kernel timer (bench.py's extra profiled step) the forward stays on one stream, so
   // each kernel's HIP-event time is its own and not shared with the other slice's kernels.
   static const bool one_stream_env = getenv("SDIAR_CAM_ONE_STREAM") != nullptr;
-  const bool one_stream = one_stream_env || prof_enabled();
-  const int E = cfg_.embed_dim, SE = cfg_.speaker_embed_dim, NS = cfg_.max_num_speaker;
-  const int T2 = CamTrunk::out_frames(Tf);
-  const bool two = !one_stream && B >= 384;
-  if (two && !side_) {
-    SD_HIP(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
-    SD_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-    SD_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-  }
+  const bool two = !(one_stream_env || prof_enabled()) && B >= 384;
   // ---------------- BatchNorm1D's NaN bypass: which windows hold a non-finite input, which reference forwards
   // (groups of forward_batch windows) therefore skip the BatchNorm (from the inputs alone, so first: the window
   // slices below then need nothing from each other until the LSTM)
@@ -357,101 +410,29 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   BnRelu sd_bn = down_bn_, bd_bn = backend_bn_;
   sd_bn.grp = grp_sd; sd_bn.group = G;
   bd_bn.grp = grp_bd; bd_bn.group = G;
-  if (cfg_.variant == 2) {
-    forward_resnet(ref, ts, B, Tf, Tl, logits, st, two, sd_bn, bd_bn, win_fb, win_ts);
-    return;
-  }
-  // speech_down_or_up conv geometry (its output frame count T3)
-  const int T3 = cam_conv1d(Tens{nullptr, bf}, 1, T2, CamTrunk::kChannels, down_, 2, 2, 1, Tens{mix_, false}, SE).Wo;
+  // ---------------- speech encoder + speech_down_or_up -> mix_ (B, T3, SE)
   const bool fused_v1 = cfg_.variant == 1 && SE == 192 && E == 2 * SE && conformer_stack_fused(conf_, E, bf);
-  // v1 conformer stack over windows [b0, b0 + Bh): every buffer of the fused stack is addressed from the slice's
-  // first row (bf16 y / qkv / ao / h, fp32 X, per-sequence GroupNorm partials, the speaker streams)
-  auto conformer_slice = [&](int b0, int Bh, hipStream_t s) {
-    const int64_t s0 = (int64_t)b0 * NS, r0 = s0 * Tl;
-    auto at = [](float* p, int64_t bytes) { return reinterpret_cast<float*>(reinterpret_cast<char*>(p) + bytes); };
-    EncoderWork w = enc_work();
-    w.Y = at(Y_, r0 * E * 2);
-    w.QKV = at(QKV_, r0 * 3 * E * 2);
-    w.AO = at(AO_, r0 * E * 2);
-    w.H = at(H_, r0 * 2 * E * 2);
-    w.partial = partial_ + s0 * ((E + 63) / 64) * 2;
-    SpeakerStreams io;
-    io.ts = ts + s0 * SE; io.mix = mixg_ + (int64_t)b0 * T3 * SE; io.ldmix = SE; io.Tmix = T3; io.NS = NS;
-    io.out = at(X2_, (int64_t)b0 * Tl * NS * E * 2);
-    run_conformer_stack(conf_, X_ + r0 * E, Bh * NS, Tl, E, cfg_.conformer_heads, cfg_.conformer_kernel, nullptr, w,
-                        s, &io);
-  };
-  if (fused_v1) SD_CHECK(std::abs(T3 - Tl) <= 3, kErrShape, "label and ref_speech(mix speech) diff: " + std::to_string(T3 - Tl));
-  if (fused_v1 && two) {
-    // Two window slices, each through the whole per-window part of the model on its own stream: CAM++ trunk,
-    // speech_down conv, gsp_fc, conformer stack.  Nothing joins between the trunk and the conformer, so one
-    // slice's HBM-bound CAM++ kernels overlap the other's MFMA-bound conformer programs (bit-identical per
-    // window: every kernel up to the LSTM computes a window independently of the rest of the batch).
-    const int B1 = B / 2;
-    SD_HIP(hipEventRecord(ev_fork_, st));
-    SD_HIP(hipStreamWaitEvent(side_, ev_fork_, 0));
-    auto slice = [&](int b0, int Bh, hipStream_t s) {
-      const Tens x4s = cam_.forward(ref, Bh, Tf, s, b0);
-      float* mx = mix_ + (int64_t)b0 * T3 * SE;
-      conv_gemm(cam_conv1d(x4s, Bh, T2, CamTrunk::kChannels, down_, 2, 2, 1, Tens{mx, false}, SE), bf, s);
-      BnRelu sb = sd_bn;
-      sb.win0 = b0;
-      gsp_fc(mx, Bh * T3, SE, SE, gsp_w_, gsp_b_, SE, mixg_ + (int64_t)b0 * T3 * SE, SE, s, sb, T3);
-      conformer_slice(b0, Bh, s);
-    };
-    slice(0, B1, st);
-    slice(B1, B - B1, side_);
-    SD_HIP(hipEventRecord(ev_join_, side_));
-    SD_HIP(hipStreamWaitEvent(st, ev_join_, 0));
-  } else {
-  // CAM++ up to transit3, (B, T2, 512): two window slices on two streams for large batches (v0)
-  Tens x4;
-  if (two) {
-    const int B1 = B / 2;
-    SD_HIP(hipEventRecord(ev_fork_, st));
-    SD_HIP(hipStreamWaitEvent(side_, ev_fork_, 0));
-    x4 = cam_.forward(ref, B1, Tf, st, 0);
-    (void)cam_.forward(ref, B - B1, Tf, side_, B1);
-    SD_HIP(hipEventRecord(ev_join_, side_));
-    SD_HIP(hipStreamWaitEvent(st, ev_join_, 0));
-  } else {
-    x4 = cam_.forward(ref, B, Tf, st);
-  }
-  // ---------------- speech_down_or_up conv (out_nonlinear BN-ReLU fused as prologue) + bias, fp32 out; its
-  // BatchNorm1D + ReLU are applied by the consumer (gsp_fc / build_speaker_input)
-  ConvGemmArgs pd = cam_conv1d(x4, B, T2, CamTrunk::kChannels, down_, 2, 2, 1, Tens{mix_, false}, SE);
-  conv_gemm(pd, bf, st);
-  const int S = B * NS;
-  if (cfg_.variant == 0) {
-    SD_CHECK(T3 - Tl <= 2 && T3 - Tl >= -1, kErrShape,
-             "label and ref_speech(mix speech) diff: " + std::to_string(T3 - Tl));
-    SD_CHECK(Tl <= pe_len_, kErrShape, "label length exceeds positional-encoding max_len");
-    transformer_backend(ts, T3, B, Tl, logits, st, sd_bn, bd_bn, win_fb, win_ts);
-    return;
-  }
-  SD_CHECK(std::abs(T3 - Tl) <= 3, kErrShape, "label and ref_speech(mix speech) diff: " + std::to_string(T3 - Tl));
-  gsp_fc(mix_, B * T3, SE, SE, gsp_w_, gsp_b_, SE, mixg_, SE, st, sd_bn, T3);
   if (fused_v1) {
-    conformer_slice(0, B, st);
+    // Each slice runs the whole per-window part of the model on its own stream: trunk, speech_down conv, gsp_fc,
+    // conformer stack.  Nothing joins between the trunk and the conformer, so one slice's HBM-bound CAM++ kernels
+    // overlap the other's MFMA-bound conformer programs.
+    run_sliced(B, two, st, [&](int b0, int Bh, hipStream_t s) {
+      const Tens x4 = trunk_forward(ref, Bh, Tf, s, b0);
+      conv_gemm(down_gemm(x4, Bh, Tf, mix_ + (int64_t)b0 * T3 * SE), bf, s);
+      conformer_slice(ts, T3, b0, Bh, Tl, s, sd_bn);
+    });
   } else {
-    build_speaker_input(ts, mixg_, SE, T3, B, NS, Tl, SE, nullptr, X_, st);
-    run_conformer_stack(conf_, X_, S, Tl, E, cfg_.conformer_heads, cfg_.conformer_kernel, nullptr, enc_work(), st);
-    speakers_to_channels(X_, B, NS, Tl, E, X2_, bf, st);
+    // the trunk alone runs sliced; the speech_down_or_up GEMM covers the whole batch after the join
+    Tens x4{};
+    run_sliced(B, two, st, [&](int b0, int Bh, hipStream_t s) {
+      const Tens x = trunk_forward(ref, Bh, Tf, s, b0);
+      if (b0 == 0) x4 = x;   // the batch's output map
+    });
+    conv_gemm(down_gemm(x4, B, Tf, mix_), bf, st);
   }
-  }
-  {
-    const int Hh = cfg_.lstm_hidden;
-    conv_gemm(lin(Tens{X2_, bf}, B * Tl, NS * E, lstm_ih_, lstm_b_, Tens{H_, false}, 8 * Hh), bf, st);
-    // SDIAR_LSTM_FP32 (diagnostic, tools/parity_stages.py): the exact-fp32 recurrence in bf16 mode too
-    static const bool lstm_fp32 = getenv("SDIAR_LSTM_FP32") != nullptr;
-    const bool x3 = !bf && gemm_x3();   // bf16x3 (precision 2): the split recurrence; fp32: exact step kernel
-    lstm_recurrence(H_, B, Tl, Hh, 2, lstm_hh_, nullptr, nullptr, nullptr, Y_, 2 * Hh, nullptr,
-                    nullptr, lstm_work_, st, (bf && !lstm_fp32) || x3 ? lstm_hh_bf_ : nullptr, lstm_err_.get(0),
-                    x3 ? lstm_hh_lo_ : nullptr);
-    ConvGemmArgs f = cam_conv1d(Tens{Y_, false}, B, Tl, 2 * Hh, fc_, 1, 0, 1, Tens{logits, false}, 1);
-    f.o_sb = (int64_t)NS * Tl; f.o_sw = 1; f.o_sn = Tl;
-    conv_gemm(f, bf, st);
-  }
+  // ---------------- back end -> logits (B, NS, Tl)
+  if (cfg_.variant == 1) ots_vad_backend(ts, T3, B, Tl, logits, st, sd_bn, fused_v1);
+  else transformer_backend(ts, T3, B, Tl, logits, st, sd_bn, bd_bn);
   // a window whose fbank or target-speaker embeddings hold a NaN / Inf has NaN logits in the reference
   poison_windows(logits, B, (int64_t)NS * Tl, win_fb, win_ts, st);
 }

@@ -1,5 +1,7 @@
 // Native TS-VAD inference runner (owns folded weights + workspace).
 #pragma once
+#include <functional>
+#include <memory>
 #include <vector>
 #include "campp.h"
 #include "resnet.h"
@@ -54,8 +56,7 @@ class TsvadModel {
   // waits for `st` and raises kErrHip if a persistent LSTM of the forwards enqueued on it timed out
   void status(hipStream_t st) {
     SD_HIP(hipStreamSynchronize(st));
-    lstm_err_.raise_if_set();
-    cam_.raise_if_set();
+    raise_if_set();
   }
   ~TsvadModel();
 
@@ -63,11 +64,29 @@ class TsvadModel {
   ConvL conv_bn(const std::string& wname, const std::string& bn, const std::string& bias = "");
   LayerLoader loader() { return LayerLoader{ps_, arena_, cfg_.bf16}; }
   EncoderWork enc_work() const { return EncoderWork{Y_, QKV_, AO_, H_, partial_, cfg_.bf16}; }
+  // Workspace sizes at max_batch windows of max_fbank_frames: frames of a mix row block, label frames of a token
+  // row block, token rows, and the elements of the mix (B, T3, SE) and token (rows, E) buffers.
+  struct Geometry { int64_t T3, Tl, rows, mix_elems, token_elems; };
+  Geometry geometry() const;
   void alloc_workspace();
+  // an earlier forward's report nobody collected with sd_tsvad_status: a persistent LSTM's, cam_dense's
+  void raise_if_set() {
+    lstm_err_.raise_if_set();
+    if (cam_) cam_->raise_if_set();
+  }
+  // The reference's label-length rules (model.py:703-710 / 849-854) and the positional encoding's length.
+  void check_label_frames(int T3, int Tl) const;
+  // body(b0, Bh, stream) over the batch's windows: once over all of them on st, or (two) over two window slices, the
+  // second on side_ between a fork from and a join to st.
+  void run_sliced(int B, bool two, hipStream_t st, const std::function<void(int b0, int Bh, hipStream_t s)>& body);
+  // speech_encoder.* over windows [b0, b0 + Bh) of the batch, and the speech_down_or_up GEMM over Bh windows of it
+  Tens trunk_forward(const float* ref, int Bh, int Tf, hipStream_t s, int b0) const;
+  ConvGemmArgs down_gemm(Tens x, int Bh, int Tf, float* out) const;
+  void conformer_slice(const float* ts, int T3, int b0, int Bh, int Tl, hipStream_t s, const BnRelu& sd_bn);
+  void ots_vad_backend(const float* ts, int T3, int B, int Tl, float* logits, hipStream_t st, const BnRelu& sd_bn,
+                       bool conformer_done);
   void transformer_backend(const float* ts, int T3, int B, int Tl, float* logits, hipStream_t st, const BnRelu& sd_bn,
-                           const BnRelu& bd_bn, const int* win_fb, const int* win_ts);
-  void forward_resnet(const float* ref, const float* ts, int B, int Tf, int Tl, float* logits, hipStream_t st,
-                      bool two, const BnRelu& sd_bn, const BnRelu& bd_bn, const int* win_fb, const int* win_ts);
+                           const BnRelu& bd_bn);
   float* ws(size_t n) { return static_cast<float*>(arena_.alloc(n * sizeof(float))); }
 
   TsvadConfig cfg_;
@@ -76,8 +95,9 @@ class TsvadModel {
   PinnedFlags lstm_err_;   // poll-timeout reports of the persistent LSTMs (lstm.hip), one slot each
   bool finalized_ = false;
 
-  CamTrunk cam_;     // speech_encoder.* (CAM++ get_time_out=True), variants 0 and 1
-  ResTrunk res_;     // speech_encoder.* (ResNet34 get_time_out=True), variant 2
+  // speech_encoder.* (get_time_out=True): the one trunk the variant uses, the other stays empty
+  std::unique_ptr<CamTrunk> cam_;   // CAM++, variants 0 and 1
+  std::unique_ptr<ResTrunk> res_;   // ResNet34, variant 2
   // frames of the speech_down_or_up output for T_fb fbank frames (the conv's stride 2, or the upsampler's 2 T')
   int mix_frames(int Tf) const {
     return cfg_.variant == 2 ? 2 * ResTrunk::out_frames(Tf) : (CamTrunk::out_frames(Tf) - 1) / 2 + 1;
@@ -104,9 +124,10 @@ class TsvadModel {
   const void* lstm_hh_lo_ = nullptr;   // bf16(W_hh - hi) (fp32 handles: the bf16x3 split recurrence)
   ConvL fc_;
 
-  // CAM++ trunk of a large batch as two window slices, the second on side_ (fork / join events on the
-  // caller's stream): the per-layer launches of one slice fill the CUs the other slice's last round of
-  // workgroups leaves idle (cam_dense: 600 items on 256 CUs = 2.34 rounds of 3).
+  // run_sliced: the speech encoder of a large batch as two window slices, the second on side_ (fork / join
+  // events on the caller's stream; all three created by the first such forward): the per-layer launches of one
+  // slice fill the CUs the other slice's last round of workgroups leaves idle (cam_dense: 600 items on 256 CUs =
+  // 2.34 rounds of 3).
   hipStream_t side_ = nullptr;
   hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
 

@@ -69,12 +69,7 @@ void TsvadStreamModel::finalize() {
     pe_ = arena_.upload(pe.data);
   }
   fc_ = LayerLoader{ps_, arena_, cfg_.bf16}.linear("fc");
-  auto extra = ps_.unused();
-  if (!extra.empty()) {
-    std::string msg = "Unexpected key(s) in state_dict:";
-    for (size_t i = 0; i < extra.size() && i < 8; ++i) msg += " \"" + extra[i] + "\"";
-    throw Error{kErrParam, msg};
-  }
+  ps_.require_all_used();
   // CAM++ workspace by total frames: a window's chunks hold 4 * T_lab fbank frames in all, and
   // the trunk's buffers scale with items x frames (see CamTrunk::alloc).
   const int64_t Tm = (int64_t)cfg_.max_windows * cfg_.max_labels, NS = cfg_.max_num_speaker, E = cfg_.embed_dim;
@@ -169,9 +164,7 @@ void TsvadStreamModel::forward(const float* feats, const float* ts, int B, int T
   per_chunk_runs(down);
   // ---- multi-speaker encoder (no positional encoding: model.py:853-858) + fc
   run_layers(multi_, X_, B, T_lab, chunk, left, st);
-  ConvGemmArgs f = cam_conv1d(Tens{X_, false}, B, T_lab, E, fc_, 1, 0, 1, Tens{logits, false}, 1);
-  f.o_sb = (int64_t)NS * T_lab; f.o_sw = 1; f.o_sn = T_lab;
-  conv_gemm(f, bf, st);
+  conv_gemm(logits_fc(X_, B, T_lab, E, fc_, NS, logits), bf, st);
 }
 
 }  // namespace sd

@@ -112,21 +112,24 @@ from speaker_diarization_amd.ts_vad.model import TSVADModel
 from speaker_diarization_amd.weights import TSVADConfig, tsvad_state_dict, to_torch
 dev = torch.device("cuda", 0)
 h = hashlib.sha256()
-for v in (1, 0):
-    cfg = TSVADConfig(rs_len=4) if v == 0 else TSVADConfig.ots_vad_v1(rs_len=4)
-    B = 400
+# variant 2 (ResNet34): B = 385 is just past the slice threshold (384) and odd, so the slices are unequal (192 / 193);
+# 38 fbank frames -> 2 * 5 = 10 upsampler frames = the label length, the shortest window the goldens pin
+for cfg, B, T, nl in ((TSVADConfig.ots_vad_v1(rs_len=4), 400, 398, 100), (TSVADConfig(rs_len=4), 400, 398, 100),
+                      (TSVADConfig(speech_encoder_type="resnet34_wespeaker"), 385, 38, 10)):
     m = TSVADModel(cfg, device=dev, precision="bf16", max_batch=B)
     m.load_state_dict(to_torch(tsvad_state_dict(cfg, seed=11)))
-    x, ts = tsvad_inputs(B, 398, 100, seed=5)
-    out = m.forward(torch.from_numpy(x).to(dev), torch.from_numpy(ts).to(dev), 100)
+    x, ts = tsvad_inputs(B, T, nl, seed=5)
+    out = m.forward(torch.from_numpy(x).to(dev), torch.from_numpy(ts).to(dev), nl)
     h.update(out.float().cpu().numpy().tobytes())
+    del m
 print("HASH " + h.hexdigest())
 """
 
 
 def test_cam_two_stream_slices_bit_identical(gpu):
-    """TS-VAD batches of >= 384 windows run the CAM++ trunk as two window slices on two streams
-    (tsvad.cpp); the logits must be bit-identical to one launch sequence over the whole batch."""
+    """TS-VAD batches of >= 384 windows run the speech encoder (CAM++ or ResNet34; for the fused ots_vad model the
+    conformer stack too) as two window slices on two streams (tsvad.cpp run_sliced); the logits of variants 1, 0
+    and 2 must be bit-identical to one launch sequence over the whole batch."""
     hashes = []
     for one in (False, True):
         env = dict(os.environ)

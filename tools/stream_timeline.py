@@ -4,7 +4,7 @@
 
 The trace is `rocprofv3 --kernel-trace --output-format csv` of `bench.py --workload c2` WITHOUT
 SDIAR_CAM_ONE_STREAM, i.e. the shipped schedule: two window slices on two HIP streams (tsvad.cpp
-`slice`), then the BiLSTM and the tail on the main stream.  A step is the span from one `fbank_kernel`
+`run_sliced`), then the BiLSTM and the tail on the main stream.  A step is the span from one `fbank_kernel`
 launch to the next.  For the chosen step (default: the last complete one) it prints, per stream, the
 spans of the kernel families (CAM++ trunk, conformer stack, BiLSTM, tail), the time both streams have
 kernels in flight, the idle gaps, and which stream's last kernel ends the slice phase - the stream that
