@@ -128,9 +128,6 @@ _SIGS = {
     "sd_probe_lstm_granule2": (c_int, [c_int, c_void_p, c_void_p]),
     "sd_probe_lstm_granule": (c_int, [c_int, c_void_p, c_void_p]),
     "sd_probe_lstm_handoff": (c_int, [c_int, c_void_p, c_void_p]),
-    "sd_tsvad_create": (c_int, [POINTER(TsvadConfig), POINTER(c_void_p)]),
-    "sd_tsvad_set_param": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
-    "sd_tsvad_finalize": (c_int, [c_void_p]),
     "sd_tsvad_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sd_tsvad_status": (c_int, [c_void_p, c_void_p]),
     "sd_tsvad_forward_batched": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
@@ -138,51 +135,19 @@ _SIGS = {
     "sd_tsvad_forward_graph": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_char_p,
                                        c_void_p]),
     "sd_tsvad_debug_buffer": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_int64)]),
-    "sd_tsvad_device_bytes": (c_int64, [c_void_p]),
-    "sd_tsvad_destroy": (c_int, [c_void_p]),
-    "sd_tsvad_stream_create": (c_int, [POINTER(TsvadStreamConfig), POINTER(c_void_p)]),
-    "sd_tsvad_stream_set_param": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
-    "sd_tsvad_stream_finalize": (c_int, [c_void_p]),
     "sd_tsvad_stream_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                         c_void_p]),
-    "sd_tsvad_stream_device_bytes": (c_int64, [c_void_p]),
-    "sd_tsvad_stream_destroy": (c_int, [c_void_p]),
-    "sd_ssnd_create": (c_int, [POINTER(SsndConfig), POINTER(c_void_p)]),
-    "sd_ssnd_set_param": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
-    "sd_ssnd_finalize": (c_int, [c_void_p]),
     "sd_ssnd_infer": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_ssnd_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "sd_ssnd_device_bytes": (c_int64, [c_void_p]),
-    "sd_ssnd_destroy": (c_int, [c_void_p]),
-    "sd_campp_create": (c_int, [POINTER(CamppConfig), POINTER(c_void_p)]),
-    "sd_campp_set_param": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
-    "sd_campp_finalize": (c_int, [c_void_p]),
     "sd_campp_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "sd_campp_device_bytes": (c_int64, [c_void_p]),
-    "sd_campp_destroy": (c_int, [c_void_p]),
-    "sd_resnet34_create": (c_int, [POINTER(Resnet34Config), POINTER(c_void_p)]),
-    "sd_resnet34_set_param": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
-    "sd_resnet34_finalize": (c_int, [c_void_p]),
     "sd_resnet34_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "sd_resnet34_device_bytes": (c_int64, [c_void_p]),
-    "sd_resnet34_destroy": (c_int, [c_void_p]),
-    "sd_eda_create": (c_int, [POINTER(EdaConfig), POINTER(c_void_p)]),
-    "sd_eda_set_param": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
-    "sd_eda_finalize": (c_int, [c_void_p]),
     "sd_eda_input_stride": (c_int, [c_void_p]),
     "sd_eda_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
     "sd_eda_status": (c_int, [c_void_p, c_void_p]),
-    "sd_eda_device_bytes": (c_int64, [c_void_p]),
-    "sd_eda_destroy": (c_int, [c_void_p]),
-    "sd_fseend_create": (c_int, [POINTER(FseendConfig), POINTER(c_void_p)]),
-    "sd_fseend_set_param": (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int]),
-    "sd_fseend_finalize": (c_int, [c_void_p]),
     "sd_fseend_input_stride": (c_int, [c_void_p]),
     "sd_fseend_test": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
-    "sd_fseend_device_bytes": (c_int64, [c_void_p]),
-    "sd_fseend_destroy": (c_int, [c_void_p]),
     "sd_fseend_stream_create": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "sd_fseend_stream_push": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, POINTER(c_int), c_void_p]),
     "sd_fseend_stream_set_audio": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
@@ -239,6 +204,17 @@ _SIGS = {
                            c_void_p, c_void_p, c_void_p]),
 }
 
+# The handle lifecycle, the same five calls for every model kind (include/sdiar.h): create -> set_param* -> finalize
+# -> <the kind's forward calls>* -> destroy, device_bytes at any time.
+KINDS = {"tsvad": TsvadConfig, "tsvad_stream": TsvadStreamConfig, "eda": EdaConfig, "fseend": FseendConfig,
+         "campp": CamppConfig, "resnet34": Resnet34Config, "ssnd": SsndConfig}
+for _kind, _conf in KINDS.items():
+    _SIGS[f"sd_{_kind}_create"] = (c_int, [POINTER(_conf), POINTER(c_void_p)])
+    _SIGS[f"sd_{_kind}_set_param"] = (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int])
+    _SIGS[f"sd_{_kind}_finalize"] = (c_int, [c_void_p])
+    _SIGS[f"sd_{_kind}_device_bytes"] = (c_int64, [c_void_p])
+    _SIGS[f"sd_{_kind}_destroy"] = (c_int, [c_void_p])
+
 EXPORTED = tuple(_SIGS)
 
 _lib = None
@@ -291,23 +267,23 @@ def call(name: str, *args):
     check(getattr(load(), name)(*args), name)
 
 
-def create_handle(kind: str, conf, state) -> ctypes.c_void_p:
-    """sd_<kind>_create + set_param for every state_dict entry (reference key names)
-    + finalize; the handle is destroyed again if any step fails."""
-    import numpy as np
-    lib = load()
-    h = ctypes.c_void_p()
-    call(f"sd_{kind}_create", ctypes.byref(conf), ctypes.byref(h))
-    try:
-        for k, v in state.items():
-            a = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
-            shape = (c_int64 * max(a.ndim, 1))(*a.shape)
-            call(f"sd_{kind}_set_param", h, k.encode(), a.ctypes.data_as(c_void_p), shape, a.ndim)
-        call(f"sd_{kind}_finalize", h)
-    except Exception:
-        getattr(lib, f"sd_{kind}_destroy")(h)
-        raise
-    return h
+PRECISION = {"fp32": 0, "bf16": 1, "bf16x3": 2}
+
+
+def precision_code(precision: str, allowed=("bf16", "fp32", "bf16x3")) -> int:
+    """The C API's precision of a wrapper's `precision` argument; ValueError for one the kind does not build."""
+    if precision not in allowed:
+        raise ValueError(f"precision must be {', '.join(allowed[:-1])} or {allowed[-1]}, got {precision}")
+    return PRECISION[precision]
+
+
+def hip_device(device, what: str):
+    """torch.device of a wrapper's `device` argument (None: the current HIP device); ValueError off the GPU."""
+    import torch
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise ValueError(f"{what} (MI355X backend) runs on a HIP device only")
+    return dev
 
 
 def host_state(state_dict) -> dict:
@@ -315,6 +291,63 @@ def host_state(state_dict) -> dict:
     import numpy as np
     return {k: (v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v, dtype=np.float32))
             for k, v in state_dict.items()}
+
+
+def load_params(kind: str, h, state):
+    """sd_<kind>_set_param for every state_dict entry (reference key names), then sd_<kind>_finalize."""
+    import numpy as np
+    for k, a in host_state(state).items():
+        data = np.ascontiguousarray(a)
+        shape = (c_int64 * max(a.ndim, 1))(*a.shape)
+        call(f"sd_{kind}_set_param", h, k.encode(), data.ctypes.data_as(c_void_p), shape, a.ndim)
+    call(f"sd_{kind}_finalize", h)
+
+
+def create_handle(kind: str, conf, state) -> ctypes.c_void_p:
+    """sd_<kind>_create + load_params; the handle is destroyed again if any step fails."""
+    h = ctypes.c_void_p()
+    call(f"sd_{kind}_create", ctypes.byref(conf), ctypes.byref(h))
+    try:
+        load_params(kind, h, state)
+    except Exception:
+        getattr(load(), f"sd_{kind}_destroy")(h)
+        raise
+    return h
+
+
+class Handle:
+    """Owner of one sd_<kind> handle, mixed into every model wrapper.  `_h` is the raw c_void_p the kind's forward
+    calls take (None while a lazy wrapper has not loaded weights).  Eager wrappers _create() in their constructor and
+    _load() in load_state_dict; lazy ones build a loaded handle with create_handle() and _adopt() it."""
+    kind = None
+    _h = None
+
+    def _create(self, conf):
+        h = ctypes.c_void_p()
+        call(f"sd_{self.kind}_create", ctypes.byref(conf), ctypes.byref(h))
+        self._h = h
+
+    def _load(self, state):
+        load_params(self.kind, self._h, state)
+
+    def _adopt(self, h):
+        """Replace the handle (the new one exists before the old one goes, so a failed reload keeps the old)."""
+        self._release()
+        self._h = h
+
+    def _release(self):
+        h, self._h = self._h, None
+        if h is not None and _lib is not None:      # never loads the library just to destroy nothing
+            getattr(_lib, f"sd_{self.kind}_destroy")(h)
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def _device_bytes(self) -> int:
+        return int(getattr(load(), f"sd_{self.kind}_device_bytes")(self._h)) if self._h is not None else 0
 
 
 def ptr(t) -> int:

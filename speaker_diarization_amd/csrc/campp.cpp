@@ -297,8 +297,7 @@ Tens CamTrunk::forward(const float* fbank, int B, int Tf, hipStream_t st, int b0
 }
 
 // ------------------------------------------------------------------------------ CamppModel
-void CamppModel::finalize() {
-  SD_CHECK(!finalized_, kErrState, "finalize called twice");
+void CamppModel::build() {
   SD_CHECK(cfg_.feat_dim == 80, kErrInvalid, "CAM++ FCM head supports feat_dim 80 only");
   trunk_.load(ps_, arena_, "", cfg_.bf16);
   // xvector.dense (cam_pplus_wespeaker.py:219-233, 380-382): the pooled head is tiny
@@ -313,11 +312,10 @@ void CamppModel::finalize() {
   ps_.require_all_used();
   trunk_.alloc(arena_, cfg_.max_batch, cfg_.max_frames);
   stats_ = static_cast<float*>(arena_.alloc((size_t)cfg_.max_batch * 2 * CamTrunk::kChannels * sizeof(float)));
-  finalized_ = true;
 }
 
 void CamppModel::forward(const float* fbank, int B, int Tf, float* emb, float* time_out, hipStream_t st) {
-  SD_CHECK(finalized_, kErrState, "model not finalized");
+  require_finalized();
   trunk_.raise_if_set();   // an earlier call's cam_dense report
   SD_CHECK(B >= 1 && B <= cfg_.max_batch, kErrInvalid, "batch exceeds max_batch");
   SD_CHECK(Tf >= 8 && Tf <= cfg_.max_frames, kErrInvalid, "fbank frames exceed max_frames");

@@ -98,22 +98,16 @@ struct CamppConfig {
   bool bf16 = false;
 };
 
-class CamppModel {
+class CamppModel : public ModelCore {
  public:
   explicit CamppModel(const CamppConfig& c) : cfg_(c) {}
-  ParamStore& params() { return ps_; }
-  void finalize();
-  bool finalized() const { return finalized_; }
-  size_t device_bytes() const { return arena_.total(); }
   // fbank (B, Tf, 80) -> emb (B, embedding_size) (forward(x), :388-399) and/or
   // time_out (B, T', 512) channel-last = relu(out_nonlinear(x)) (forward(x, get_time_out=True)).
   void forward(const float* fbank, int B, int Tf, float* emb, float* time_out, hipStream_t st);
 
  private:
+  void build() override;
   CamppConfig cfg_;
-  ParamStore ps_;
-  DeviceArena arena_;
-  bool finalized_ = false;
   CamTrunk trunk_;
   ConvL dense_;            // xvector.dense: Conv1d(1024 -> E, 1, bias=False) + BatchNorm1d(affine=False)
   float* stats_ = nullptr; // (max_batch, 1024) [mean | std]

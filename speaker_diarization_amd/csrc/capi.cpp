@@ -5,6 +5,7 @@
 #include <cmath>
 #include <memory>
 #include <string>
+#include <utility>
 
 #include <algorithm>
 
@@ -25,40 +26,21 @@ void set_error(const std::string& m) { g_err = m; }
 const char* last_error() { return g_err.c_str(); }
 }  // namespace sd
 
-struct sd_tsvad {
+// Every opaque handle type of sdiar.h is this, over its kind's runner.
+template <class M>
+struct Handle {
   bool x3 = false;   // precision 2: conv_gemm's exact path in bf16x3 (GemmX3Scope around compute)
-  std::unique_ptr<sd::TsvadModel> model;
+  std::unique_ptr<M> model;
 };
 
-struct sd_eda {
-  bool x3 = false;   // precision 2: conv_gemm's exact path in bf16x3 (GemmX3Scope around compute)
-  std::unique_ptr<sd::EdaModel> model;
-};
-
-struct sd_campp {
-  std::unique_ptr<sd::CamppModel> model;
-};
-
-struct sd_resnet34 {
-  std::unique_ptr<sd::ResEmbModel> model;
-};
-
-struct sd_ssnd {
-  std::unique_ptr<sd::SsndModel> model;
-};
-
-struct sd_tsvad_stream {
-  std::unique_ptr<sd::TsvadStreamModel> model;
-};
-
-struct sd_fseend {
-  bool x3 = false;   // precision 2: conv_gemm's exact path in bf16x3 (GemmX3Scope around compute)
-  std::unique_ptr<sd::FsEendModel> model;
-};
-
-struct sd_fseend_stream {
-  std::unique_ptr<sd::FsEendStream> s;
-};
+struct sd_tsvad : Handle<sd::TsvadModel> {};
+struct sd_tsvad_stream : Handle<sd::TsvadStreamModel> {};
+struct sd_eda : Handle<sd::EdaModel> {};
+struct sd_fseend : Handle<sd::FsEendModel> {};
+struct sd_fseend_stream : Handle<sd::FsEendStream> {};
+struct sd_campp : Handle<sd::CamppModel> {};
+struct sd_resnet34 : Handle<sd::ResEmbModel> {};
+struct sd_ssnd : Handle<sd::SsndModel> {};
 
 namespace {
 
@@ -92,6 +74,65 @@ struct Scratch {
   }
 };
 
+// `w` (N, Cin, taps) packed into scratch as conv_gemm's Wt[N][tap * Cin + c], bf16 bits when bf; a null w (an
+// optional weight the caller does not have) leaves the scratch unpacked.
+struct PackedScratch : Scratch {
+  PackedScratch(const float* w, int N, int Cin, int taps, bool bf, hipStream_t s)
+      : Scratch((size_t)N * Cin * taps * (bf ? 2 : 4), s) {
+    if (w) sd::pack_weight(w, N, Cin, taps, p, bf, s);
+  }
+};
+
+// The A operand a test op hands conv_gemm: the caller's fp32 activations, or their bf16 copy at precision 2.
+struct Activations : Scratch {
+  const void* a;
+  bool bf16;
+  Activations(const float* x, int64_t n, int precision, hipStream_t s)
+      : Scratch(precision == 2 ? (size_t)n * 2 : 4, s), a(x), bf16(precision == 2) {
+    if (!bf16) return;
+    sd::f32_to_bf16(x, n, p, s);
+    a = p;
+  }
+};
+
+// ---- the handle lifecycle, the same for every kind: create -> set_param* -> finalize -> (forward)* -> destroy
+// The tail of every sd_<kind>_create, after its argument checks: *out receives the handle only once its runner is
+// constructed, so a throwing constructor leaks nothing.
+template <class H, class... Args>
+void create(H** out, bool x3, Args&&... args) {
+  auto h = std::make_unique<H>();
+  h->x3 = x3;
+  h->model.reset(new typename decltype(h->model)::element_type(std::forward<Args>(args)...));
+  *out = h.release();
+}
+
+template <class H>
+int set_param(H* h, const char* name, const float* data, const int64_t* shape, int ndim) {
+  return guard([&] {
+    SD_CHECK(h && name && (data || ndim == 0), sd::kErrInvalid, "null argument");
+    SD_CHECK(!h->model->finalized(), sd::kErrState, "set_param after finalize");
+    h->model->params().set(name, data, shape, ndim);
+  });
+}
+
+template <class H>
+int finalize(H* h) {
+  return guard([&] {
+    SD_CHECK(h, sd::kErrInvalid, "null handle");
+    h->model->finalize();
+  });
+}
+
+template <class H>
+int64_t device_bytes(const H* h) {
+  return h ? (int64_t)h->model->device_bytes() : 0;
+}
+
+template <class H>
+int destroy(H* h) {
+  return guard([&] { delete h; });
+}
+
 }  // namespace
 
 extern "C" {
@@ -117,18 +158,19 @@ int sd_prof_query(int i, char* name, int name_len, int64_t* launches, double* fl
 
 double sd_prof_query_steps(int i) { return sd::prof_query_steps(i); }
 
-int sd_probe_lstm_granule(int steps, float* us_per_step, void* stream) {
+static int probe_lstm_granule(const char* what, int steps, float* us_per_step, void* stream, int nwg) {
   return guard([&] {
-    SD_CHECK(steps >= 1 && us_per_step, sd::kErrInvalid, "probe_lstm_granule: bad argument");
-    *us_per_step = sd::lstm_granule_probe(steps, S(stream));
+    SD_CHECK(steps >= 1 && us_per_step, sd::kErrInvalid, std::string(what) + ": bad argument");
+    *us_per_step = sd::lstm_granule_probe(steps, S(stream), nwg);
   });
 }
 
+int sd_probe_lstm_granule(int steps, float* us_per_step, void* stream) {
+  return probe_lstm_granule("probe_lstm_granule", steps, us_per_step, stream, 4);
+}
+
 int sd_probe_lstm_granule2(int steps, float* us_per_step, void* stream) {
-  return guard([&] {
-    SD_CHECK(steps >= 1 && us_per_step, sd::kErrInvalid, "probe_lstm_granule2: bad argument");
-    *us_per_step = sd::lstm_granule_probe(steps, S(stream), 2);
-  });
+  return probe_lstm_granule("probe_lstm_granule2", steps, us_per_step, stream, 2);
 }
 
 int sd_probe_lstm_handoff(int steps, float* us_per_step, void* stream) {
@@ -161,28 +203,15 @@ int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
     t.ffn_dim = c->transformer_ffn_embed_dim;
     t.speaker_embed_dim = c->speaker_embed_dim;
     sd::TsvadModel::validate(t);   // proj_layer configurations (speaker_embed_dim * 2 != transformer_embed_dim)
-    auto* h = new sd_tsvad;
-    h->x3 = c->precision == 2;
-    h->model.reset(new sd::TsvadModel(t));
-    *out = h;
+    create(out, c->precision == 2, t);
   });
 }
 
-int sd_tsvad_set_param(sd_tsvad* h, const char* name, const float* data, const int64_t* shape,
-                       int ndim) {
-  return guard([&] {
-    SD_CHECK(h && name && (data || ndim == 0), sd::kErrInvalid, "null argument");
-    SD_CHECK(!h->model->finalized(), sd::kErrState, "set_param after finalize");
-    h->model->params().set(name, data, shape, ndim);
-  });
+int sd_tsvad_set_param(sd_tsvad* h, const char* name, const float* data, const int64_t* shape, int ndim) {
+  return set_param(h, name, data, shape, ndim);
 }
 
-int sd_tsvad_finalize(sd_tsvad* h) {
-  return guard([&] {
-    SD_CHECK(h, sd::kErrInvalid, "null handle");
-    h->model->finalize();
-  });
-}
+int sd_tsvad_finalize(sd_tsvad* h) { return finalize(h); }
 
 int sd_tsvad_forward(sd_tsvad* h, const float* ref, const float* ts, int B, int Tf, int Tl,
                      float* logits, void* stream) {
@@ -225,11 +254,9 @@ int sd_tsvad_forward_batched(sd_tsvad* h, const float* ref, const float* ts, int
   });
 }
 
-int64_t sd_tsvad_device_bytes(const sd_tsvad* h) { return h ? (int64_t)h->model->device_bytes() : 0; }
+int64_t sd_tsvad_device_bytes(const sd_tsvad* h) { return device_bytes(h); }
 
-int sd_tsvad_destroy(sd_tsvad* h) {
-  return guard([&] { delete h; });
-}
+int sd_tsvad_destroy(sd_tsvad* h) { return destroy(h); }
 
 int sd_eda_create(const sd_eda_config* c, sd_eda** out) {
   return guard([&] {
@@ -253,27 +280,15 @@ int sd_eda_create(const sd_eda_config* c, sd_eda** out) {
     t.max_n_speakers = c->max_n_speakers;
     t.n_speakers = c->n_speakers;
     t.bf16 = c->precision == 1;
-    auto* h = new sd_eda;
-    h->x3 = c->precision == 2;
-    h->model.reset(new sd::EdaModel(t));
-    *out = h;
+    create(out, c->precision == 2, t);
   });
 }
 
 int sd_eda_set_param(sd_eda* h, const char* name, const float* data, const int64_t* shape, int ndim) {
-  return guard([&] {
-    SD_CHECK(h && name && (data || ndim == 0), sd::kErrInvalid, "null argument");
-    SD_CHECK(!h->model->finalized(), sd::kErrState, "set_param after finalize");
-    h->model->params().set(name, data, shape, ndim);
-  });
+  return set_param(h, name, data, shape, ndim);
 }
 
-int sd_eda_finalize(sd_eda* h) {
-  return guard([&] {
-    SD_CHECK(h, sd::kErrInvalid, "null handle");
-    h->model->finalize();
-  });
-}
+int sd_eda_finalize(sd_eda* h) { return finalize(h); }
 
 int sd_eda_input_stride(const sd_eda* h) { return h && h->model->finalized() ? h->model->in_ld() : 0; }
 
@@ -293,11 +308,9 @@ int sd_eda_status(sd_eda* h, void* stream) {
   });
 }
 
-int64_t sd_eda_device_bytes(const sd_eda* h) { return h ? (int64_t)h->model->device_bytes() : 0; }
+int64_t sd_eda_device_bytes(const sd_eda* h) { return device_bytes(h); }
 
-int sd_eda_destroy(sd_eda* h) {
-  return guard([&] { delete h; });
-}
+int sd_eda_destroy(sd_eda* h) { return destroy(h); }
 
 int sd_fseend_create(const sd_fseend_config* c, sd_fseend** out) {
   return guard([&] {
@@ -323,27 +336,15 @@ int sd_fseend_create(const sd_fseend_config* c, sd_fseend** out) {
     t.max_frames = c->max_frames;
     t.max_nspks = c->max_nspks;
     t.bf16 = c->precision == 1;
-    auto* h = new sd_fseend;
-    h->x3 = c->precision == 2;
-    h->model.reset(new sd::FsEendModel(t));
-    *out = h;
+    create(out, c->precision == 2, t);
   });
 }
 
 int sd_fseend_set_param(sd_fseend* h, const char* name, const float* data, const int64_t* shape, int ndim) {
-  return guard([&] {
-    SD_CHECK(h && name && (data || ndim == 0), sd::kErrInvalid, "null argument");
-    SD_CHECK(!h->model->finalized(), sd::kErrState, "set_param after finalize");
-    h->model->params().set(name, data, shape, ndim);
-  });
+  return set_param(h, name, data, shape, ndim);
 }
 
-int sd_fseend_finalize(sd_fseend* h) {
-  return guard([&] {
-    SD_CHECK(h, sd::kErrInvalid, "null handle");
-    h->model->finalize();
-  });
-}
+int sd_fseend_finalize(sd_fseend* h) { return finalize(h); }
 
 int sd_fseend_input_stride(const sd_fseend* h) { return h && h->model->finalized() ? h->model->in_ld() : 0; }
 
@@ -356,24 +357,15 @@ int sd_fseend_test(sd_fseend* h, const float* feats, int ld_feats, int S_, int T
   });
 }
 
-int64_t sd_fseend_device_bytes(const sd_fseend* h) { return h ? (int64_t)h->model->device_bytes() : 0; }
+int64_t sd_fseend_device_bytes(const sd_fseend* h) { return device_bytes(h); }
 
-int sd_fseend_destroy(sd_fseend* h) {
-  return guard([&] { delete h; });
-}
+int sd_fseend_destroy(sd_fseend* h) { return destroy(h); }
 
 int sd_fseend_stream_create(sd_fseend* h, int chunk, int max_frames, int max_nspks, int use_graph,
                             sd_fseend_stream** out) {
   return guard([&] {
     SD_CHECK(h && out, sd::kErrInvalid, "null argument");
-    auto* s = new sd_fseend_stream;
-    try {
-      s->s.reset(new sd::FsEendStream(*h->model, chunk, max_frames, max_nspks, use_graph != 0));
-    } catch (...) {
-      delete s;
-      throw;
-    }
-    *out = s;
+    create(out, false, *h->model, chunk, max_frames, max_nspks, use_graph != 0);
   });
 }
 
@@ -381,7 +373,7 @@ int sd_fseend_stream_push(sd_fseend_stream* s, const float* feats, int ld_feats,
                           int* n_out, void* stream) {
   return guard([&] {
     SD_CHECK(s && n_out, sd::kErrInvalid, "null argument");
-    *n_out = s->s->push(feats, ld_feats, n, preds, cap, S(stream));
+    *n_out = s->model->push(feats, ld_feats, n, preds, cap, S(stream));
   });
 }
 
@@ -389,7 +381,7 @@ int sd_fseend_stream_set_audio(sd_fseend_stream* s, const float* mel_fb, int n_m
                                int context_size, int subsampling) {
   return guard([&] {
     SD_CHECK(s, sd::kErrInvalid, "null handle");
-    s->s->set_audio(mel_fb, n_mels, frame_size, frame_shift, context_size, subsampling);
+    s->model->set_audio(mel_fb, n_mels, frame_size, frame_shift, context_size, subsampling);
   });
 }
 
@@ -397,21 +389,21 @@ int sd_fseend_stream_push_audio(sd_fseend_stream* s, const float* samples, int64
                                 int* n_out, void* stream) {
   return guard([&] {
     SD_CHECK(s && n_out, sd::kErrInvalid, "null argument");
-    *n_out = s->s->push_audio(samples, n, preds, cap, S(stream));
+    *n_out = s->model->push_audio(samples, n, preds, cap, S(stream));
   });
 }
 
 int sd_fseend_stream_flush(sd_fseend_stream* s, float* preds, int cap, int* n_out, void* stream) {
   return guard([&] {
     SD_CHECK(s && n_out, sd::kErrInvalid, "null argument");
-    *n_out = s->s->flush(preds, cap, S(stream));
+    *n_out = s->model->flush(preds, cap, S(stream));
   });
 }
 
 int sd_fseend_stream_reset(sd_fseend_stream* s, void* stream) {
   return guard([&] {
     SD_CHECK(s, sd::kErrInvalid, "null handle");
-    s->s->reset(S(stream));
+    s->model->reset(S(stream));
   });
 }
 
@@ -419,27 +411,23 @@ int sd_fseend_stream_stats(const sd_fseend_stream* s, int64_t* enc_runs, int64_t
                            int* dec_nodes) {
   return guard([&] {
     SD_CHECK(s && enc_runs && dec_runs && enc_nodes && dec_nodes, sd::kErrInvalid, "null argument");
-    *enc_runs = s->s->runs(0);
-    *dec_runs = s->s->runs(1);
-    *enc_nodes = s->s->graph_nodes(0);
-    *dec_nodes = s->s->graph_nodes(1);
+    *enc_runs = s->model->runs(0);
+    *dec_runs = s->model->runs(1);
+    *enc_nodes = s->model->graph_nodes(0);
+    *dec_nodes = s->model->graph_nodes(1);
   });
 }
 
 int sd_fseend_stream_debug_counters(const sd_fseend_stream* s, unsigned* host_out, int cap, int* n, void* stream) {
   return guard([&] {
     SD_CHECK(s && n && (host_out || cap == 0), sd::kErrInvalid, "null argument");
-    *n = s->s->debug_counters(host_out, cap, S(stream));
+    *n = s->model->debug_counters(host_out, cap, S(stream));
   });
 }
 
-int64_t sd_fseend_stream_device_bytes(const sd_fseend_stream* s) {
-  return s ? (int64_t)s->s->device_bytes() : 0;
-}
+int64_t sd_fseend_stream_device_bytes(const sd_fseend_stream* h) { return device_bytes(h); }
 
-int sd_fseend_stream_destroy(sd_fseend_stream* s) {
-  return guard([&] { delete s; });
-}
+int sd_fseend_stream_destroy(sd_fseend_stream* h) { return destroy(h); }
 
 int sd_eend_features(const float* wav, int64_t n_samples, int frame_size, int frame_shift, int n_frames,
                      const float* mel_fb, int n_mels, int mean_norm, int context_size, int subsampling,
@@ -462,15 +450,6 @@ int sd_eend_features(const float* wav, int64_t n_samples, int frame_size, int fr
   });
 }
 
-int sd_fbank_kaldi(const float* wav, int64_t n_samples, float in_scale, int n_frames,
-                   const float* mel_fb, int n_mels, float* out, void* stream) {
-  return guard([&] {
-    SD_CHECK(n_frames >= 0 && (n_frames == 0 || n_samples >= 400 + (int64_t)(n_frames - 1) * 160),
-             sd::kErrInvalid, "fbank: n_frames exceeds the samples");
-    sd::fbank_kaldi(wav, n_samples, in_scale, n_frames, mel_fb, n_mels, out, S(stream));
-  });
-}
-
 int sd_fbank_kaldi_ex(const float* wav, int64_t n_samples, float in_scale, int n_frames, const float* mel_fb,
                       int n_mels, int window_type, float* out, void* stream) {
   return guard([&] {
@@ -478,6 +457,11 @@ int sd_fbank_kaldi_ex(const float* wav, int64_t n_samples, float in_scale, int n
              sd::kErrInvalid, "fbank: n_frames exceeds the samples");
     sd::fbank_kaldi(wav, n_samples, in_scale, n_frames, mel_fb, n_mels, out, S(stream), window_type);
   });
+}
+
+int sd_fbank_kaldi(const float* wav, int64_t n_samples, float in_scale, int n_frames,
+                   const float* mel_fb, int n_mels, float* out, void* stream) {
+  return sd_fbank_kaldi_ex(wav, n_samples, in_scale, n_frames, mel_fb, n_mels, /*hamming*/ 0, out, stream);
 }
 
 int sd_tsvad_stream_create(const sd_tsvad_stream_config* c, sd_tsvad_stream** out) {
@@ -501,27 +485,16 @@ int sd_tsvad_stream_create(const sd_tsvad_stream_config* c, sd_tsvad_stream** ou
     t.embed_dim = c->transformer_embed_dim;
     t.ffn_dim = c->transformer_ffn_embed_dim;
     t.speaker_embed_dim = c->speaker_embed_dim;
-    auto* h = new sd_tsvad_stream;
-    h->model.reset(new sd::TsvadStreamModel(t));
-    *out = h;
+    create(out, false, t);
   });
 }
 
 int sd_tsvad_stream_set_param(sd_tsvad_stream* h, const char* name, const float* data, const int64_t* shape,
                               int ndim) {
-  return guard([&] {
-    SD_CHECK(h && name && (data || ndim == 0), sd::kErrInvalid, "null argument");
-    SD_CHECK(!h->model->finalized(), sd::kErrState, "set_param after finalize");
-    h->model->params().set(name, data, shape, ndim);
-  });
+  return set_param(h, name, data, shape, ndim);
 }
 
-int sd_tsvad_stream_finalize(sd_tsvad_stream* h) {
-  return guard([&] {
-    SD_CHECK(h, sd::kErrInvalid, "null handle");
-    h->model->finalize();
-  });
-}
+int sd_tsvad_stream_finalize(sd_tsvad_stream* h) { return finalize(h); }
 
 int sd_tsvad_stream_forward(sd_tsvad_stream* h, const float* feats, const float* ts, int B, int T_label, int chunk,
                             int left_chunks, float* logits, void* stream) {
@@ -532,13 +505,9 @@ int sd_tsvad_stream_forward(sd_tsvad_stream* h, const float* feats, const float*
   });
 }
 
-int64_t sd_tsvad_stream_device_bytes(const sd_tsvad_stream* h) {
-  return h ? (int64_t)h->model->device_bytes() : 0;
-}
+int64_t sd_tsvad_stream_device_bytes(const sd_tsvad_stream* h) { return device_bytes(h); }
 
-int sd_tsvad_stream_destroy(sd_tsvad_stream* h) {
-  return guard([&] { delete h; });
-}
+int sd_tsvad_stream_destroy(sd_tsvad_stream* h) { return destroy(h); }
 
 int sd_campp_create(const sd_campp_config* c, sd_campp** out) {
   return guard([&] {
@@ -553,26 +522,15 @@ int sd_campp_create(const sd_campp_config* c, sd_campp** out) {
     t.max_batch = c->max_batch;
     t.max_frames = c->max_frames;
     t.bf16 = c->precision == 1;
-    auto* h = new sd_campp;
-    h->model.reset(new sd::CamppModel(t));
-    *out = h;
+    create(out, false, t);
   });
 }
 
 int sd_campp_set_param(sd_campp* h, const char* name, const float* data, const int64_t* shape, int ndim) {
-  return guard([&] {
-    SD_CHECK(h && name && (data || ndim == 0), sd::kErrInvalid, "null argument");
-    SD_CHECK(!h->model->finalized(), sd::kErrState, "set_param after finalize");
-    h->model->params().set(name, data, shape, ndim);
-  });
+  return set_param(h, name, data, shape, ndim);
 }
 
-int sd_campp_finalize(sd_campp* h) {
-  return guard([&] {
-    SD_CHECK(h, sd::kErrInvalid, "null handle");
-    h->model->finalize();
-  });
-}
+int sd_campp_finalize(sd_campp* h) { return finalize(h); }
 
 int sd_campp_forward(sd_campp* h, const float* feats, int B, int T, float* emb, float* time_out, void* stream) {
   return guard([&] {
@@ -581,11 +539,9 @@ int sd_campp_forward(sd_campp* h, const float* feats, int B, int T, float* emb, 
   });
 }
 
-int64_t sd_campp_device_bytes(const sd_campp* h) { return h ? (int64_t)h->model->device_bytes() : 0; }
+int64_t sd_campp_device_bytes(const sd_campp* h) { return device_bytes(h); }
 
-int sd_campp_destroy(sd_campp* h) {
-  return guard([&] { delete h; });
-}
+int sd_campp_destroy(sd_campp* h) { return destroy(h); }
 
 int sd_resnet34_create(const sd_resnet34_config* c, sd_resnet34** out) {
   return guard([&] {
@@ -601,26 +557,15 @@ int sd_resnet34_create(const sd_resnet34_config* c, sd_resnet34** out) {
     t.max_batch = c->max_batch;
     t.max_frames = c->max_frames;
     t.bf16 = c->precision == 1;
-    auto* h = new sd_resnet34;
-    h->model.reset(new sd::ResEmbModel(t));
-    *out = h;
+    create(out, false, t);
   });
 }
 
 int sd_resnet34_set_param(sd_resnet34* h, const char* name, const float* data, const int64_t* shape, int ndim) {
-  return guard([&] {
-    SD_CHECK(h && name && (data || ndim == 0), sd::kErrInvalid, "null argument");
-    SD_CHECK(!h->model->finalized(), sd::kErrState, "set_param after finalize");
-    h->model->params().set(name, data, shape, ndim);
-  });
+  return set_param(h, name, data, shape, ndim);
 }
 
-int sd_resnet34_finalize(sd_resnet34* h) {
-  return guard([&] {
-    SD_CHECK(h, sd::kErrInvalid, "null handle");
-    h->model->finalize();
-  });
-}
+int sd_resnet34_finalize(sd_resnet34* h) { return finalize(h); }
 
 int sd_resnet34_forward(sd_resnet34* h, const float* feats, int B, int T, float* emb, float* emb_a, float* time_out,
                         void* stream) {
@@ -630,11 +575,9 @@ int sd_resnet34_forward(sd_resnet34* h, const float* feats, int B, int T, float*
   });
 }
 
-int64_t sd_resnet34_device_bytes(const sd_resnet34* h) { return h ? (int64_t)h->model->device_bytes() : 0; }
+int64_t sd_resnet34_device_bytes(const sd_resnet34* h) { return device_bytes(h); }
 
-int sd_resnet34_destroy(sd_resnet34* h) {
-  return guard([&] { delete h; });
-}
+int sd_resnet34_destroy(sd_resnet34* h) { return destroy(h); }
 
 int sd_ssnd_create(const sd_ssnd_config* c, sd_ssnd** out) {
   return guard([&] {
@@ -657,26 +600,15 @@ int sd_ssnd_create(const sd_ssnd_config* c, sd_ssnd** out) {
     t.num_layers = c->num_layers; t.vad_out_len = c->vad_out_len; t.pos_emb_dim = c->pos_emb_dim;
     t.max_seq_len = c->max_seq_len; t.n_all_speakers = c->n_all_speakers; t.conformer_kernel = c->conformer_kernel;
     t.bf16 = c->precision == 1;
-    auto* h = new sd_ssnd;
-    h->model.reset(new sd::SsndModel(t));
-    *out = h;
+    create(out, false, t);
   });
 }
 
 int sd_ssnd_set_param(sd_ssnd* h, const char* name, const float* data, const int64_t* shape, int ndim) {
-  return guard([&] {
-    SD_CHECK(h && name && (data || ndim == 0), sd::kErrInvalid, "null argument");
-    SD_CHECK(!h->model->finalized(), sd::kErrState, "set_param after finalize");
-    h->model->params().set(name, data, shape, ndim);
-  });
+  return set_param(h, name, data, shape, ndim);
 }
 
-int sd_ssnd_finalize(sd_ssnd* h) {
-  return guard([&] {
-    SD_CHECK(h, sd::kErrInvalid, "null handle");
-    h->model->finalize();
-  });
-}
+int sd_ssnd_finalize(sd_ssnd* h) { return finalize(h); }
 
 int sd_ssnd_infer(sd_ssnd* h, const float* feats, const float* spk, int B, int T_fbank, float* vad, float* emb,
                   void* stream) {
@@ -694,11 +626,9 @@ int sd_ssnd_decode(sd_ssnd* h, const float* enc, const float* x, const float* sp
   });
 }
 
-int64_t sd_ssnd_device_bytes(const sd_ssnd* h) { return h ? (int64_t)h->model->device_bytes() : 0; }
+int64_t sd_ssnd_device_bytes(const sd_ssnd* h) { return device_bytes(h); }
 
-int sd_ssnd_destroy(sd_ssnd* h) {
-  return guard([&] { delete h; });
-}
+int sd_ssnd_destroy(sd_ssnd* h) { return destroy(h); }
 
 int sd_window_cmn(const float* feats, int n_mels, const int* win_start, const int* win_n, int n_win,
                   int T_out, float* out, void* stream) {
@@ -708,24 +638,25 @@ int sd_window_cmn(const float* feats, int n_mels, const int* win_start, const in
   });
 }
 
+// sd_overlap_average (sigmoid of logits, then the mean) and sd_overlap_mean (the mean of probabilities)
+static int overlap(const std::string& what, bool sigmoid, const float* x, int n_win, int NS, int Tw, const int* start,
+                   const int* len, int dis, int chunk, int n_frames, float* out, void* stream) {
+  return guard([&] {
+    SD_CHECK(dis > 0 && chunk > 0, sd::kErrInvalid, what + ": bad window geometry");
+    SD_CHECK((chunk + dis - 1) / dis <= sd::kOverlapMaxWindows, sd::kErrInvalid,
+             what + ": more covering windows per frame than the pairwise mean supports");
+    sd::overlap_average(x, n_win, NS, Tw, start, len, dis, chunk, n_frames, out, S(stream), sigmoid);
+  });
+}
+
 int sd_overlap_average(const float* logits, int n_win, int NS, int Tw, const int* start,
                        const int* len, int dis, int chunk, int n_frames, float* out, void* stream) {
-  return guard([&] {
-    SD_CHECK(dis > 0 && chunk > 0, sd::kErrInvalid, "overlap_average: bad window geometry");
-    SD_CHECK((chunk + dis - 1) / dis <= sd::kOverlapMaxWindows, sd::kErrInvalid,
-             "overlap_average: more covering windows per frame than the pairwise mean supports");
-    sd::overlap_average(logits, n_win, NS, Tw, start, len, dis, chunk, n_frames, out, S(stream));
-  });
+  return overlap("overlap_average", true, logits, n_win, NS, Tw, start, len, dis, chunk, n_frames, out, stream);
 }
 
 int sd_overlap_mean(const float* probs, int n_win, int NS, int Tw, const int* start, const int* len, int dis,
                     int chunk, int n_frames, float* out, void* stream) {
-  return guard([&] {
-    SD_CHECK(dis > 0 && chunk > 0, sd::kErrInvalid, "overlap_mean: bad window geometry");
-    SD_CHECK((chunk + dis - 1) / dis <= sd::kOverlapMaxWindows, sd::kErrInvalid,
-             "overlap_mean: more covering windows per frame than the pairwise mean supports");
-    sd::overlap_average(probs, n_win, NS, Tw, start, len, dis, chunk, n_frames, out, S(stream), false);
-  });
+  return overlap("overlap_mean", false, probs, n_win, NS, Tw, start, len, dis, chunk, n_frames, out, stream);
 }
 
 int sd_postprocess_segments(const float* post, int rows, int T, int med_filter, const float* thresholds,
@@ -758,12 +689,10 @@ int sd_op_linear(const float* x, int M, int K, const float* w, const float* b, i
   return guard([&] {
     hipStream_t st = S(stream);
     const bool bf = precision >= 1;
-    Scratch wt((size_t)N * K * (bf ? 2 : 4), st);
-    sd::pack_weight(w, N, K, 1, wt.p, bf, st);
-    Scratch xb(precision == 2 ? (size_t)M * K * 2 : 4, st);   // precision 2: bf16 activations
-    if (precision == 2) sd::f32_to_bf16(x, (int64_t)M * K, xb.p, st);
-    sd::ConvGemmArgs p = sd::linear_args(precision == 2 ? xb.p : (const void*)x, M, K, K, wt.p, N, out, N);
-    p.a_bf16 = precision == 2;
+    PackedScratch wt(w, N, K, 1, bf, st);
+    Activations xa(x, (int64_t)M * K, precision, st);
+    sd::ConvGemmArgs p = sd::linear_args(xa.a, M, K, K, wt.p, N, out, N);
+    p.a_bf16 = xa.bf16;
     p.beta = b;
     p.act = act;
     sd::conv_gemm(p, bf, st);
@@ -777,8 +706,7 @@ int sd_op_gemm_bf16(const void* x, int M, int K, int lda, int a_coff, const floa
     hipStream_t st = S(stream);
     SD_CHECK(M > 0 && K > 0 && N > 0 && lda >= a_coff + K && ldo >= N, sd::kErrInvalid, "gemm_bf16: bad shape");
     SD_CHECK((pre_scale == nullptr) == (pre_shift == nullptr), sd::kErrInvalid, "gemm_bf16: pre_scale/pre_shift");
-    Scratch wt((size_t)N * K * 2, st);
-    sd::pack_weight(w, N, K, 1, wt.p, true, st);
+    PackedScratch wt(w, N, K, 1, true, st);
     sd::ConvGemmArgs p = sd::linear_args(x, M, K, lda, wt.p, N, out, ldo);
     p.a_bf16 = true;
     p.a_coff = a_coff;
@@ -856,9 +784,7 @@ int sd_op_cam_dense(const void* x, int B, int T, int ld, int cin, int dil, const
     SD_CHECK(B >= 1 && repeats >= 1 && ld >= cin + 32 &&
                  sd::cam_dense_supported(T, cin, ld, 128, 64, 32, 32, 3, dil, 100, true),
              sd::kErrInvalid, "cam_dense: unsupported shape");
-    Scratch wbt((size_t)128 * cin * 2, st), wlt((size_t)32 * 3 * 128 * 2, st);
-    sd::pack_weight(wb, 128, cin, 1, wbt.p, true, st);
-    sd::pack_weight(wl, 32, 128, 3, wlt.p, true, st);   // Wt[o][tap * 128 + c]
+    PackedScratch wbt(wb, 128, cin, 1, true, st), wlt(wl, 32, 128, 3, true, st);   // wlt: Wt[o][tap * 128 + c]
     Scratch rec(sd::cam_dense_record_bytes(B), st), cnt(sd::cam_dense_counter_bytes(B), st);
     SD_HIP(hipMemsetAsync(cnt.p, 0, sd::cam_dense_counter_bytes(B), st));
     for (int r = 0; r < repeats; ++r)
@@ -873,8 +799,7 @@ int sd_op_mha_block(const void* y, const float* w, const float* bias, int nseq, 
     hipStream_t st = S(stream);
     SD_CHECK(nseq >= 1 && sd::mha_block_supported(384, 8, T, true), sd::kErrInvalid, "mha_block: unsupported shape");
     SD_CHECK(flags >= 0 && flags <= 3, sd::kErrInvalid, "mha_block: flags");
-    Scratch wt((size_t)3 * 384 * 384 * 2, st);
-    sd::pack_weight(w, 3 * 384, 384, 1, wt.p, true, st);
+    PackedScratch wt(w, 3 * 384, 384, 1, true, st);
     sd::MhaBlockArgs m;
     m.y = y; m.W = wt.p; m.bias = bias; m.out = out; m.ldo = 384;
     m.S = nseq; m.T = T; m.D = 384; m.nh = 8; m.scale = 1.f / std::sqrt(48.f); m.key_len = key_len;
@@ -890,12 +815,10 @@ int sd_op_conv1d(const float* x, int B, int T, int Cin, const float* w, const fl
   return guard([&] {
     hipStream_t st = S(stream);
     const bool bf = precision >= 1;
-    Scratch wt((size_t)Cout * Cin * k * (bf ? 2 : 4), st);
-    sd::pack_weight(w, Cout, Cin, k, wt.p, bf, st);
-    Scratch xb(precision == 2 ? (size_t)B * T * Cin * 2 : 4, st);
-    if (precision == 2) sd::f32_to_bf16(x, (int64_t)B * T * Cin, xb.p, st);
+    PackedScratch wt(w, Cout, Cin, k, bf, st);
+    Activations xa(x, (int64_t)B * T * Cin, precision, st);
     sd::ConvGemmArgs p;
-    p.A = precision == 2 ? xb.p : (const void*)x; p.a_bf16 = precision == 2; p.B = B; p.H = 1; p.W = T; p.Cin = Cin; p.lda = Cin;
+    p.A = xa.a; p.a_bf16 = xa.bf16; p.B = B; p.H = 1; p.W = T; p.Cin = Cin; p.lda = Cin;
     p.kh = 1; p.kw = k; p.sw = stride; p.pw = pad; p.dw = dil;
     p.Ho = 1; p.Wo = (T + 2 * pad - dil * (k - 1) - 1) / stride + 1;
     SD_CHECK(p.Wo > 0, sd::kErrInvalid, "conv1d: empty output");
@@ -911,12 +834,10 @@ int sd_op_conv2d(const float* x, int B, int H, int W, int Cin, const float* w, i
   return guard([&] {
     hipStream_t st = S(stream);
     const bool bf = precision >= 1;
-    Scratch wt((size_t)Cout * Cin * kh * kw * (bf ? 2 : 4), st);
-    sd::pack_weight(w, Cout, Cin, kh * kw, wt.p, bf, st);
-    Scratch xb(precision == 2 ? (size_t)B * H * W * Cin * 2 : 4, st);
-    if (precision == 2) sd::f32_to_bf16(x, (int64_t)B * H * W * Cin, xb.p, st);
+    PackedScratch wt(w, Cout, Cin, kh * kw, bf, st);
+    Activations xa(x, (int64_t)B * H * W * Cin, precision, st);
     sd::ConvGemmArgs p;
-    p.A = precision == 2 ? xb.p : (const void*)x; p.a_bf16 = precision == 2; p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.lda = Cin;
+    p.A = xa.a; p.a_bf16 = xa.bf16; p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.lda = Cin;
     p.kh = kh; p.kw = kw; p.sh = sh; p.sw = sw; p.ph = ph; p.pw = pw;
     p.Ho = (H + 2 * ph - kh) / sh + 1;
     p.Wo = (W + 2 * pw - kw) / sw + 1;
@@ -935,9 +856,7 @@ int sd_op_res_conv(const void* x, int B, int H, int W, int Cin, const float* w, 
     SD_CHECK(x && w && out && B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2), sd::kErrInvalid,
              "res_conv: bad argument");
     SD_CHECK(!sc_w || (sc_alpha && sc_beta && sc_out), sd::kErrInvalid, "res_conv: incomplete shortcut");
-    Scratch wt((size_t)Cout * Cin * 9 * 2, st), swt((size_t)Cout * Cin * 2, st);
-    sd::pack_weight(w, Cout, Cin, 9, wt.p, true, st);
-    if (sc_w) sd::pack_weight(sc_w, Cout, Cin, 1, swt.p, true, st);
+    PackedScratch wt(w, Cout, Cin, 9, true, st), swt(sc_w, Cout, Cin, 1, true, st);   // sc_w: nullable
     sd::ConvGemmArgs p;
     p.A = x; p.a_bf16 = true; p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.lda = Cin;
     p.kh = 3; p.kw = 3; p.sh = stride; p.sw = stride; p.ph = 1; p.pw = 1;

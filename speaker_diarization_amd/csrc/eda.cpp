@@ -15,8 +15,7 @@
 
 namespace sd {
 
-void EdaModel::finalize() {
-  SD_CHECK(!finalized_, kErrState, "finalize called twice");
+void EdaModel::build() {
   SD_CHECK(cfg_.variant >= 0 && cfg_.variant <= 3, kErrInvalid, "unknown EDA model variant");
   const int E = cfg_.n_units;
   SD_CHECK(E % cfg_.n_heads == 0, kErrInvalid, "n_units must be divisible by n_heads");
@@ -88,12 +87,11 @@ void EdaModel::finalize() {
   hT_ = ws((int64_t)cfg_.max_seqs * E);
   cT_ = ws((int64_t)cfg_.max_seqs * E);
   lstm_work_ = ws(lstm_work_floats(cfg_.max_seqs, E, 1));
-  finalized_ = true;
 }
 
 void EdaModel::forward(const float* feats, int ld_in, int S, int T, const int* lengths, const int* key_len,
                        const int* perm, float* probs, float* act, hipStream_t st) {
-  SD_CHECK(finalized_, kErrState, "model not finalized");
+  require_finalized();
   lstm_err_.raise_if_set();   // an earlier forward's report nobody collected with sd_eda_status
   SD_CHECK(S >= 1 && S <= cfg_.max_seqs, kErrInvalid, "sequences exceed max_seqs");
   SD_CHECK(T >= 1 && T <= cfg_.max_frames, kErrInvalid, "frames exceed max_frames");

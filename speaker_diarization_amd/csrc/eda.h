@@ -23,11 +23,9 @@ struct EdaConfig {
 
 constexpr int kEdaInPad = 8;   // input rows are padded to a multiple of 8 floats (345 -> 352)
 
-class EdaModel {
+class EdaModel : public ModelCore {
  public:
   explicit EdaModel(const EdaConfig& c) : cfg_(c) {}
-  ParamStore& params() { return ps_; }
-  void finalize();
   int in_ld() const { return in_ld_; }
   // feats (S, T, ld_in) fp32 with ld_in >= in_ld(), finite values in the pad columns;
   // lengths (S) device int32 (LSTM / shuffle lengths); key_len (S) device int32 or
@@ -35,19 +33,14 @@ class EdaModel {
   // randperm(lengths[s]).  probs (S, max_n_speakers); act (S, T, max_n_speakers-1).
   void forward(const float* feats, int ld_in, int S, int T, const int* lengths, const int* key_len,
                const int* perm, float* probs, float* act, hipStream_t st);
-  bool finalized() const { return finalized_; }
-  size_t device_bytes() const { return arena_.total(); }
   // waits for `st` and raises kErrHip if a persistent LSTM of the forwards enqueued on it timed out
   void status(hipStream_t st) { SD_HIP(hipStreamSynchronize(st)); lstm_err_.raise_if_set(); }
 
  private:
-  float* ws(size_t n) { return static_cast<float*>(arena_.alloc(n * sizeof(float))); }
+  void build() override;
 
   EdaConfig cfg_;
-  ParamStore ps_;
-  DeviceArena arena_;
   PinnedFlags lstm_err_;   // poll-timeout reports of the persistent LSTMs (lstm.hip), one slot each
-  bool finalized_ = false;
   int in_ld_ = 352;
 
   ConvL in_;

@@ -15,8 +15,7 @@
 
 namespace sd {
 
-void FsEendModel::finalize() {
-  SD_CHECK(!finalized_, kErrState, "finalize called twice");
+void FsEendModel::build() {
   const int D = cfg_.n_units;
   SD_CHECK(D % cfg_.n_heads == 0, kErrInvalid, "n_units must be divisible by n_heads");
   LayerLoader ld{ps_, arena_, cfg_.bf16};
@@ -118,7 +117,6 @@ void FsEendModel::finalize() {
   QKV_ = ws(grid * 3 * D);
   AO_ = ws(grid * D);
   H_ = ws(std::max(grid * cfg_.dec_ffn, rows * (int64_t)cfg_.enc_ffn));
-  finalized_ = true;
 }
 
 void FsEendModel::run_fusion(float* A, int S, int T, int C, hipStream_t st) {
@@ -163,7 +161,7 @@ void FsEendModel::run_fusion(float* A, int S, int T, int C, hipStream_t st) {
 
 void FsEendModel::forward(const float* feats, int ld_in, int S, int T, const int* lengths, int C, float* preds,
                           float* emb_out, float* att_out, hipStream_t st) {
-  SD_CHECK(finalized_, kErrState, "model not finalized");
+  require_finalized();
   SD_CHECK(S >= 1 && S <= cfg_.max_seqs, kErrInvalid, "sequences exceed max_seqs");
   SD_CHECK(T >= 1 && T <= cfg_.max_frames, kErrInvalid, "frames exceed max_frames");
   SD_CHECK(C >= 1 && C <= cfg_.max_nspks, kErrInvalid, "max_nspks exceeds the configured maximum");

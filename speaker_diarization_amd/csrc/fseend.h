@@ -30,29 +30,22 @@ struct FusionL {            // TransformerEncoderFusionLayer (fs_eend.py:282-333
 
 class FsEendStream;
 
-class FsEendModel {
+class FsEendModel : public ModelCore {
  public:
   explicit FsEendModel(const FsEendConfig& c) : cfg_(c) {}
-  ParamStore& params() { return ps_; }
-  void finalize();
   int in_ld() const { return in_ld_; }
   // feats (S, T, ld_in) f32 (pad_sequence(-1) rows beyond a sequence's length);
   // lengths_host (S) frames per sequence; C = max_nspks of test().
   // preds (S, T, C); emb_out (S, T, D) and att_out (S, T, C, D) optional (normalised, as test() returns).
   void forward(const float* feats, int ld_in, int S, int T, const int* lengths_host, int C, float* preds,
                float* emb_out, float* att_out, hipStream_t st);
-  bool finalized() const { return finalized_; }
-  size_t device_bytes() const { return arena_.total(); }
 
  private:
+  void build() override;
   friend class FsEendStream;
-  float* ws(size_t n) { return static_cast<float*>(arena_.alloc(n * sizeof(float))); }
   void run_fusion(float* A, int S, int T, int C, hipStream_t st);
 
   FsEendConfig cfg_;
-  ParamStore ps_;
-  DeviceArena arena_;
-  bool finalized_ = false;
   int in_ld_ = 352;
 
   ConvL in_;

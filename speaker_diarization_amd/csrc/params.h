@@ -112,6 +112,32 @@ class ParamStore {
   mutable std::map<std::string, bool> used_;
 };
 
+// What every model runner behind a C-API handle shares: the parameters it is given, the device memory it
+// owns, and the lifecycle  construct -> params().set()* -> finalize() -> forward*.  A runner derives from
+// it and puts its weight folding / upload and its workspace allocation into build().
+class ModelCore {
+ public:
+  virtual ~ModelCore() = default;
+  ParamStore& params() { return ps_; }
+  bool finalized() const { return finalized_; }
+  size_t device_bytes() const { return arena_.total(); }
+  // Once; a build() that throws leaves the model unfinalized (and what it allocated in the arena).
+  void finalize() {
+    SD_CHECK(!finalized_, kErrState, "finalize called twice");
+    build();
+    finalized_ = true;
+  }
+
+ protected:
+  virtual void build() = 0;
+  void require_finalized() const { SD_CHECK(finalized_, kErrState, "model not finalized"); }
+  float* ws(size_t n) { return static_cast<float*>(arena_.alloc(n * sizeof(float))); }
+
+  ParamStore ps_;
+  DeviceArena arena_;
+  bool finalized_ = false;
+};
+
 // Converts a packed fp32 weight to the device layout (bf16 bits when bf16).
 PackedW upload_packed(DeviceArena& arena, const std::vector<float>& w, int N, int Cin, int kh,
                       int kw, bool bf16);

@@ -3,8 +3,7 @@
 
 namespace sd {
 
-void ResEmbModel::finalize() {
-  SD_CHECK(!finalized_, kErrState, "finalize called twice");
+void ResEmbModel::build() {
   SD_CHECK(cfg_.feat_dim == 80, kErrInvalid, "ResNet34 (MI355X backend) supports feat_dim 80 only");
   const int E = cfg_.embed_dim, C2 = 2 * ResTrunk::kChannels;
   trunk_.load(ps_, arena_, "", cfg_.bf16);   // resnet_wespeaker.py:127-134
@@ -42,12 +41,11 @@ void ResEmbModel::finalize() {
   stats_ = static_cast<float*>(arena_.alloc((size_t)cfg_.max_batch * C2 * sizeof(float)));
   ea_ = static_cast<float*>(arena_.alloc((size_t)cfg_.max_batch * E * sizeof(float)));
   relu_ = static_cast<float*>(arena_.alloc((size_t)cfg_.max_batch * E * sizeof(float)));
-  finalized_ = true;
 }
 
 void ResEmbModel::forward(const float* fbank, int B, int Tf, float* emb, float* emb_a, float* time_out,
                           hipStream_t st) {
-  SD_CHECK(finalized_, kErrState, "model not finalized");
+  require_finalized();
   SD_CHECK(B >= 1 && B <= cfg_.max_batch, kErrInvalid, "batch exceeds max_batch");
   SD_CHECK(Tf >= 1 && Tf <= cfg_.max_frames, kErrInvalid, "fbank frames exceed max_frames");
   const int E = cfg_.embed_dim, C = ResTrunk::kChannels;

@@ -20,13 +20,9 @@ struct ResEmbConfig {
   bool bf16 = false;         // bf16 trunk (maps and conv operands); TSTP and the seg layers stay fp32
 };
 
-class ResEmbModel {
+class ResEmbModel : public ModelCore {
  public:
   explicit ResEmbModel(const ResEmbConfig& c) : cfg_(c) {}
-  ParamStore& params() { return ps_; }
-  void finalize();
-  bool finalized() const { return finalized_; }
-  size_t device_bytes() const { return arena_.total(); }
   // fbank (B, Tf, 80) -> emb (B, E): the last element of the reference's returned tuple (embed_b with
   // two_emb_layer, else embed_a; :176-183); emb_a (B, E, nullable): seg_1's output; time_out (B, T', 2560)
   // channel-last (nullable): forward(x, get_time_out=True) (:165-171).  T' == 1 (Tf <= 8) gives all-NaN embeddings
@@ -35,10 +31,8 @@ class ResEmbModel {
   void forward(const float* fbank, int B, int Tf, float* emb, float* emb_a, float* time_out, hipStream_t st);
 
  private:
+  void build() override;
   ResEmbConfig cfg_;
-  ParamStore ps_;
-  DeviceArena arena_;
-  bool finalized_ = false;
   ResTrunk trunk_;
   ConvL seg1_, seg2_;        // seg_2: W2 diag(s) and W2 h + b2 with seg_bn_1 = (s, h)
   float* stats_ = nullptr;   // (max_batch, 5120) [mean | std]

@@ -50,8 +50,7 @@ std::vector<SsndModel::DecL> SsndModel::load_decoder(const std::string& pre, int
   return out;
 }
 
-void SsndModel::finalize() {
-  SD_CHECK(!finalized_, kErrState, "finalize called twice");
+void SsndModel::build() {
   const SsndConfig& c = cfg_;
   SD_CHECK(c.feat_dim == 80, kErrInvalid, "CAM++ FCM head supports feat_dim 80 only");
   SD_CHECK(c.d_model % c.nhead == 0 && (c.d_model / c.nhead) % 4 == 0 && c.d_model / c.nhead <= 128, kErrInvalid,
@@ -149,7 +148,6 @@ void SsndModel::finalize() {
   xa_ = ws(Bm * N * D);
   h_ = ws(Bm * N * c.d_ff);
   fea_ = ws(Bm * T * D);
-  finalized_ = true;
 }
 
 void SsndModel::run_decoder(const std::vector<DecL>& Ls, float* xdec, const float* qaux, int d_aux, const float* fea,
@@ -195,7 +193,7 @@ void SsndModel::run_decoder(const std::vector<DecL>& Ls, float* xdec, const floa
 
 void SsndModel::decode(const float* enc, const float* x, const float* spk, int B, int T, float* vad, float* emb,
                        hipStream_t st) {
-  SD_CHECK(finalized_, kErrState, "model not finalized");
+  require_finalized();
   SD_CHECK(B >= 1 && B <= cfg_.max_batch, kErrInvalid, "blocks exceed max_batch");
   SD_CHECK(T == cfg_.vad_out_len, kErrShape, "frames per block must equal vad_out_len (rep_query_emb.expand)");
   SD_CHECK(T <= cfg_.max_seq_len, kErrShape, "frames per block exceed the positional table");
@@ -217,7 +215,7 @@ void SsndModel::decode(const float* enc, const float* x, const float* spk, int B
 }
 
 void SsndModel::infer(const float* feats, const float* spk, int B, int Tf, float* vad, float* emb, hipStream_t st) {
-  SD_CHECK(finalized_, kErrState, "model not finalized");
+  require_finalized();
   cam_.raise_if_set();   // an earlier call's cam_dense report
   SD_CHECK(B >= 1 && B <= cfg_.max_batch, kErrInvalid, "blocks exceed max_batch");
   SD_CHECK(Tf >= 8 && Tf <= cfg_.max_fbank_frames, kErrInvalid, "fbank frames exceed max_fbank_frames");

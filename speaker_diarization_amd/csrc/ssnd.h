@@ -39,13 +39,9 @@ struct SsndConfig {
   bool bf16 = false;          // extractor + encoder precision; the decoders are fp32
 };
 
-class SsndModel {
+class SsndModel : public ModelCore {
  public:
   explicit SsndModel(const SsndConfig& c) : cfg_(c) {}
-  ParamStore& params() { return ps_; }
-  void finalize();
-  bool finalized() const { return finalized_; }
-  size_t device_bytes() const { return arena_.total(); }
   // Label frames of a block of Tf fbank frames (CAM++ /2, speech_down_or_up /2).
   static int label_frames(int Tf) { return (CamTrunk::out_frames(Tf) - 1) / 2 + 1; }
   // SSNDModel.infer: feats (B, Tf, 80), speaker_embs (B, N, emb) -> vad (B, N, T), emb (B, N, emb).
@@ -55,6 +51,7 @@ class SsndModel {
               hipStream_t st);
 
  private:
+  void build() override;
   struct DecL {
     PackedW fq, fk, cq, ck, cv, co, sa_in, so, f1, f2;
     const float *fq_b, *fk_b, *cq_b, *ck_b, *cv_b, *co_b, *sa_in_b, *so_b, *f1_b, *f2_b;
@@ -63,12 +60,8 @@ class SsndModel {
   std::vector<DecL> load_decoder(const std::string& pre, int d_aux);
   void run_decoder(const std::vector<DecL>& L, float* xdec, const float* qaux, int d_aux, const float* fea,
                    int B, int T, hipStream_t st);
-  float* ws(size_t n) { return static_cast<float*>(arena_.alloc(n * sizeof(float))); }
 
   SsndConfig cfg_;
-  ParamStore ps_;
-  DeviceArena arena_;
-  bool finalized_ = false;
   CamTrunk cam_;
   ConvL out_proj_, down_;
   ConvL enc_in_;

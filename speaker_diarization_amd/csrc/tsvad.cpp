@@ -39,8 +39,7 @@ void TsvadModel::validate(const TsvadConfig& c) {
            "proj_layer: speaker_embed_dim and transformer_embed_dim must be multiples of 8");
 }
 
-void TsvadModel::finalize() {
-  SD_CHECK(!finalized_, kErrState, "finalize called twice");
+void TsvadModel::build() {
   validate(cfg_);
   const std::string se = "speech_encoder.";
   if (cfg_.variant == 2) {
@@ -156,7 +155,6 @@ void TsvadModel::finalize() {
   }
   ps_.require_all_used();
   alloc_workspace();
-  finalized_ = true;
 }
 
 TsvadModel::Geometry TsvadModel::geometry() const {
@@ -379,7 +377,7 @@ ConvGemmArgs TsvadModel::down_gemm(Tens x, int Bh, int Tf, float* out) const {
 void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int Tl, float* logits,
                          hipStream_t st, int forward_batch, int force) {
   SD_CHECK(forward_batch >= 0 && force >= 0 && force <= 3, kErrInvalid, "forward: bad forward_batch / force");
-  SD_CHECK(finalized_, kErrState, "model not finalized");
+  require_finalized();
   SD_CHECK(B >= 1 && B <= cfg_.max_batch, kErrInvalid, "batch exceeds max_batch");
   SD_CHECK(Tf >= 8 && Tf <= cfg_.max_fbank_frames, kErrInvalid, "fbank frames exceed max_fbank_frames");
   raise_if_set();

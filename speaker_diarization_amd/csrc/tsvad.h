@@ -28,11 +28,9 @@ struct TsvadConfig {
   int lstm_hidden = 256;
 };
 
-class TsvadModel {
+class TsvadModel : public ModelCore {
  public:
   explicit TsvadModel(const TsvadConfig& c) : cfg_(c) {}
-  ParamStore& params() { return ps_; }
-  void finalize();
   // Raises kErrInvalid for a configuration the runner does not build (sd_tsvad_create calls it): with
   // speaker_embed_dim * 2 != embed_dim the reference inserts proj_layer (model.py:212-217), built for variants 0 and 2.
   static void validate(const TsvadConfig& c);
@@ -43,8 +41,6 @@ class TsvadModel {
   // both BatchNorms for every window (a non-finite fbank), bit 1 backend_down's (a non-finite v0 embedding).
   void forward(const float* ref_speech, const float* target_speech, int B, int T_fb, int T_lab,
                float* logits, hipStream_t st, int forward_batch = 0, int force = 0);
-  bool finalized() const { return finalized_; }
-  size_t device_bytes() const { return arena_.total(); }
   // Diagnostics (graph-replay investigation): captures forward() once into a hipGraph on a capture stream
   // (the fork / join side stream included), then replays it `replays` times on st; `dot` (nullable) receives
   // hipGraphDebugDotPrint of the captured graph.
@@ -61,6 +57,7 @@ class TsvadModel {
   ~TsvadModel();
 
  private:
+  void build() override;
   ConvL conv_bn(const std::string& wname, const std::string& bn, const std::string& bias = "");
   LayerLoader loader() { return LayerLoader{ps_, arena_, cfg_.bf16}; }
   EncoderWork enc_work() const { return EncoderWork{Y_, QKV_, AO_, H_, partial_, cfg_.bf16}; }
@@ -87,13 +84,9 @@ class TsvadModel {
                        bool conformer_done);
   void transformer_backend(const float* ts, int T3, int B, int Tl, float* logits, hipStream_t st, const BnRelu& sd_bn,
                            const BnRelu& bd_bn);
-  float* ws(size_t n) { return static_cast<float*>(arena_.alloc(n * sizeof(float))); }
 
   TsvadConfig cfg_;
-  ParamStore ps_;
-  DeviceArena arena_;
   PinnedFlags lstm_err_;   // poll-timeout reports of the persistent LSTMs (lstm.hip), one slot each
-  bool finalized_ = false;
 
   // speech_encoder.* (get_time_out=True): the one trunk the variant uses, the other stays empty
   std::unique_ptr<CamTrunk> cam_;   // CAM++, variants 0 and 1

@@ -41,8 +41,7 @@ WenetLayerL TsvadStreamModel::load_layer(const std::string& p) {
   return L;
 }
 
-void TsvadStreamModel::finalize() {
-  SD_CHECK(!finalized_, kErrState, "finalize called twice");
+void TsvadStreamModel::build() {
   SD_CHECK(cfg_.speaker_embed_dim * 2 == cfg_.embed_dim, kErrInvalid,
            "transformer_embed_dim must be 2 * speaker_embed_dim (cat of ts and mix embeddings)");
   const std::string se = "embed.speech_encoder.";
@@ -83,7 +82,6 @@ void TsvadStreamModel::finalize() {
   T1_ = ws(rows * E);
   H_ = ws(rows * cfg_.ffn_dim);
   X2_ = ws(Tm * NS * E);
-  finalized_ = true;
 }
 
 void TsvadStreamModel::run_layers(const std::vector<WenetLayerL>& Ls, float* X, int S, int T, int chunk, int left,
@@ -116,7 +114,7 @@ void TsvadStreamModel::run_layers(const std::vector<WenetLayerL>& Ls, float* X, 
 
 void TsvadStreamModel::forward(const float* feats, const float* ts, int B, int T_lab, int chunk, int left,
                                float* logits, hipStream_t st) {
-  SD_CHECK(finalized_, kErrState, "model not finalized");
+  require_finalized();
   cam_.raise_if_set();   // an earlier call's cam_dense report
   SD_CHECK(B >= 1 && B <= cfg_.max_windows, kErrInvalid, "windows per call exceed max_windows");
   SD_CHECK(T_lab >= 1 && T_lab <= cfg_.max_labels, kErrInvalid, "label frames exceed max_labels");

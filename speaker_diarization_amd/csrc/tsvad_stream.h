@@ -32,13 +32,9 @@ struct WenetLayerL {           // transformer_chunk_streaming.TransformerEncoder
   const float *n1g = nullptr, *n1b = nullptr, *n2g = nullptr, *n2b = nullptr;
 };
 
-class TsvadStreamModel {
+class TsvadStreamModel : public ModelCore {
  public:
   explicit TsvadStreamModel(const TsvadStreamConfig& c) : cfg_(c) {}
-  ParamStore& params() { return ps_; }
-  void finalize();
-  bool finalized() const { return finalized_; }
-  size_t device_bytes() const { return arena_.total(); }
   // B independent windows: feats (B, 4 * T_lab, 80) fbank (padded to 4 x labels,
   // model.py:614-618); ts (B, NS, 192); chunk = decoding_chunk_size (label frames),
   // left = num_decoding_left_chunks; logits (B, NS, T_lab) pre-sigmoid.
@@ -46,14 +42,11 @@ class TsvadStreamModel {
                hipStream_t st);
 
  private:
+  void build() override;
   WenetLayerL load_layer(const std::string& prefix);
   void run_layers(const std::vector<WenetLayerL>& L, float* X, int S, int T, int chunk, int left, hipStream_t st);
-  float* ws(size_t n) { return static_cast<float*>(arena_.alloc(n * sizeof(float))); }
 
   TsvadStreamConfig cfg_;
-  ParamStore ps_;
-  DeviceArena arena_;
-  bool finalized_ = false;
   CamTrunk cam_;               // embed.speech_encoder.*
   ConvL down_;                 // embed.speech_down_or_up (Conv1d k5 s2 + BatchNorm1D + ReLU)
   std::vector<WenetLayerL> single_, multi_;

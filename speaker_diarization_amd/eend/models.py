@@ -7,31 +7,27 @@ sigmoid) runs in libsdiar as variant 3 of the EDA runner.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from .. import _lib
 from ..weights import EDAConfig
 
 
-class TransformerModel:
+class TransformerModel(_lib.Handle):
+    kind = "eda"
+
     def __init__(self, n_speakers, in_size, n_heads, n_units, n_layers, dim_feedforward=2048, dropout=0.5,
                  has_pos=False, *, device=None, precision: str = "fp32", max_seqs: int = 8,
                  max_frames: int = 2000):
         if has_pos:
             raise NotImplementedError("has_pos=True is not on the inference path")
-        if precision not in ("bf16", "fp32", "bf16x3"):
-            raise ValueError(f"precision must be bf16, fp32 or bf16x3, got {precision}")
+        _lib.precision_code(precision)
         self.cfg = EDAConfig(n_speakers=n_speakers, in_size=in_size, n_heads=n_heads, n_units=n_units,
                              n_layers=n_layers, dim_feedforward=dim_feedforward)
         self.n_speakers = n_speakers
         self.precision = precision
         self.max_seqs, self.max_frames = max_seqs, max_frames
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise ValueError("EEND (MI355X backend) runs on a HIP device only")
-        self._h = None
+        self.device = _lib.hip_device(device, "EEND")
 
     def load_state_dict(self, state_dict, strict: bool = True):
         if not strict:
@@ -40,30 +36,16 @@ class TransformerModel:
         conf = _lib.EdaConfig(variant=3, in_size=c.in_size, n_units=c.n_units, n_heads=c.n_heads,
                               n_layers=c.n_layers, dim_feedforward=c.dim_feedforward, max_seqs=self.max_seqs,
                               max_frames=self.max_frames, max_n_speakers=2,
-                              precision={"fp32": 0, "bf16": 1, "bf16x3": 2}[self.precision], n_speakers=c.n_speakers)
-        h = _lib.create_handle("eda", conf, _lib.host_state(state_dict))
-        self._release()
-        self._h = h
-        self.in_ld = _lib.load().sd_eda_input_stride(h)
+                              precision=_lib.PRECISION[self.precision], n_speakers=c.n_speakers)
+        self._adopt(_lib.create_handle("eda", conf, state_dict))
+        self.in_ld = _lib.load().sd_eda_input_stride(self._h)
         return self
-
-    def _release(self):
-        if self._h is not None:
-            _lib.load().sd_eda_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     def eval(self):
         return self
 
     def to(self, device):
-        if torch.device(device).type != "cuda":
-            raise ValueError("EEND (MI355X backend) runs on a HIP device only")
+        _lib.hip_device(device, "EEND")
         return self
 
     def __call__(self, src, has_mask=False, activation=None):

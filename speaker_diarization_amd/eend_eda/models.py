@@ -16,7 +16,6 @@ seeded script draws the same permutations.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List, Optional
 
 import numpy as np
@@ -57,25 +56,22 @@ def _replay_torchaudio_conformer(d, nh, ffn, layers, k):
         nn.LayerNorm(d)                                             # final_layer_norm
 
 
-class _EdaBase:
-    """Shared handle management for the two reference classes."""
+class _EdaBase(_lib.Handle):
+    """What the two reference classes share; the handle is built when the weights arrive (and again when infer()
+    asks for another number of attractors)."""
+    kind = "eda"
 
     def __init__(self, cfg: EDAConfig, dropout: float, device=None, precision: str = "fp32",
                  max_seqs: int = 8, max_frames: int = 2000):
-        import torch
         cfg.variant  # validates model/encoder type like the reference constructor
-        if precision not in ("bf16", "fp32", "bf16x3"):
-            raise ValueError(f"precision must be bf16, fp32 or bf16x3, got {precision}")
+        _lib.precision_code(precision)
         self.cfg = cfg
         self.precision = precision
         self.max_seqs = max_seqs
         self.max_frames = max_frames
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise ValueError("EEND-EDA (MI355X backend) runs on a HIP device only")
+        self.device = _lib.hip_device(device, "EEND-EDA")
         _replay_construction_rng(cfg, dropout)
         self._state = None
-        self._h = None
         self._n_att = None
 
     # ------------------------------------------------------------------ handle
@@ -84,40 +80,17 @@ class _EdaBase:
         conf = _lib.EdaConfig(variant=c.variant, in_size=c.in_size, n_units=c.n_units, n_heads=c.n_heads,
                               n_layers=c.n_layers, dim_feedforward=c.dim_feedforward, max_seqs=self.max_seqs,
                               max_frames=self.max_frames, max_n_speakers=max_n_speakers,
-                              precision={"fp32": 0, "bf16": 1, "bf16x3": 2}[self.precision])
-        h = ctypes.c_void_p()
-        _lib.call("sd_eda_create", ctypes.byref(conf), ctypes.byref(h))
-        try:
-            for k, v in self._state.items():
-                a = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
-                shape = (ctypes.c_int64 * max(a.ndim, 1))(*a.shape)
-                _lib.call("sd_eda_set_param", h, k.encode(), a.ctypes.data_as(ctypes.c_void_p), shape, a.ndim)
-            _lib.call("sd_eda_finalize", h)
-        except Exception:
-            _lib.load().sd_eda_destroy(h)
-            raise
-        self._release()
-        self._h, self._n_att = h, max_n_speakers
-        self.in_ld = _lib.load().sd_eda_input_stride(h)
-
-    def _release(self):
-        if self._h is not None:
-            _lib.load().sd_eda_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+                              precision=_lib.PRECISION[self.precision])
+        self._adopt(_lib.create_handle("eda", conf, self._state))
+        self._n_att = max_n_speakers
+        self.in_ld = _lib.load().sd_eda_input_stride(self._h)
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Same keys as the reference module (torch.load of the model file,
         infer_eda.py:88).  Missing/unexpected keys raise RuntimeError."""
         if not strict:
             raise ValueError("strict=False is not supported by the MI355X backend")
-        self._state = {k: (v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v))
-                       for k, v in state_dict.items()}
+        self._state = _lib.host_state(state_dict)
         self._build(15)
         return self
 
@@ -125,13 +98,11 @@ class _EdaBase:
         return self
 
     def to(self, device):
-        import torch
-        if torch.device(device).type != "cuda":
-            raise ValueError("EEND-EDA (MI355X backend) runs on a HIP device only")
+        _lib.hip_device(device, "EEND-EDA")
         return self
 
     def device_bytes(self) -> int:
-        return int(_lib.load().sd_eda_device_bytes(self._h)) if self._h is not None else 0
+        return self._device_bytes()
 
     # ------------------------------------------------------------------ forward
     def forward_infer(self, feats, lengths: List[int], perms, max_n_speakers: int = 15,

@@ -22,13 +22,14 @@ from .. import _lib
 from ..weights import FSEENDConfig, unwrap_checkpoint
 
 
-class OnlineTransformerDADiarization:
+class OnlineTransformerDADiarization(_lib.Handle):
+    kind = "fseend"
+
     def __init__(self, n_speakers, in_size, n_units, n_heads, enc_n_layers, dec_n_layers, dropout, has_mask,
                  max_seqlen, dec_dim_feedforward, conv_delay=9, mask_delay=0, decom_kernel_size=64, *,
                  device=None, precision: str = "fp32", max_seqs: int = 1, max_frames: int = None,
                  max_nspks: int = 6):
-        if precision not in ("bf16", "fp32", "bf16x3"):
-            raise ValueError(f"precision must be bf16, fp32 or bf16x3, got {precision}")
+        _lib.precision_code(precision)
         self.cfg = FSEENDConfig(n_speakers=n_speakers, in_size=in_size, n_units=n_units, n_heads=n_heads,
                                 enc_n_layers=enc_n_layers, dec_n_layers=dec_n_layers, dropout=dropout,
                                 has_mask=has_mask, max_seqlen=max_seqlen, dec_dim_feedforward=dec_dim_feedforward,
@@ -38,10 +39,7 @@ class OnlineTransformerDADiarization:
         self.max_seqs = max_seqs
         self.max_frames = max_frames or max_seqlen
         self.max_nspks = max_nspks
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise ValueError("FS-EEND (MI355X backend) runs on a HIP device only")
-        self._h = None
+        self.device = _lib.hip_device(device, "FS-EEND")
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Accepts the module state_dict or the Lightning checkpoint layout
@@ -54,34 +52,20 @@ class OnlineTransformerDADiarization:
                                  dec_dim_feedforward=c.dec_dim_feedforward, conv_delay=c.conv_delay,
                                  mask_delay=c.mask_delay, has_mask=int(bool(c.has_mask)), max_seqs=self.max_seqs,
                                  max_frames=self.max_frames, max_nspks=self.max_nspks,
-                                 precision={"fp32": 0, "bf16": 1, "bf16x3": 2}[self.precision])
-        h = _lib.create_handle("fseend", conf, _lib.host_state(unwrap_checkpoint(state_dict)))
-        self._release()
-        self._h = h
-        self.in_ld = _lib.load().sd_fseend_input_stride(h)
+                                 precision=_lib.PRECISION[self.precision])
+        self._adopt(_lib.create_handle("fseend", conf, unwrap_checkpoint(state_dict)))
+        self.in_ld = _lib.load().sd_fseend_input_stride(self._h)
         return self
-
-    def _release(self):
-        if self._h is not None:
-            _lib.load().sd_fseend_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     def eval(self):
         return self
 
     def to(self, device):
-        if torch.device(device).type != "cuda":
-            raise ValueError("FS-EEND (MI355X backend) runs on a HIP device only")
+        _lib.hip_device(device, "FS-EEND")
         return self
 
     def device_bytes(self) -> int:
-        return int(_lib.load().sd_fseend_device_bytes(self._h)) if self._h is not None else 0
+        return self._device_bytes()
 
     def test_device(self, feats, ilens: List[int], max_nspks: int = 6, want_emb: bool = True,
                     want_attractors: bool = True):

@@ -10,68 +10,51 @@ the reference's host-side bookkeeping (speaker buffer of online_infer).
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
 from .. import _lib
 from ..weights import SSNDConfig, unwrap_checkpoint
 
 
-class SSNDModel:
+class SSNDModel(_lib.Handle):
+    kind = "ssnd"
+
     def __init__(self, speaker_pretrain_model_path=None, extractor_model_type="CAM++_wo_gsp", feat_dim=80,
                  emb_dim=256, q_det_aux_dim=256, q_rep_aux_dim=256, d_model=256, nhead=8, d_ff=512,
                  num_layers=4, max_speakers=4, vad_out_len=100, pos_emb_dim=256, max_seq_len=1000,
                  n_all_speakers=1000, training=False, device=None, precision: str = "fp32", max_batch: int = 8,
                  **_unused_training_args):
-        import torch
         if extractor_model_type != "CAM++_wo_gsp":
             raise ValueError(f"the MI355X SSND backend builds extractor CAM++_wo_gsp, got {extractor_model_type}")
-        if precision not in ("bf16", "fp32"):
-            raise ValueError(f"precision must be bf16 or fp32, got {precision}")
+        code = _lib.precision_code(precision, ("bf16", "fp32"))
         self.cfg = SSNDConfig(feat_dim=feat_dim, emb_dim=emb_dim, q_det_aux_dim=q_det_aux_dim,
                               q_rep_aux_dim=q_rep_aux_dim, d_model=d_model, nhead=nhead, d_ff=d_ff,
                               num_layers=num_layers, max_speakers=max_speakers, vad_out_len=vad_out_len,
                               pos_emb_dim=pos_emb_dim, max_seq_len=max_seq_len, n_all_speakers=n_all_speakers)
-        self.device = torch.device(device) if device is not None and str(device) != "cpu" else \
-            torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise ValueError("SSNDModel (MI355X backend) runs on a HIP device only")
+        # the reference's device="cpu" default means "where the model runs": here, the current HIP device
+        self.device = _lib.hip_device(None if str(device) == "cpu" else device, "SSNDModel")
         self.precision, self.max_batch = precision, max_batch
         self.max_speakers, self.emb_dim, self.d_model = max_speakers, emb_dim, d_model
         # a block of vad_out_len label frames = 4 * vad_out_len fbank frames (CAM++ /2, down conv /2)
         self.block_frames = 4 * vad_out_len
         c = self.cfg
-        conf = _lib.SsndConfig(max_batch=max_batch, max_fbank_frames=self.block_frames, max_speakers=max_speakers,
-                               feat_dim=feat_dim, emb_dim=emb_dim, q_det_aux_dim=q_det_aux_dim,
-                               q_rep_aux_dim=q_rep_aux_dim, d_model=d_model, nhead=nhead, d_ff=d_ff,
-                               num_layers=num_layers, vad_out_len=vad_out_len, pos_emb_dim=pos_emb_dim,
-                               max_seq_len=max_seq_len, n_all_speakers=n_all_speakers,
-                               conformer_kernel=c.conformer_kernel, precision=1 if precision == "bf16" else 0)
-        h = ctypes.c_void_p()
-        _lib.call("sd_ssnd_create", ctypes.byref(conf), ctypes.byref(h))
-        self._h = h
+        self._create(_lib.SsndConfig(max_batch=max_batch, max_fbank_frames=self.block_frames,
+                                     max_speakers=max_speakers, feat_dim=feat_dim, emb_dim=emb_dim,
+                                     q_det_aux_dim=q_det_aux_dim, q_rep_aux_dim=q_rep_aux_dim, d_model=d_model,
+                                     nhead=nhead, d_ff=d_ff, num_layers=num_layers, vad_out_len=vad_out_len,
+                                     pos_emb_dim=pos_emb_dim, max_seq_len=max_seq_len, n_all_speakers=n_all_speakers,
+                                     conformer_kernel=c.conformer_kernel, precision=code))
         self.E_all = self.e_pse = self.e_non = None
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _lib._lib is not None:
-            _lib.load().sd_ssnd_destroy(h)
-            self._h = None
 
     def load_state_dict(self, state_dict, strict: bool = True):
         import torch
         if not strict:
             raise ValueError("the MI355X backend only supports strict=True loading")
-        state_dict = unwrap_checkpoint(state_dict, kind="ssnd")
-        with torch.device("cpu"):
-            for k, v in state_dict.items():
-                t = torch.as_tensor(np.asarray(v.cpu() if hasattr(v, "cpu") else v)).to(torch.float32).contiguous()
-                shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
-                _lib.call("sd_ssnd_set_param", self._h, k.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim())
-                if k in ("E_all", "e_pse", "e_non"):
-                    setattr(self, k, t.to(self.device))
-        _lib.call("sd_ssnd_finalize", self._h)
+        state = _lib.host_state(unwrap_checkpoint(state_dict, kind="ssnd"))
+        for k in ("E_all", "e_pse", "e_non"):      # the host logic of offline_diarization / online_infer reads them
+            if k in state:
+                setattr(self, k, torch.from_numpy(np.ascontiguousarray(state[k])).to(self.device))
+        self._load(state)
         return self
 
     def eval(self):
@@ -79,7 +62,7 @@ class SSNDModel:
 
     @property
     def device_bytes(self) -> int:
-        return int(_lib.load().sd_ssnd_device_bytes(self._h))
+        return self._device_bytes()
 
     # ------------------------------------------------------------------ inference
     def infer(self, feats, speaker_embs):

@@ -20,7 +20,6 @@ Drop-in for the step before TS-VAD inference:
 """
 from __future__ import annotations
 
-import ctypes
 import os
 
 import numpy as np
@@ -32,43 +31,25 @@ from ..weights import unwrap_checkpoint
 POVEY = 1
 
 
-class CAMPPlus:
+class CAMPPlus(_lib.Handle):
+    kind = "campp"
+
     def __init__(self, feat_dim: int = 80, embedding_size: int = 192, growth_rate: int = 32, bn_size: int = 4,
                  init_channels: int = 128, config_str: str = "batchnorm-relu", memory_efficient: bool = True,
                  *, device=None, precision: str = "bf16", max_batch: int = 96, max_frames: int = 598):
-        import torch
         if (growth_rate, bn_size, init_channels, config_str) != (32, 4, 128, "batchnorm-relu"):
             raise ValueError("the MI355X CAM++ supports the shipped CAMPPlus topology only")
-        if precision not in ("bf16", "fp32"):
-            raise ValueError(f"precision must be bf16 or fp32, got {precision}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise ValueError("CAMPPlus (MI355X backend) runs on a HIP device only")
+        code = _lib.precision_code(precision, ("bf16", "fp32"))
+        self.device = _lib.hip_device(device, "CAMPPlus")
         self.feat_dim, self.embedding_size = feat_dim, embedding_size
         self.precision, self.max_batch, self.max_frames = precision, max_batch, max_frames
-        conf = _lib.CamppConfig(feat_dim=feat_dim, embedding_size=embedding_size, max_batch=max_batch,
-                                max_frames=max_frames, precision=1 if precision == "bf16" else 0)
-        h = ctypes.c_void_p()
-        _lib.call("sd_campp_create", ctypes.byref(conf), ctypes.byref(h))
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _lib._lib is not None:
-            _lib.load().sd_campp_destroy(h)
-            self._h = None
+        self._create(_lib.CamppConfig(feat_dim=feat_dim, embedding_size=embedding_size, max_batch=max_batch,
+                                      max_frames=max_frames, precision=code))
 
     def load_state_dict(self, state_dict, strict: bool = True):
-        import torch
         if not strict:
             raise ValueError("the MI355X backend only supports strict=True loading")
-        state_dict = unwrap_checkpoint(state_dict, kind="campp")
-        with torch.device("cpu"):
-            for k, v in state_dict.items():
-                t = torch.as_tensor(np.asarray(v.cpu() if hasattr(v, "cpu") else v)).to(torch.float32).contiguous()
-                shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
-                _lib.call("sd_campp_set_param", self._h, k.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim())
-        _lib.call("sd_campp_finalize", self._h)
+        self._load(unwrap_checkpoint(state_dict, kind="campp"))
         return self
 
     def eval(self):
@@ -82,7 +63,7 @@ class CAMPPlus:
 
     @property
     def device_bytes(self) -> int:
-        return int(_lib.load().sd_campp_device_bytes(self._h))
+        return self._device_bytes()
 
     def forward(self, x, get_time_out: bool = False, out=None):
         """x (B, T, 80) -> (B, E), or (B, 512, (T-1)//2+1) with get_time_out (cam_pplus_wespeaker.py:388-399)."""
@@ -108,53 +89,34 @@ class CAMPPlus:
     __call__ = forward
 
 
-class ResNet34:
+class ResNet34(_lib.Handle):
     """egs/alimeeting/ts_vad2/resnet_wespeaker.py:108-183, 198-208 with speech_encoder=False: the WeSpeaker
     ResNet34 embedding extractor (TSTP pooling + seg_1 [+ seg_bn_1 + seg_2]) run by libsdiar (`sd_resnet34_*`).
     Same constructor arguments and standalone state_dict keys; forward(x) -> (embed_a, embed_b), or
     (tensor(0.0), embed_a) without two_emb_layer; forward(x, get_time_out=True) -> (B, 2560, T').  The encoder-only
     form (speech_encoder=True) is TSVADModel's speech encoder, not this class."""
+    kind = "resnet34"
 
     def __init__(self, feat_dim: int, embed_dim: int, pooling_func: str = "TSTP", two_emb_layer: bool = True,
                  speech_encoder: bool = False, *, device=None, precision: str = "bf16", max_batch: int = 96,
                  max_frames: int = 598):
-        import torch
         if pooling_func != "TSTP":
             raise ValueError(f"the MI355X ResNet34 builds TSTP pooling only, got {pooling_func}")
         if speech_encoder:
             raise ValueError("speech_encoder=True (no pooling head) is TSVADModel's resnet34_wespeaker speech encoder")
-        if precision not in ("bf16", "fp32"):
-            raise ValueError(f"precision must be bf16 or fp32, got {precision}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise ValueError("ResNet34 (MI355X backend) runs on a HIP device only")
+        code = _lib.precision_code(precision, ("bf16", "fp32"))
+        self.device = _lib.hip_device(device, "ResNet34")
         self.feat_dim, self.embed_dim, self.two_emb_layer = feat_dim, embed_dim, bool(two_emb_layer)
         self.embedding_size = embed_dim      # what extract_embed sizes its output with
         self.precision, self.max_batch, self.max_frames = precision, max_batch, max_frames
-        conf = _lib.Resnet34Config(feat_dim=feat_dim, embed_dim=embed_dim, two_emb_layer=int(self.two_emb_layer),
-                                   max_batch=max_batch, max_frames=max_frames,
-                                   precision=1 if precision == "bf16" else 0)
-        h = ctypes.c_void_p()
-        _lib.call("sd_resnet34_create", ctypes.byref(conf), ctypes.byref(h))
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _lib._lib is not None:
-            _lib.load().sd_resnet34_destroy(h)
-            self._h = None
+        self._create(_lib.Resnet34Config(feat_dim=feat_dim, embed_dim=embed_dim,
+                                         two_emb_layer=int(self.two_emb_layer), max_batch=max_batch,
+                                         max_frames=max_frames, precision=code))
 
     def load_state_dict(self, state_dict, strict: bool = True):
-        import torch
         if not strict:
             raise ValueError("the MI355X backend only supports strict=True loading")
-        state_dict = unwrap_checkpoint(state_dict, kind="resnet34")
-        with torch.device("cpu"):
-            for k, v in state_dict.items():
-                t = torch.as_tensor(np.asarray(v.cpu() if hasattr(v, "cpu") else v)).to(torch.float32).contiguous()
-                shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
-                _lib.call("sd_resnet34_set_param", self._h, k.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim())
-        _lib.call("sd_resnet34_finalize", self._h)
+        self._load(unwrap_checkpoint(state_dict, kind="resnet34"))
         return self
 
     def eval(self):
@@ -168,7 +130,7 @@ class ResNet34:
 
     @property
     def device_bytes(self) -> int:
-        return int(_lib.load().sd_resnet34_device_bytes(self._h))
+        return self._device_bytes()
 
     @staticmethod
     def out_frames(T: int) -> int:

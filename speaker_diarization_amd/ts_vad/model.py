@@ -8,7 +8,6 @@ state_dict tensors across the C ABI and wraps device pointers.
 """
 from __future__ import annotations
 
-import ctypes
 from collections import defaultdict
 
 import numpy as np
@@ -22,59 +21,36 @@ def fbank_frames(rs_len: int, sample_rate: int = 16000) -> int:
     return 1 + (n - 400) // 160
 
 
-class TSVADModel:
+class TSVADModel(_lib.Handle):
+    kind = "tsvad"
+
     def __init__(self, cfg: TSVADConfig = None, task_cfg=None, device=None, precision: str = "bf16",
                  max_batch: int = 64):
-        import torch
         self.cfg = cfg or TSVADConfig()
         if task_cfg is not None:   # mirror of TSVADDataConfig fields the model reads
             for k in ("rs_len", "max_num_speaker", "label_rate", "sample_rate"):
                 if hasattr(task_cfg, k):
                     setattr(self.cfg, k, getattr(task_cfg, k))
         assert self.cfg.label_rate == 25, f"self.label_rate is {self.cfg.label_rate} not support!"
-        if precision not in ("bf16", "fp32", "bf16x3"):
-            raise ValueError(f"precision must be bf16, fp32 or bf16x3, got {precision}")
+        _lib.precision_code(precision)
         self.precision = precision
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise ValueError("TSVADModel (MI355X backend) runs on a HIP device only")
+        self.device = _lib.hip_device(device, "TSVADModel")
         self.max_batch = max_batch
         self.max_num_speaker = self.cfg.max_num_speaker
         self.max_fbank = fbank_frames(self.cfg.rs_len, self.cfg.sample_rate)
-        self._h = None
-        self._create()
-
-    # ------------------------------------------------------------------ handle
-    def _create(self):
         c = self.cfg
-        conf = _lib.TsvadConfig(
+        self._create(_lib.TsvadConfig(
             variant=c.variant, max_num_speaker=c.max_num_speaker, rs_len=c.rs_len, max_batch=self.max_batch,
-            max_fbank_frames=self.max_fbank, precision={"fp32": 0, "bf16": 1, "bf16x3": 2}[self.precision],
+            max_fbank_frames=self.max_fbank, precision=_lib.PRECISION[precision],
             num_transformer_layer=c.num_transformer_layer, num_attention_head=c.num_attention_head,
             transformer_embed_dim=c.transformer_embed_dim,
-            transformer_ffn_embed_dim=c.transformer_ffn_embed_dim, speaker_embed_dim=c.speaker_embed_dim)
-        h = ctypes.c_void_p()
-        _lib.call("sd_tsvad_create", ctypes.byref(conf), ctypes.byref(h))
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _lib._lib is not None:
-            _lib.load().sd_tsvad_destroy(h)
-            self._h = None
+            transformer_ffn_embed_dim=c.transformer_ffn_embed_dim, speaker_embed_dim=c.speaker_embed_dim))
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Strict load (missing/unexpected keys raise RuntimeError like torch)."""
-        import torch
         if not strict:
             raise ValueError("the MI355X backend only supports strict=True loading")
-        state_dict = unwrap_checkpoint(state_dict)
-        with torch.device("cpu"):
-            for k, v in state_dict.items():
-                t = torch.as_tensor(np.asarray(v.cpu() if hasattr(v, "cpu") else v)).to(torch.float32).contiguous()
-                shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
-                _lib.call("sd_tsvad_set_param", self._h, k.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim())
-        _lib.call("sd_tsvad_finalize", self._h)
+        self._load(unwrap_checkpoint(state_dict))
         return self
 
     def eval(self):
@@ -88,7 +64,7 @@ class TSVADModel:
 
     @property
     def device_bytes(self) -> int:
-        return int(_lib.load().sd_tsvad_device_bytes(self._h))
+        return self._device_bytes()
 
     # ------------------------------------------------------------------ forward
     def forward(self, ref_speech, target_speech, labels, num_updates: int = 0, out=None, check: bool = True,

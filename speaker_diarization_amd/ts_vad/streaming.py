@@ -12,55 +12,32 @@ loop does one window at a time, infer_debug batch 1).
 """
 from __future__ import annotations
 
-import ctypes
-
-import numpy as np
-
 from .. import _lib
 from ..weights import TSVADStreamingConfig, unwrap_checkpoint
 
 
-class TSVADStreamingModel:
+class TSVADStreamingModel(_lib.Handle):
+    kind = "tsvad_stream"
+
     def __init__(self, cfg: TSVADStreamingConfig = None, device=None, precision: str = "bf16",
                  max_labels: int = 400, max_windows: int = 1):
-        import torch
         self.cfg = cfg or TSVADStreamingConfig()
-        if precision not in ("bf16", "fp32"):
-            raise ValueError(f"precision must be bf16 or fp32, got {precision}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise ValueError("TSVADStreamingModel (MI355X backend) runs on a HIP device only")
+        code = _lib.precision_code(precision, ("bf16", "fp32"))
+        self.device = _lib.hip_device(device, "TSVADStreamingModel")
         self.precision, self.max_labels, self.max_windows = precision, max_labels, max_windows
         self.max_num_speaker = self.cfg.max_num_speaker
         self.subsampling_rate = 4   # Subsampling4 (model.py:1318)
         c = self.cfg
-        conf = _lib.TsvadStreamConfig(
-            max_num_speaker=c.max_num_speaker, max_labels=max_labels, precision=1 if precision == "bf16" else 0,
+        self._create(_lib.TsvadStreamConfig(
+            max_num_speaker=c.max_num_speaker, max_labels=max_labels, precision=code,
             num_transformer_layer=c.num_transformer_layer, num_attention_head=c.num_attention_head,
             transformer_embed_dim=c.transformer_embed_dim, transformer_ffn_embed_dim=c.transformer_ffn_embed_dim,
-            speaker_embed_dim=c.speaker_embed_dim, max_windows=max_windows)
-        h = ctypes.c_void_p()
-        _lib.call("sd_tsvad_stream_create", ctypes.byref(conf), ctypes.byref(h))
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _lib._lib is not None:
-            _lib.load().sd_tsvad_stream_destroy(h)
-            self._h = None
+            speaker_embed_dim=c.speaker_embed_dim, max_windows=max_windows))
 
     def load_state_dict(self, state_dict, strict: bool = True):
-        import torch
         if not strict:
             raise ValueError("the MI355X backend only supports strict=True loading")
-        state_dict = unwrap_checkpoint(state_dict)
-        with torch.device("cpu"):
-            for k, v in state_dict.items():
-                t = torch.as_tensor(np.asarray(v.cpu() if hasattr(v, "cpu") else v)).to(torch.float32).contiguous()
-                shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
-                _lib.call("sd_tsvad_stream_set_param", self._h, k.encode(), ctypes.c_void_p(t.data_ptr()), shape,
-                          t.dim())
-        _lib.call("sd_tsvad_stream_finalize", self._h)
+        self._load(unwrap_checkpoint(state_dict))
         return self
 
     def eval(self):
@@ -68,7 +45,7 @@ class TSVADStreamingModel:
 
     @property
     def device_bytes(self) -> int:
-        return int(_lib.load().sd_tsvad_stream_device_bytes(self._h))
+        return self._device_bytes()
 
     def forward_chunk_by_chunk(self, xs, target_speech, labels, decoding_chunk_size: int = 0,
                                num_decoding_left_chunks: int = -1, out=None):

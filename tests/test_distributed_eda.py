@@ -60,10 +60,13 @@ def _fake_chunk_activities(model, feats, args, perms, c0=0, c1=None):
 
 def _run(world, rank, variant, num_speakers):
     from speaker_diarization_amd.eend_eda import infer as inf
-    inf.recording_features = _fake_feats
-    inf.chunk_activities = _fake_chunk_activities
+    real = inf.recording_features, inf.chunk_activities
+    inf.recording_features, inf.chunk_activities = _fake_feats, _fake_chunk_activities
     torch.manual_seed(777)
-    return inf.infer_recording(_FakeModel(variant), None, inf.EdaInferArgs(num_speakers=num_speakers))
+    try:
+        return inf.infer_recording(_FakeModel(variant), None, inf.EdaInferArgs(num_speakers=num_speakers))
+    finally:      # the single-rank reference runs in the pytest process: the GPU tests of a later file need the real ones
+        inf.recording_features, inf.chunk_activities = real
 
 
 def _worker(rank, world, port, outdir, variant, num_speakers):
