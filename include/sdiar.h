@@ -63,7 +63,11 @@ typedef struct {
   int variant;                    /* 0: speech_encoder_type "CAM++", single/multi_backend "transformer"
                                      1: "CAM++_ots_vad", "conformer_ots_vad", "lstm_ots_vad", ots_vad_style "v1"
                                      2: "resnet34_wespeaker" (ResNet34 trunk + SpeechFeatUpsample2 transposed-conv
-                                        upsampler, model.py:114-134, 584-606), single/multi_backend "transformer" */
+                                        upsampler, model.py:114-134, 584-606), single/multi_backend "transformer"
+                                     3: "ecapa_channel_1024_wespeaker" (ECAPA_TDNN_GLOB_c1024 trunk + Conv1d(1536 ->
+                                        speaker_embed_dim, k5, stride 4, pad 2), model.py:631-654), single/multi_backend
+                                        "transformer"; any window of 1 .. max_fbank_frames frames runs, T fbank frames
+                                        give (T - 1) / 4 + 1 mix frames */
   int max_num_speaker;            /* TSVADDataConfig.max_num_speaker (4)                     */
   int rs_len;                     /* seconds; PositionalEncoding max_len = rs_len * 25       */
   int max_batch;                  /* workspace sizing                                        */
@@ -76,7 +80,7 @@ typedef struct {
   int speaker_embed_dim;          /* 192; any other multiple of 8 with 2 * speaker_embed_dim != transformer_embed_dim
                                      (256 for ResNet34 embeddings, run_ts_vad2.sh:3684) adds proj_layer =
                                      nn.Linear(2 * speaker_embed_dim, transformer_embed_dim) (model.py:212-217,
-                                     873-874), variants 0 and 2 only: the reference's ots_vad forward never applies
+                                     873-874), variants 0, 2 and 3 only: the reference's ots_vad forward never applies
                                      it (model.py:730-731), so variant 1 is refused at create */
 } sd_tsvad_config;
 
@@ -213,6 +217,39 @@ int sd_resnet34_forward(sd_resnet34* h, const float* feats, int B, int T, float*
                         void* stream);
 int64_t sd_resnet34_device_bytes(const sd_resnet34* h);
 int sd_resnet34_destroy(sd_resnet34* h);
+
+/* ------------------------------------------------------------------ ECAPA-TDNN embeddings
+ * Replaces ECAPA_TDNN_GLOB_c1024(feat_dim=80, embed_dim=192, pooling_func="ASTP")
+ * (egs/alimeeting/ts_vad2/ecapa_tdnn_wespeaker.py:161-271, pooling_layers_wespeaker.py:91-144) as the target-speaker
+ * embedding extractor of generate_chunk_speaker_embedding_from_ecapa_tdnn_for_diarization.py:
+ *   construction  :111-112
+ *   forward(x)    :128-131 / ecapa_tdnn_wespeaker.py:227-254
+ * State-dict keys are the standalone module's (layer1.*, layer2..4.se_res2block.*, conv.*, pool.linear1/2.*, bn.*,
+ * linear.*); emb_bn is off, so a bn2.* key is unexpected. */
+typedef struct sd_ecapa sd_ecapa;
+
+typedef struct {
+  int channels;        /* 1024 only (ECAPA_TDNN_GLOB_c1024; the c512 models are not built) */
+  int embed_dim;       /* 192 (a multiple of 4) */
+  int max_batch;       /* workspace: chunks per forward (extract_embed batch_size 96)      */
+  int max_frames;      /* workspace: fbank frames per chunk (598 for 6 s)                  */
+  int precision;       /* 0: fp32 (exact-f32 MFMA), 1: bf16 trunk (ASTP, bn and linear stay fp32) */
+} sd_ecapa_config;
+
+/* ecapa_tdnn_wespeaker.py:163-225, 264-271; channels != 1024 gives SD_ERR_INVALID */
+int sd_ecapa_create(const sd_ecapa_config* cfg, sd_ecapa** out);
+/* load_state_dict (generate_chunk_..._ecapa_tdnn_...py:121; strict here) */
+int sd_ecapa_set_param(sd_ecapa* h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+int sd_ecapa_finalize(sd_ecapa* h);
+/* ecapa_tdnn_wespeaker.py:227-254.  feats: device (B, T, 80) fbank; emb: device (B, embed_dim) or NULL =
+ * linear(bn(pool(out))); time_out: device (B, T, 1536) channel-last fp32 or NULL (forward(x, get_time_out=True)
+ * transposed; the time axis is not subsampled).  emb with T == 1 is refused with SD_ERR_SHAPE: the reference's
+ * unbiased variance of a single frame (ASTP's global context) is NaN. */
+int sd_ecapa_forward(sd_ecapa* h, const float* feats, int B, int T, float* emb, float* time_out, void* stream);
+/* Device (B, 3072) pre-bn ASTP statistics [mean | std] of the last forward that wrote embeddings (diagnostics). */
+int sd_ecapa_debug_stats(const sd_ecapa* h, void** ptr);
+int64_t sd_ecapa_device_bytes(const sd_ecapa* h);
+int sd_ecapa_destroy(sd_ecapa* h);
 
 /* ------------------------------------------------------------------ SSND
  * Replaces SSNDModel.infer (egs/alimeeting/ssnd/ssnd_model.py:752-776) with extractor
@@ -511,6 +548,22 @@ int sd_op_res_conv(const void* x, int B, int H, int W, int Cin, const float* w, 
  * (x_bf16): stats (B, 2C) fp32 = [mean over T | sqrt(unbiased variance over T + 1e-7)].  A NaN stays in its
  * channel; T == 1 gives NaN stds. */
 int sd_op_tstp_pool(const void* x, int x_bf16, int B, int T, int C, float* stats, void* stream);
+/* Res2Conv1dReluBn at scale 8 (ecapa_tdnn_wespeaker.py:30-79) on a channel-last map x (B, T, 1024): stage i = 0..6
+ * computes sp_i = relu(conv_i(sp_{i-1} + x[.., 128 i : 128 i + 128]) + bias_i) * s_i + h_i (stage 0 without sp; conv_i
+ * 128 -> 128, k3, dilation = padding = `dilation`, zeros outside the window's own [0, T)) into out[.., 128 i : ..],
+ * channels 896.. are copied through.  w fp32 (7, 128, 128, 3), bias / s / h fp32 (7, 128) (s, h: the folded BatchNorm
+ * that follows the ReLU).  precision 0: x / out fp32, exact; 1: x / out bf16 bits, bf16 MFMA; 2: fp32, bf16x3.
+ * use_generic 1: seven conv_gemm launches (the only form of precision 0 and 2); 0: the single-launch kernel of
+ * ecapa.hip (precision 1 and dilation <= 4 only, SD_ERR_INVALID otherwise). */
+int sd_op_res2_chain(const void* x, int B, int T, int dilation, const float* w, const float* bias, const float* s,
+                     const float* h, void* out, int use_generic, int precision, void* stream);
+/* ASTP with the global context (pooling_layers_wespeaker.py:91-144) on a channel-last map x (B, T, 1536), fp32 or
+ * bf16 bits (x_bf16): stats (B, 3072) fp32 = [sum_t a x | sqrt(clamp(sum_t a x^2 - mean^2, 1e-7))] with a =
+ * softmax over T of linear2(tanh(linear1([x | mean | sqrt(unbiased var + 1e-7)]))).  w1 fp32 (128, 4608), b1 (128), w2
+ * (1536, 128), b2 (1536).  The statistics are accumulated in fp64 and the two linears run in fp32 whatever x's type.
+ * T < 2 gives SD_ERR_SHAPE (the reference's variance of one frame is NaN). */
+int sd_op_astp_pool(const void* x, int x_bf16, int B, int T, const float* w1, const float* b1, const float* w2,
+                    const float* b2, float* stats, void* stream);
 /* TS-VAD speaker input through proj_layer (model.py:212-217, 870-876), the stage of configurations with
  * 2 * speaker_embed_dim != transformer_embed_dim: out[(b, spk, t), :] = w [ts[b, spk] | relu(bn(mix[b, t]))] + bias
  * + pe[t], with w (E, 2 SE) split on its input axis (one GEMM over the B * NS embeddings, one over the B * Tmix mix

@@ -96,6 +96,16 @@ class Resnet34Config(ctypes.Structure):
     ]
 
 
+class EcapaConfig(ctypes.Structure):
+    _fields_ = [
+        ("channels", c_int),
+        ("embed_dim", c_int),
+        ("max_batch", c_int),
+        ("max_frames", c_int),
+        ("precision", c_int),
+    ]
+
+
 class SsndConfig(ctypes.Structure):
     _fields_ = [(n, c_int) for n in (
         "max_batch", "max_fbank_frames", "max_speakers", "feat_dim", "emb_dim", "q_det_aux_dim", "q_rep_aux_dim",
@@ -141,6 +151,8 @@ _SIGS = {
     "sd_ssnd_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_campp_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_resnet34_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sd_ecapa_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sd_ecapa_debug_stats": (c_int, [c_void_p, POINTER(c_void_p)]),
     "sd_eda_input_stride": (c_int, [c_void_p]),
     "sd_eda_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
@@ -188,6 +200,10 @@ _SIGS = {
     "sd_op_res_conv": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "sd_op_tstp_pool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sd_op_res2_chain": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                 c_int, c_void_p]),
+    "sd_op_astp_pool": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
     "sd_op_speaker_input_proj": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                          c_int, c_void_p]),
@@ -207,7 +223,7 @@ _SIGS = {
 # The handle lifecycle, the same five calls for every model kind (include/sdiar.h): create -> set_param* -> finalize
 # -> <the kind's forward calls>* -> destroy, device_bytes at any time.
 KINDS = {"tsvad": TsvadConfig, "tsvad_stream": TsvadStreamConfig, "eda": EdaConfig, "fseend": FseendConfig,
-         "campp": CamppConfig, "resnet34": Resnet34Config, "ssnd": SsndConfig}
+         "campp": CamppConfig, "resnet34": Resnet34Config, "ecapa": EcapaConfig, "ssnd": SsndConfig}
 for _kind, _conf in KINDS.items():
     _SIGS[f"sd_{_kind}_create"] = (c_int, [POINTER(_conf), POINTER(c_void_p)])
     _SIGS[f"sd_{_kind}_set_param"] = (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int])

@@ -17,6 +17,7 @@
 #include "tsvad.h"
 #include "campp.h"
 #include "resemb.h"
+#include "ecapa.h"
 #include "tsvad_stream.h"
 #include "ssnd.h"
 
@@ -40,6 +41,7 @@ struct sd_fseend : Handle<sd::FsEendModel> {};
 struct sd_fseend_stream : Handle<sd::FsEendStream> {};
 struct sd_campp : Handle<sd::CamppModel> {};
 struct sd_resnet34 : Handle<sd::ResEmbModel> {};
+struct sd_ecapa : Handle<sd::EcapaModel> {};
 struct sd_ssnd : Handle<sd::SsndModel> {};
 
 namespace {
@@ -183,7 +185,7 @@ int sd_probe_lstm_handoff(int steps, float* us_per_step, void* stream) {
 int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
-    SD_CHECK(c->variant >= 0 && c->variant <= 2, sd::kErrInvalid, "unknown TS-VAD variant");
+    SD_CHECK(c->variant >= 0 && c->variant <= 3, sd::kErrInvalid, "unknown TS-VAD variant");
     SD_CHECK(c->precision >= 0 && c->precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
     SD_CHECK(c->max_batch > 0 && c->max_fbank_frames > 0, sd::kErrInvalid, "bad workspace sizes");
     SD_CHECK(c->max_num_speaker > 0 && c->num_transformer_layer >= 1 && c->transformer_ffn_embed_dim > 0 &&
@@ -579,6 +581,47 @@ int64_t sd_resnet34_device_bytes(const sd_resnet34* h) { return device_bytes(h);
 
 int sd_resnet34_destroy(sd_resnet34* h) { return destroy(h); }
 
+int sd_ecapa_create(const sd_ecapa_config* c, sd_ecapa** out) {
+  return guard([&] {
+    SD_CHECK(c && out, sd::kErrInvalid, "null argument");
+    SD_CHECK(c->precision == 0 || c->precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    SD_CHECK(c->channels == 1024, sd::kErrInvalid, "ECAPA-TDNN (MI355X backend) builds channels 1024 only");
+    SD_CHECK(c->embed_dim >= 4 && c->embed_dim % 4 == 0, sd::kErrInvalid, "embed_dim must be a positive multiple of 4");
+    SD_CHECK(c->max_batch > 0 && c->max_frames >= 2, sd::kErrInvalid, "bad workspace sizes");
+    sd::EcapaConfig t;
+    t.embed_dim = c->embed_dim;
+    t.max_batch = c->max_batch;
+    t.max_frames = c->max_frames;
+    t.bf16 = c->precision == 1;
+    create(out, false, t);
+  });
+}
+
+int sd_ecapa_set_param(sd_ecapa* h, const char* name, const float* data, const int64_t* shape, int ndim) {
+  return set_param(h, name, data, shape, ndim);
+}
+
+int sd_ecapa_finalize(sd_ecapa* h) { return finalize(h); }
+
+int sd_ecapa_forward(sd_ecapa* h, const float* feats, int B, int T, float* emb, float* time_out, void* stream) {
+  return guard([&] {
+    SD_CHECK(h && feats && (emb || time_out), sd::kErrInvalid, "null argument");
+    h->model->forward(feats, B, T, emb, time_out, S(stream));
+  });
+}
+
+int sd_ecapa_debug_stats(const sd_ecapa* h, void** ptr) {
+  return guard([&] {
+    SD_CHECK(h && ptr, sd::kErrInvalid, "null argument");
+    SD_CHECK(h->model->finalized(), sd::kErrState, "model not finalized");
+    *ptr = const_cast<float*>(h->model->stats());
+  });
+}
+
+int64_t sd_ecapa_device_bytes(const sd_ecapa* h) { return device_bytes(h); }
+
+int sd_ecapa_destroy(sd_ecapa* h) { return destroy(h); }
+
 int sd_ssnd_create(const sd_ssnd_config* c, sd_ssnd** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
@@ -724,6 +767,57 @@ int sd_op_tstp_pool(const void* x, int x_bf16, int B, int T, int C, float* stats
   return guard([&] {
     SD_CHECK(x && stats, sd::kErrInvalid, "tstp_pool: null argument");
     sd::tstp_pool(x, x_bf16 != 0, B, T, C, stats, nullptr, S(stream));
+  });
+}
+
+int sd_op_res2_chain(const void* x, int B, int T, int dilation, const float* w, const float* bias, const float* s,
+                     const float* h, void* out, int use_generic, int precision, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && w && bias && s && h && out && B >= 1 && T >= 1 && dilation >= 1, sd::kErrInvalid,
+             "res2_chain: bad argument");
+    SD_CHECK(precision >= 0 && precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
+    SD_CHECK(use_generic || precision == 1, sd::kErrInvalid,
+             "res2_chain: the fused kernel is bf16 (precision 1); fp32 and bf16x3 take use_generic 1");
+    const bool bf = precision == 1;
+    const sd::GemmX3Scope x3(precision == 2);
+    constexpr int G = 128, NS = sd::Res2ChainW::kStages;
+    Scratch wt((size_t)NS * G * 3 * G * (bf ? 2 : 4), st), tmp((size_t)B * T * G * (bf ? 2 : 4), st);
+    sd::Res2ChainW W;
+    for (int i = 0; i < NS; ++i) {
+      void* wi = static_cast<char*>(wt.p) + (size_t)i * G * 3 * G * (bf ? 2 : 4);
+      sd::pack_weight(w + (size_t)i * G * G * 3, G, G, 3, wi, bf, st);
+      W.w[i] = wi; W.bias[i] = bias + i * G; W.s[i] = s + i * G; W.h[i] = h + i * G;
+    }
+    sd::res2_chain(x, B, T, dilation, W, tmp.p, out, bf, use_generic != 0, st);
+  });
+}
+
+int sd_op_astp_pool(const void* x, int x_bf16, int B, int T, const float* w1, const float* b1, const float* w2,
+                    const float* b2, float* stats, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && w1 && b1 && w2 && b2 && stats && B >= 1, sd::kErrInvalid, "astp_pool: bad argument");
+    SD_CHECK(T >= 2, sd::kErrShape, "ASTP needs at least 2 frames (the unbiased variance of one frame is NaN)");
+    constexpr int C = 1536, H = 128;
+    const size_t rows = (size_t)B * T;
+    // linear1.weight (128, 3 C) split on its input axis: the per-frame half (packed for conv_gemm) and the context half
+    Scratch halves((size_t)3 * H * C * 4, st), w1x((size_t)H * C * 4, st), w2p((size_t)C * H * 4, st);
+    float* hx = static_cast<float*>(halves.p);
+    float* hc = hx + (size_t)H * C;
+    SD_HIP(hipMemcpy2DAsync(hx, (size_t)C * 4, w1, (size_t)3 * C * 4, (size_t)C * 4, H, hipMemcpyDeviceToDevice, st));
+    SD_HIP(hipMemcpy2DAsync(hc, (size_t)2 * C * 4, w1 + C, (size_t)3 * C * 4, (size_t)2 * C * 4, H,
+                            hipMemcpyDeviceToDevice, st));
+    sd::pack_weight(hx, H, C, 1, w1x.p, false, st);
+    sd::pack_weight(w2, C, H, 1, w2p.p, false, st);
+    Scratch ctx((size_t)B * 2 * C * 4, st), cv((size_t)B * H * 4, st), x32(x_bf16 ? rows * C * 4 : 4, st),
+        hh(rows * H * 4, st), e(rows * C * 4, st);
+    sd::AstpArgs a;
+    a.x = x; a.x_bf16 = x_bf16 != 0; a.B = B; a.T = T;
+    a.w1x = w1x.p; a.w1c = hc; a.b1 = b1; a.w2 = w2p.p; a.b2 = b2; a.stats = stats;
+    a.ctx = static_cast<float*>(ctx.p); a.cv = static_cast<float*>(cv.p); a.x32 = static_cast<float*>(x32.p);
+    a.h = static_cast<float*>(hh.p); a.e = static_cast<float*>(e.p);
+    sd::astp_pool(a, st);
   });
 }
 

@@ -78,6 +78,15 @@ __device__ __forceinline__ void staged_epilogue_f32(const ConvGemmArgs& p, const
       al[u] = (p.alpha && ok) ? p.alpha[n + u] : 1.f;
       be[u] = (p.beta && ok) ? p.beta[n + u] : 0.f;
     }
+    float ps[4], ph[4];
+    if (p.post_scale) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const bool ok = full || n + u < p.N;
+        ps[u] = ok ? p.post_scale[n + u] : 1.f;
+        ph[u] = ok ? p.post_shift[n + u] : 0.f;
+      }
+    }
     float4 rv[ITER];
     if (p.res) {
       const float* rbase = reinterpret_cast<const float*>(p.res);
@@ -105,6 +114,10 @@ __device__ __forceinline__ void staged_epilogue_f32(const ConvGemmArgs& p, const
       const float r4[4] = {p.res ? rv[i].x : 0.f, p.res ? rv[i].y : 0.f, p.res ? rv[i].z : 0.f, p.res ? rv[i].w : 0.f};
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = apply_act(v[u] * al[u] + be[u] + r4[u], p.act);
+      if (p.post_scale) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = v[u] * ps[u] + ph[u];
+      }
       const int64_t o = (int64_t)m * p.o_sw + n;
       if (full) *reinterpret_cast<float4*>(outp + o) = make_float4(v[0], v[1], v[2], v[3]);
       else
@@ -121,6 +134,7 @@ __device__ __forceinline__ void staged_epilogue_f32(const ConvGemmArgs& p, const
     if (p.beta) v += p.beta[n];
     if (p.res) v += reinterpret_cast<const float*>(p.res)[(int64_t)m * p.res_ld + n];
     v = apply_act(v, p.act);
+    if (p.post_scale) v = v * p.post_scale[n] + p.post_shift[n];
     if (p.gate) v *= p.gate[((int64_t)b * p.gate_nseg + wo / p.gate_seg) * p.N + n];
     outp[(int64_t)b * p.o_sb + (int64_t)ho * p.o_sh + (int64_t)wo * p.o_sw + (int64_t)n * p.o_sn] = v;
   }
@@ -344,6 +358,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p) {
         if (p.beta) v += p.beta[n];
         if (p.res) v += reinterpret_cast<const float*>(p.res)[(int64_t)m * p.res_ld + n];
         v = apply_act(v, p.act);
+        if (p.post_scale) v = v * p.post_scale[n] + p.post_shift[n];
         if (p.gate) v *= p.gate[((int64_t)b * p.gate_nseg + wo / p.gate_seg) * p.N + n];
         reinterpret_cast<float*>(p.out)[obase + (int64_t)n * p.o_sn] = v;
       }
@@ -621,6 +636,8 @@ void conv_gemm(const ConvGemmArgs& p, bool bf16, hipStream_t st) {
   SD_CHECK(p.lda % 4 == 0 && p.a_coff % 4 == 0, kErrInvalid, "conv_gemm: lda/a_coff must be multiples of 4");
   SD_CHECK(p.N > 0 && p.B > 0 && p.Ho > 0 && p.Wo > 0, kErrInvalid, "conv_gemm: empty problem");
   SD_CHECK(!p.gate || p.gate_seg > 0, kErrInvalid, "conv_gemm: gate_seg must be > 0");
+  SD_CHECK((p.post_scale == nullptr) == (p.post_shift == nullptr), kErrInvalid,
+           "conv_gemm: post_scale and post_shift come together");
   SD_CHECK(!p.glu || (bf16 && gemm_stream_supported(p)), kErrInvalid,
            "conv_gemm: the GLU epilogue exists on the bf16 streaming path only");
   SD_CHECK(!p.a_tiled || (bf16 && p.a_bf16 && p.lda == p.K && p.a_coff == 0 && (p.B * p.Ho * p.Wo) % 16 == 0 &&

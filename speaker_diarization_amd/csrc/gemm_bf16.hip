@@ -238,6 +238,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(ConvGemmArgs p) {
       if (p.beta) x += p.beta[nn];
       x += rv[u];
       x = apply_act(x, p.act);
+      if (p.post_scale) x = x * p.post_scale[nn] + p.post_shift[nn];
       if (gr) x *= gr[nn];
       v[u] = x;
     }
@@ -290,7 +291,9 @@ void conv_gemm_bf16(const ConvGemmArgs& p, hipStream_t st) {
                        (p.res ? (p.res_bf16 ? 2.0 : 4.0) * M * p.N : 0.0);
   // Path selection first, so the live timer (bench.py roofline) is keyed by the kernel that runs.
   enum Path { kFcm, kAreg, kRing, kStream, kDma, kReg } path = kReg;
-  if (fcm_conv_supported(p))              // CAM++ FCM 3x3 32->32 convs (fcm_conv.hip)
+  if (p.post_scale)                       // the post-activation affine: the ring GEMM's wide form, or this file's kernel
+    path = gemm_ring_supported(p) ? kRing : kReg;
+  else if (fcm_conv_supported(p))         // CAM++ FCM 3x3 32->32 convs (fcm_conv.hip)
     path = kFcm;
   else if (gemm_areg_supported(p))        // A read once, weights streamed (gemm_areg.hip)
     path = kAreg;

@@ -237,6 +237,14 @@ __global__ __launch_bounds__(kRingThreads) void gemm_ring_kernel(ConvGemmArgs p)
       }
       const int m = m0 + wm * TM + mt * 16 + l15;
       const int n = n0 + wn * TN + nt * 16 + lk * 4;
+      if (p.post_scale && n < p.N) {   // BatchNorm after the activation (N % 4 == 0: the four columns exist)
+        const float4 ps = *reinterpret_cast<const float4*>(p.post_scale + n);
+        const float4 ph = *reinterpret_cast<const float4*>(p.post_shift + n);
+        x[0] = x[0] * ps.x + ph.x;
+        x[1] = x[1] * ps.y + ph.y;
+        x[2] = x[2] * ps.z + ph.z;
+        x[3] = x[3] * ps.w + ph.w;
+      }
       const uint32_t off = (m < M && n < p.N) ? (uint32_t)(((int64_t)m * p.o_sw + n) * eb) : kOOB;
       if (p.out_bf16) {
         const u32x2_t v = {pack_bf16x2(x[0], x[1]), pack_bf16x2(x[2], x[3])};
@@ -515,7 +523,8 @@ bool gemm_ring_supported(const ConvGemmArgs& p) {
   const int64_t a_bytes = ((int64_t)p.B * p.H * p.W) * p.lda * 2;
   // fp32 output: the one-tile-per-workgroup kernel only (N > RBN); K > kRingMaxK: no prologue (the s/h
   // staging in LDS is what bounds K)
-  return p.a_bf16 && (p.out_bf16 || p.N > RBN) && !p.gate && !p.res && !p.glu && p.kh * p.kw == 1 &&
+  // the post-activation affine: the one-tile-per-workgroup kernel only
+  return p.a_bf16 && (p.out_bf16 || p.N > RBN) && (!p.post_scale || p.N > RBN) && !p.gate && !p.res && !p.glu && p.kh * p.kw == 1 &&
          (!p.pre_scale || p.pre_shift) && (!p.pre_scale || p.K <= kRingMaxK) && p.K % 8 == 0 && p.lda % 8 == 0 &&
          p.a_coff % 8 == 0 && p.N >= 96 && p.N % 4 == 0 && p.o_sw % 4 == 0 && row_major && M >= 8 * RBM &&
          a_bytes < (int64_t)kOOB && (int64_t)p.N * p.K * 2 < (int64_t)kOOB;

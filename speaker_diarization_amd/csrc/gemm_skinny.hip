@@ -305,7 +305,7 @@ void launch_skinny(const ConvGemmArgs& p, int M, int rs, bool wbf, hipStream_t s
 
 bool gemm_skinny_supported(const ConvGemmArgs& p) {
   const int M = p.B * p.Ho * p.Wo;
-  if (M < 1 || M > 16 || p.pre_scale || p.gate || p.glu) return false;
+  if (M < 1 || M > 16 || p.pre_scale || p.post_scale || p.gate || p.glu) return false;
   if (p.K % 8 != 0) return false;
   const int rs = skinny_row_stride(p);
   if (rs < 0) return false;

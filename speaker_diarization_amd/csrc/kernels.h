@@ -29,6 +29,11 @@ struct ConvGemmArgs {
   bool res_bf16 = false;
   int res_ld = 0;
   int act = kActNone;
+  // Post-activation affine per output channel, v = act(v) * post_scale[n] + post_shift[n]: a BatchNorm that FOLLOWS
+  // the ReLU (ECAPA's Conv1dReluBn).  Null (the default): off.  On the exact / bf16x3 kernels, the ring GEMM (N > 128)
+  // and the register-staged bf16 kernel; conv_gemm selects one of these (the other bf16 paths do not read it).
+  const float* post_scale = nullptr;
+  const float* post_shift = nullptr;
   const float* gate = nullptr;       // gate[(b*gate_nseg + wo/gate_seg)*N + n]
   int gate_seg = 1, gate_nseg = 1;
   void* out = nullptr;               // out[b*o_sb + ho*o_sh + wo*o_sw + n*o_sn]
@@ -196,6 +201,53 @@ void tstp_pool(const void* x, bool x_bf16, int B, int T, int C, float* stats, fl
 void seg_linear(const float* x, int B, int K, const float* w, const float* bias, int N, float* y, hipStream_t st);
 // y = x < 0 ? 0 : x over n floats: F.relu that keeps NaN (resnet_wespeaker.py:178).
 void relu_keep_nan(const float* x, int64_t n, float* y, hipStream_t st);
+
+// ---------------------------------------------------------------- ecapa-tdnn (ecapa.hip)
+// layer1's input rows: out (B, T, 400) = the k5 pad-2 window [t - 2, t + 2] of fbank (B, T, 80), tap-major, zeros
+// outside the window's own [0, T) (ecapa_tdnn_wespeaker.py:193-196).
+void ecapa_im2col(const float* fbank, int B, int T, void* out, bool out_bf16, hipStream_t st);
+// out[r, 0..128) = a[r, 0..128) (+ b[r, 0..128), nullable) over `rows` rows of strides lda / ldb / ldo (elements;
+// the pointers already at their channel slice): a Res2 stage's input sp + split_i, or the pass-through group (:66-76).
+void ecapa_add_slice(const void* a, int lda, const void* b, int ldb, int64_t rows, void* out, int ldo, bool bf16,
+                     hipStream_t st);
+// Res2Conv1dReluBn at scale 8 (:30-79): seven 128 -> 128 k3 dilated stages, weights packed Wt[128][tap * 128 + c]
+// (bf16 bits or fp32), bias and the folded BatchNorm (s, h) that follows each stage's ReLU.
+struct Res2ChainW {
+  static constexpr int kStages = 7, kWidth = 128;
+  const void* w[kStages] = {};
+  const float *bias[kStages] = {}, *s[kStages] = {}, *h[kStages] = {};
+};
+// The whole chain of a bf16 map x (B, T, 1024) -> out (B, T, 1024) in ONE launch (ecapa.hip): a workgroup owns 64
+// output frames of one window, recomputes a halo of 7 * dilation frames per side, keeps every intermediate in LDS and
+// holds each stage's weights in registers as MFMA operands.  bf16 weights; dilation 1..4.
+bool res2_chain_fused_supported(int dilation);
+void res2_chain_fused(const void* x, int B, int T, int dilation, const Res2ChainW& W, void* out, hipStream_t st);
+// SE_Connect's gate (:119-123) of y (B, T, 1024): mean (B, 1024) scratch = mean over all T frames (fixed-order fp64
+// sums, no atomics), gate (B, 1024) = sigmoid(W2 relu(W1 mean + b1) + b2); both weights transposed, w1t
+// (1024, 128) and w2t (128, 1024), fp32.
+void ecapa_se_gate(const void* y, bool y_bf16, int B, int T, const float* w1t, const float* b1, const float* w2t,
+                   const float* b2, float* mean, float* gate, hipStream_t st);
+// out[b, t, c] = x[b, t, c] + y[b, t, c] * gate[b, c], c < 1024 (:124, :158); x / out at row strides ldx / ldo.
+void ecapa_se_apply(const void* x, int ldx, const void* y, const float* gate, int B, int T, void* out, int ldo,
+                    bool bf16, hipStream_t st);
+// ASTP with global_context_att (pooling_layers_wespeaker.py:91-144) over x (B, T, 1536) channel-last:
+// stats (B, 3072) = [sum_t a x | sqrt(clamp(sum_t a x^2 - mean^2, 1e-7))], a = softmax_t(W2 tanh(W1 [x | mean |
+// std] + b1) + b2).  The context statistics and the weighted sums are fp64, the two GEMMs exact fp32 (bf16x3 under a
+// GemmX3Scope) whatever x's type.  T < 2 raises kErrShape (the reference's unbiased variance of one frame is NaN).
+struct AstpArgs {
+  const void* x = nullptr;
+  bool x_bf16 = false;
+  int B = 0, T = 0;
+  const void* w1x = nullptr;   // packed fp32 [128][1536]: linear1.weight[:, :1536]
+  const float* w1c = nullptr;  // (128, 3072) row-major: linear1.weight[:, 1536:]
+  const float* b1 = nullptr;
+  const void* w2 = nullptr;    // packed fp32 [1536][128]
+  const float* b2 = nullptr;
+  float* stats = nullptr;      // (B, 3072)
+  float *ctx = nullptr, *cv = nullptr;   // scratch (B, 3072), (B, 128)
+  float *x32 = nullptr, *h = nullptr, *e = nullptr;   // scratch (B T, 1536) (bf16 x only), (B T, 128), (B T, 1536)
+};
+void astp_pool(const AstpArgs& a, hipStream_t st);
 
 // ---------------------------------------------------------------- norms
 // y = LN(x) * g + b over the last dim D; rows of x at stride ldx, y at ldy.

@@ -5,10 +5,12 @@
 //     -> speech encoder trunk (trunk_forward), over the batch or as two window slices on two streams (run_sliced)
 //          variants 0, 1: CAM++ FCM head + xvector[:-2]       cam_pplus_wespeaker.py:271-399
 //          variant 2 (speech_encoder_type resnet34_wespeaker, model.py:584-606): ResNet34 trunk (resnet.h)
+//          variant 3 (ecapa_channel_1024_wespeaker, model.py:631-654): ECAPA-TDNN trunk (ecapa.h)
 //     -> speech_down_or_up (down_gemm) -> mix (B, T3, SE)
 //          variants 0, 1: conv + BN + ReLU                    model.py:385-395 / 406-416
 //          variant 2: SpeechFeatUpsample2 transposed conv + BN + ReLU (model.py:114-134)
-//     -> transformer_backend, variants 0 and 2 (forward_common, model.py:758-897):
+//          variant 3: conv k5 stride 4 pad 2 + BN + ReLU (model.py:641-654)
+//     -> transformer_backend, variants 0, 2 and 3 (forward_common, model.py:758-897):
 //          [ts_embed | mix] + PE, 2-layer transformer per speaker (batched over speakers)
 //          -> backend_down conv(1536->384, k5)+BN+ReLU -> PE -> 2-layer transformer -> fc
 //        ots_vad_backend, variant 1 (forward_common_ots_vad, model.py:669-756):
@@ -45,6 +47,9 @@ void TsvadModel::build() {
   if (cfg_.variant == 2) {
     res_ = std::make_unique<ResTrunk>();
     res_->load(ps_, arena_, se, cfg_.bf16);   // resnet_wespeaker.py:108-171
+  } else if (cfg_.variant == 3) {
+    ecapa_ = std::make_unique<EcapaTrunk>();
+    ecapa_->load(ps_, arena_, se, cfg_.bf16);   // ecapa_tdnn_wespeaker.py:161-209 (no pool / bn / linear keys)
   } else {
     cam_ = std::make_unique<CamTrunk>();
     cam_->load(ps_, arena_, se, cfg_.bf16);   // cam_pplus_wespeaker.py:271-372
@@ -89,6 +94,14 @@ void TsvadModel::build() {
     down_.w = upload_packed(arena_, wt, 2 * D, C, 1, 3, cfg_.bf16);
     down_.beta = arena_.upload(bias);
     down_bn_ = bn_only("speech_down_or_up.batchnorm.bn");
+  } else if (cfg_.variant == 3) {
+    // Conv1d(1536 -> D, k5, stride 4, pad 2) (model.py:643-650) on the trunk's ReLU output: no prologue
+    down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
+    SD_CHECK(down_.w.N == cfg_.speaker_embed_dim && down_.w.Cin == EcapaTrunk::kChannels && down_.w.kw == 5, kErrParam,
+             "speech_down_or_up.0.weight must be (speaker_embed_dim, 1536, 5)");
+    SD_CHECK(ps_.get("speech_down_or_up.0.bias").numel() == cfg_.speaker_embed_dim, kErrParam,
+             "speech_down_or_up.0.bias size");
+    down_bn_ = bn_only("speech_down_or_up.1.bn");
   } else {
     down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
     down_bn_ = bn_only("speech_down_or_up.1.bn");
@@ -96,7 +109,7 @@ void TsvadModel::build() {
     down_.pre_h = cam_->out_h();
   }
 
-  if (cfg_.variant == 0 || cfg_.variant == 2) {
+  if (transformer_variant()) {
     const HostTensor& pe = ps_.get("pos_encoder.pe");
     SD_CHECK(pe.shape.size() == 3 && pe.shape[2] == cfg_.embed_dim, kErrParam, "pos_encoder.pe shape");
     pe_len_ = (int)pe.shape[0];
@@ -171,6 +184,7 @@ void TsvadModel::alloc_workspace() {
   const Geometry g = geometry();
   const int64_t Bm = cfg_.max_batch, NS = cfg_.max_num_speaker, E = cfg_.embed_dim;
   if (res_) res_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
+  else if (ecapa_) ecapa_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
   else cam_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
   mix_ = ws(g.mix_elems);
   mixg_ = ws(g.mix_elems);
@@ -241,7 +255,7 @@ void TsvadModel::debug_buffer(int which, void** ptr, int64_t* bytes) const {
   }
 }
 
-// forward_common's back end from the mix embeddings on (model.py:856-897), shared by variants 0 and 2: mix_ holds
+// forward_common's back end from the mix embeddings on (model.py:856-897), shared by variants 0, 2 and 3: mix_ holds
 // speech_down_or_up's conv + bias (B, T3, SE); its BatchNorm1D + ReLU are applied on load (sd_bn).
 void TsvadModel::transformer_backend(const float* ts, int T3, int B, int Tl, float* logits, hipStream_t st,
                                      const BnRelu& sd_bn, const BnRelu& bd_bn) {
@@ -356,6 +370,7 @@ void TsvadModel::run_sliced(int B, bool two, hipStream_t st,
 }
 
 Tens TsvadModel::trunk_forward(const float* ref, int Bh, int Tf, hipStream_t s, int b0) const {
+  if (ecapa_) return ecapa_->forward(ref, Bh, Tf, s, b0);
   return res_ ? res_->forward(ref, Bh, Tf, s, b0) : cam_->forward(ref, Bh, Tf, s, b0);
 }
 
@@ -364,6 +379,8 @@ ConvGemmArgs TsvadModel::down_gemm(Tens x, int Bh, int Tf, float* out) const {
   const int SE = cfg_.speaker_embed_dim;
   // ResNet34: (Bh, T4, 2560) -> (Bh, T4, [y[2j] | y[2j+1]]) = (Bh, 2 T4, SE), the upsampler as a k3 pad-1 conv
   if (res_) return cam_conv1d(x, Bh, ResTrunk::out_frames(Tf), ResTrunk::kChannels, down_, 1, 1, 1, Tens{out, false}, 2 * SE);
+  // ECAPA: k5 stride-4 pad-2 conv over the unsubsampled (Bh, Tf, 1536) map
+  if (ecapa_) return cam_conv1d(x, Bh, Tf, EcapaTrunk::kChannels, down_, 4, 2, 1, Tens{out, false}, SE);
   // CAM++: k5 stride-2 pad-2 conv, out_nonlinear's BN-ReLU fused as its prologue
   return cam_conv1d(x, Bh, CamTrunk::out_frames(Tf), CamTrunk::kChannels, down_, 2, 2, 1, Tens{out, false}, SE);
 }
@@ -379,7 +396,9 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   SD_CHECK(forward_batch >= 0 && force >= 0 && force <= 3, kErrInvalid, "forward: bad forward_batch / force");
   require_finalized();
   SD_CHECK(B >= 1 && B <= cfg_.max_batch, kErrInvalid, "batch exceeds max_batch");
-  SD_CHECK(Tf >= 8 && Tf <= cfg_.max_fbank_frames, kErrInvalid, "fbank frames exceed max_fbank_frames");
+  // ECAPA never subsamples inside the trunk: any window of at least one frame runs
+  SD_CHECK(Tf >= (cfg_.variant == 3 ? 1 : 8) && Tf <= cfg_.max_fbank_frames, kErrInvalid,
+           "fbank frames exceed max_fbank_frames");
   raise_if_set();
   const int T3 = mix_frames(Tf);
   check_label_frames(T3, Tl);

@@ -4,6 +4,7 @@
 #include <memory>
 #include <vector>
 #include "campp.h"
+#include "ecapa.h"
 #include "resnet.h"
 
 namespace sd {
@@ -11,6 +12,7 @@ namespace sd {
 struct TsvadConfig {
   int variant = 0;            // 0: CAM++ + transformer (model.py:758-897); 1: CAM++_ots_vad (669-756);
                               // 2: resnet34_wespeaker + SpeechFeatUpsample2 + transformer (584-606, 114-134)
+                              // 3: ecapa_channel_1024_wespeaker + conv k5 stride 4 + transformer (631-654)
   int max_num_speaker = 4;
   int rs_len = 4;
   int max_batch = 64;
@@ -32,7 +34,7 @@ class TsvadModel : public ModelCore {
  public:
   explicit TsvadModel(const TsvadConfig& c) : cfg_(c) {}
   // Raises kErrInvalid for a configuration the runner does not build (sd_tsvad_create calls it): with
-  // speaker_embed_dim * 2 != embed_dim the reference inserts proj_layer (model.py:212-217), built for variants 0 and 2.
+  // speaker_embed_dim * 2 != embed_dim the reference inserts proj_layer (model.py:212-217), built for variants 0, 2 and 3.
   static void validate(const TsvadConfig& c);
   // ref_speech (B, T_fb, 80) fbank, target_speech (B, NS, speaker_embed_dim), logits out (B, NS, T_lab).
   // forward_batch: windows per reference forward call, the scope of BatchNorm1D's NaN bypass (model.py:161-171),
@@ -91,10 +93,15 @@ class TsvadModel : public ModelCore {
   // speech_encoder.* (get_time_out=True): the one trunk the variant uses, the other stays empty
   std::unique_ptr<CamTrunk> cam_;   // CAM++, variants 0 and 1
   std::unique_ptr<ResTrunk> res_;   // ResNet34, variant 2
-  // frames of the speech_down_or_up output for T_fb fbank frames (the conv's stride 2, or the upsampler's 2 T')
+  std::unique_ptr<EcapaTrunk> ecapa_;   // ECAPA-TDNN c1024, variant 3
+  // frames of the speech_down_or_up output for T_fb fbank frames (the conv's stride 2, the upsampler's 2 T', or
+  // ECAPA's stride 4 on the unsubsampled time axis)
   int mix_frames(int Tf) const {
+    if (cfg_.variant == 3) return (Tf - 1) / 4 + 1;
     return cfg_.variant == 2 ? 2 * ResTrunk::out_frames(Tf) : (CamTrunk::out_frames(Tf) - 1) / 2 + 1;
   }
+  // the back end of forward_common (variant 0's; also behind the ResNet34 and ECAPA encoders)
+  bool transformer_variant() const { return cfg_.variant != 1; }
   // speech_down_or_up conv: epilogue = + bias only (its BatchNorm1D is down_bn_).  Variant 2: the transposed conv
   // ConvTranspose1d(2560 -> D, k5, stride 2, pad 2, output_padding 1) as ONE k-3 pad-1 conv with 2 D outputs per
   // input frame j, [even phase y[2j] | odd phase y[2j+1]] = two consecutive rows of the (B, 2 T', D) output.

@@ -6,7 +6,11 @@ Drop-in for the step before TS-VAD inference:
     forward(x, get_time_out=True) -> (B, 512, T')), run by libsdiar (`sd_campp_*`).
   * `ResNet34` — egs/alimeeting/ts_vad2/resnet_wespeaker.py:108-208 (speech_encoder=False): the WeSpeaker
     ResNet34 extractor of generate_chunk_speaker_embedding_from_wespeaker_for_diarization.py:116-133 (256-d
-    embeddings, TSTP pooling + seg_1), run by libsdiar (`sd_resnet34_*`); `extract_embed` drives either model.
+    embeddings, TSTP pooling + seg_1), run by libsdiar (`sd_resnet34_*`).
+  * `ECAPA_TDNN_GLOB_c1024` — egs/alimeeting/ts_vad2/ecapa_tdnn_wespeaker.py:161-271: the WeSpeaker ECAPA-TDNN
+    extractor of generate_chunk_speaker_embedding_from_ecapa_tdnn_for_diarization.py:95-172 (192-d embeddings,
+    attentive statistics pooling with the global context), run by libsdiar (`sd_ecapa_*`); `extract_embed` drives
+    any of the three models.
   * `FBank` — the extractor's FBank (generate_chunk_speaker_embedding_from_modelscope_for_
     diarization.py:307-331): kaldi fbank with the povey window, dither 0, no 2^15 scale,
     mean_nor over the chunk.
@@ -171,6 +175,91 @@ class ResNet34(_lib.Handle):
     __call__ = forward
 
 
+class ECAPA_TDNN_GLOB_c1024(_lib.Handle):
+    """egs/alimeeting/ts_vad2/ecapa_tdnn_wespeaker.py:161-254, 264-271 with speech_encoder=False: ECAPA-TDNN at 1024
+    channels with global-context ASTP, bn and linear, run by libsdiar (`sd_ecapa_*`).  Same constructor arguments and
+    standalone state_dict keys; forward(x) -> (B, embed_dim), forward(x, get_time_out=True) -> (B, 1536, T).  The
+    encoder-only form (speech_encoder=True) is TSVADModel's speech encoder, not this class."""
+    kind = "ecapa"
+
+    def __init__(self, feat_dim: int = 80, embed_dim: int = 192, pooling_func: str = "ASTP", emb_bn: bool = False,
+                 speech_encoder: bool = False, *, device=None, precision: str = "bf16", max_batch: int = 96,
+                 max_frames: int = 598):
+        if pooling_func != "ASTP":
+            raise ValueError(f"the MI355X ECAPA-TDNN builds ASTP pooling only, got {pooling_func}")
+        if emb_bn:
+            raise ValueError("the MI355X ECAPA-TDNN builds emb_bn=False only (the extractor script's setting)")
+        if speech_encoder:
+            raise ValueError("speech_encoder=True (no pooling head) is TSVADModel's ecapa_channel_1024_wespeaker "
+                             "speech encoder")
+        if feat_dim != 80:
+            raise ValueError(f"the MI355X ECAPA-TDNN supports feat_dim 80 only, got {feat_dim}")
+        code = _lib.precision_code(precision, ("bf16", "fp32"))
+        self.device = _lib.hip_device(device, "ECAPA_TDNN_GLOB_c1024")
+        self.feat_dim, self.embed_dim = feat_dim, embed_dim
+        self.embedding_size = embed_dim      # what extract_embed sizes its output with
+        self.precision, self.max_batch, self.max_frames = precision, max_batch, max_frames
+        self._create(_lib.EcapaConfig(channels=1024, embed_dim=embed_dim, max_batch=max_batch, max_frames=max_frames,
+                                      precision=code))
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        if not strict:
+            raise ValueError("the MI355X backend only supports strict=True loading")
+        self._load(unwrap_checkpoint(state_dict, kind="ecapa"))
+        return self
+
+    def eval(self):
+        return self
+
+    def to(self, device):
+        import torch
+        if torch.device(device) != self.device:
+            raise ValueError("re-create the model on the target device")
+        return self
+
+    @property
+    def device_bytes(self) -> int:
+        return self._device_bytes()
+
+    def forward(self, x, get_time_out: bool = False, out=None):
+        """x (B, T, 80) -> (B, embed_dim) (ecapa_tdnn_wespeaker.py:250-254), or (B, 1536, T) with get_time_out
+        (:247-249).  Embeddings need T >= 2 (AssertionError otherwise: the reference's are NaN there)."""
+        import torch
+        B, T, F = x.shape
+        if F != self.feat_dim:
+            raise ValueError(f"expected {self.feat_dim}-dim fbank, got {F}")
+        x = x.to(self.device, torch.float32).contiguous()
+        if B > self.max_batch:
+            parts = [self.forward(x[s:s + self.max_batch], get_time_out,
+                                  None if out is None else out[s:s + self.max_batch])
+                     for s in range(0, B, self.max_batch)]
+            return out if (out is not None and not get_time_out) else torch.cat(parts)
+        st = _lib.stream_ptr(self.device)
+        if get_time_out:
+            tout = torch.empty(B, T, 1536, device=self.device, dtype=torch.float32)
+            _lib.call("sd_ecapa_forward", self._h, _lib.ptr(x), B, T, None, _lib.ptr(tout), st)
+            return tout.permute(0, 2, 1)
+        if out is None:
+            out = torch.empty(B, self.embed_dim, device=self.device, dtype=torch.float32)
+        _lib.call("sd_ecapa_forward", self._h, _lib.ptr(x), B, T, _lib.ptr(out), None, st)
+        return out
+
+    __call__ = forward
+
+    def pooled_stats(self, B: int):
+        """The pre-bn ASTP statistics (B, 3072) [mean | std] of the last forward that returned embeddings."""
+        import ctypes
+        import torch
+        p = ctypes.c_void_p()
+        _lib.call("sd_ecapa_debug_stats", self._h, ctypes.byref(p))
+        out = torch.empty(B, 3072, device=self.device, dtype=torch.float32)
+        torch.cuda.current_stream(self.device).synchronize()
+        rc = ctypes.CDLL("libamdhip64.so").hipMemcpy(ctypes.c_void_p(out.data_ptr()), p, ctypes.c_size_t(out.numel() * 4), 3)
+        if rc != 0:
+            raise _lib.SdiarError("copy of the ASTP statistics failed")
+        return out
+
+
 def kaldi_fbank_povey(wav, n_mels: int = 80, out=None):
     """Kaldi.fbank(wav, num_mel_bins, sample_frequency=16000, dither=0) (povey window,
     samples as read, no 2^15 scale): 1-D float32 CUDA tensor -> (n_frames, n_mels)."""
@@ -217,8 +306,9 @@ def extract_embed(wav, model, length_embedding: float = 6.0, step_embedding: flo
                   batch_size: int = 96, n_mels: int = 80):
     """wav: 1-D float samples in [-1, 1) (numpy or tensor; soundfile values cast to float32
     like torch.FloatTensor at :283) -> (n_chunks, E) float32 embeddings on the model device.
-    model: CAMPPlus, or ResNet34 (generate_chunk_speaker_embedding_from_wespeaker_for_diarization.py:143-176, the
-    same chunk loop; the last element of the model's tuple is kept, :132-133).  A file too short for ResNet34's
+    model: CAMPPlus, ResNet34 (generate_chunk_speaker_embedding_from_wespeaker_for_diarization.py:143-176, the
+    same chunk loop; the last element of the model's tuple is kept, :132-133) or ECAPA_TDNN_GLOB_c1024
+    (generate_chunk_speaker_embedding_from_ecapa_tdnn_for_diarization.py:142-172, the same loop again).  A file too short for ResNet34's
     three stride-2 stages (at most 8 fbank frames) yields the reference's all-NaN embedding."""
     import torch
     dev = model.device

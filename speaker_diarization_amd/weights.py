@@ -52,12 +52,16 @@ class TSVADConfig:
         if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) == (
                 "resnet34_wespeaker", "transformer", "transformer"):
             return 2
+        if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) == (
+                "ecapa_channel_1024_wespeaker", "transformer", "transformer"):
+            return 3
         if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) != (
                 "CAM++", "transformer", "transformer"):
             raise ValueError(
                 f"unsupported TS-VAD configuration {self.speech_encoder_type}/"
                 f"{self.single_backend_type}/{self.multi_backend_type} (MI355X backend builds CAM++ "
-                "with transformer or conformer_ots_vad/lstm_ots_vad)")
+                "with transformer or conformer_ots_vad/lstm_ots_vad, resnet34_wespeaker and "
+                "ecapa_channel_1024_wespeaker with transformer)")
         return 0
 
     @staticmethod
@@ -69,12 +73,12 @@ class TSVADConfig:
         return TSVADConfig(**d)
 
 
-def _bn(keys: list, prefix: str, c: int, affine: bool = True):
+def _bn(keys: list, prefix: str, c: int, affine: bool = True, kind: str = "bn"):
     if affine:
-        keys.append((prefix + ".weight", (c,), "bn_w"))
-        keys.append((prefix + ".bias", (c,), "bn_b"))
-    keys.append((prefix + ".running_mean", (c,), "bn_m"))
-    keys.append((prefix + ".running_var", (c,), "bn_v"))
+        keys.append((prefix + ".weight", (c,), kind + "_w"))
+        keys.append((prefix + ".bias", (c,), kind + "_b"))
+    keys.append((prefix + ".running_mean", (c,), kind + "_m"))
+    keys.append((prefix + ".running_var", (c,), kind + "_v"))
     keys.append((prefix + ".num_batches_tracked", (), "nbt"))
 
 
@@ -162,6 +166,52 @@ def resnet34_embed_layout(embed_dim: int = 256, two_emb_layer: bool = False) -> 
     return k
 
 
+def _conv_relu_bn(k: list, p: str, cout: int, cin: int, taps: int, kind: str):
+    """Conv1dReluBn (ecapa_tdnn_wespeaker.py:85-108): conv with bias, ReLU, then BatchNorm."""
+    k.append((p + "conv.weight", (cout, cin, taps), kind))
+    k.append((p + "conv.bias", (cout,), "small"))
+    _bn(k, p + "bn", cout, kind="ec")
+
+
+def ecapa_layout(prefix: str = "speech_encoder.") -> list:
+    """Key layout of ECAPA_TDNN_GLOB_c1024(feat_dim=80, speech_encoder=True) (ecapa_tdnn_wespeaker.py:161-209): layer1
+    (k5), three SE_Res2Blocks (1x1, Res2 chain of 7 k3 128 -> 128 convs, 1x1, SE 1024 -> 128 -> 1024) and the
+    3072 -> 1536 conv; no pool / bn / linear (the TS-VAD speech encoder, model.py:631-640)."""
+    k: list = []
+    _conv_relu_bn(k, prefix + "layer1.", 1024, 80, 5, "ec_conv")
+    for layer in (2, 3, 4):
+        q = f"{prefix}layer{layer}.se_res2block."
+        _conv_relu_bn(k, q + "0.", 1024, 1024, 1, "ec_conv")
+        for i in range(7):
+            k.append((f"{q}1.convs.{i}.weight", (128, 128, 3), "ec_conv"))
+            k.append((f"{q}1.convs.{i}.bias", (128,), "small"))
+        for i in range(7):
+            _bn(k, f"{q}1.bns.{i}", 128, kind="ec")
+        _conv_relu_bn(k, q + "2.", 1024, 1024, 1, "ec_conv2")
+        k.append((q + "3.linear1.weight", (128, 1024), "ec_se1"))
+        k.append((q + "3.linear1.bias", (128,), "small"))
+        k.append((q + "3.linear2.weight", (1024, 128), "ec_se2"))
+        k.append((q + "3.linear2.bias", (1024,), "small"))
+    k.append((prefix + "conv.weight", (1536, 3072, 1), "ec_out"))
+    k.append((prefix + "conv.bias", (1536,), "small"))
+    return k
+
+
+def ecapa_embed_layout(embed_dim: int = 192) -> list:
+    """Key layout of the standalone extractor ECAPA_TDNN_GLOB_c1024(feat_dim=80, embed_dim, pooling_func="ASTP")
+    (ecapa_tdnn_wespeaker.py:161-225): the trunk of ecapa_layout("") + ASTP with global context
+    (pooling_layers_wespeaker.py:91-144: linear1 4608 -> 128, linear2 128 -> 1536) + bn(3072) + linear(3072 -> E)."""
+    k = ecapa_layout("")
+    k.append(("pool.linear1.weight", (128, 4608, 1), "ec_att1"))
+    k.append(("pool.linear1.bias", (128,), "small"))
+    k.append(("pool.linear2.weight", (1536, 128, 1), "ec_att2"))
+    k.append(("pool.linear2.bias", (1536,), "small"))
+    _bn(k, "bn", 3072, kind="ec")
+    k.append(("linear.weight", (embed_dim, 3072), "kaiming"))
+    k.append(("linear.bias", (embed_dim,), "small"))
+    return k
+
+
 def _mha(k: list, p: str, e: int):
     k.append((p + "in_proj_weight", (3 * e, e), "xavier"))
     k.append((p + "in_proj_bias", (3 * e,), "small"))
@@ -183,6 +233,12 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         k.append(("speech_down_or_up.up.weight", (2560, se, 5), "convT"))
         k.append(("speech_down_or_up.up.bias", (se,), "small"))
         _bn(k, "speech_down_or_up.batchnorm.bn", se)
+    elif cfg.variant == 3:
+        # ECAPA-TDNN c1024 + Conv1d(1536 -> D, k5, stride 4, pad 2) (model.py:631-654); the back end is variant 0's
+        k = ecapa_layout()
+        k.append(("speech_down_or_up.0.weight", (se, 1536, 5), "ec_down"))
+        k.append(("speech_down_or_up.0.bias", (se,), "small"))
+        _bn(k, "speech_down_or_up.1.bn", se)
     else:
         k = campplus_layout()
         if cfg.variant == 1:
@@ -196,7 +252,7 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         # 873-874); the reference registers it for every variant, its ots_vad forward never applies it
         k.append(("proj_layer.weight", (e, 2 * se), "linear"))
         k.append(("proj_layer.bias", (e,), "small"))
-    if cfg.variant in (0, 2):
+    if cfg.variant in (0, 2, 3):
         k.append(("pos_encoder.pe", (cfg.rs_len * cfg.label_rate, 1, e), "pe"))
         for i in range(cfg.num_transformer_layer):
             _tfm(k, f"single_backend.layers.{i}.", e, cfg.transformer_ffn_embed_dim)
@@ -269,6 +325,16 @@ RN_GAIN = {"rn_conv": 1.0, "rn_conv2": 0.3, "rn_sc": 0.7}
 CONVT_GAIN = 0.5
 
 
+# Seeded ECAPA init (ecapa_layout).  Every conv is followed by ReLU and THEN BatchNorm, so the BatchNorm's running
+# mean sits near the mean of a rectified unit-variance signal (0.4 +- 0.2) and its running variance varies by 3x:
+# a BatchNorm applied on the wrong side of the ReLU moves every activation by O(1).  The block's closing 1x1 conv
+# is damped so the three residual sums stay O(1); the SE and attention gains are tuned until
+# tests/golden/make_golden_ecapa.py's assertions on the reference run hold (gates on both sides of 0.4 .. 0.6,
+# attention weights neither uniform nor one-hot).
+EC_GAIN = {"ec_conv": 1.0, "ec_conv2": 0.5, "ec_out": 1.0, "ec_down": 0.5, "ec_se1": 1.0, "ec_se2": 2.0,
+           "ec_att1": 1.0, "ec_att2": 2.0}
+
+
 def _init(rng: np.random.Generator, shape: Shape, kind: str) -> np.ndarray:
     if kind == "nbt":
         return np.array(0, dtype=np.int64)
@@ -286,6 +352,16 @@ def _init(rng: np.random.Generator, shape: Shape, kind: str) -> np.ndarray:
         v = rng.uniform(-b, b, n)
     elif kind in RN_GAIN:                 # ResNet34 convs: He-normal times a per-role gain
         v = rng.standard_normal(n) * (RN_GAIN[kind] * np.sqrt(2.0 / fan_in))
+    elif kind in EC_GAIN:                 # ECAPA convs / linears: He-normal times a per-role gain
+        v = rng.standard_normal(n) * (EC_GAIN[kind] * np.sqrt(2.0 / fan_in))
+    elif kind == "ec_w":
+        v = rng.uniform(0.7, 1.3, n)
+    elif kind == "ec_b":
+        v = rng.standard_normal(n) * 0.1
+    elif kind == "ec_m":
+        v = rng.uniform(0.2, 0.6, n)
+    elif kind == "ec_v":
+        v = rng.uniform(0.5, 1.5, n)
     elif kind == "convT":                 # ConvTranspose1d (Cin, Cout, k), stride 2: Cin * k / 2 taps per output
         v = rng.standard_normal(n) * (CONVT_GAIN * np.sqrt(2.0 / (shape[0] * shape[2] / 2.0)))
     elif kind == "xavier":
@@ -480,6 +556,11 @@ def campplus_state_dict(seed: int = 777, embedding_size: int = 192):
 def resnet34_embed_state_dict(seed: int = 777, embed_dim: int = 256, two_emb_layer: bool = False):
     """Seeded weights for a standalone ResNet34 embedding extractor (keys conv1.*, layer*.*, seg_*)."""
     return synthetic_state_dict(resnet34_embed_layout(embed_dim, two_emb_layer), seed)
+
+
+def ecapa_embed_state_dict(seed: int = 777, embed_dim: int = 192):
+    """Seeded weights for a standalone ECAPA_TDNN_GLOB_c1024 extractor (keys layer*.*, conv.*, pool.*, bn.*, linear.*)."""
+    return synthetic_state_dict(ecapa_embed_layout(embed_dim), seed)
 
 
 def to_torch(sd):
