@@ -218,6 +218,47 @@ int sd_resnet34_forward(sd_resnet34* h, const float* feats, int B, int T, float*
 int64_t sd_resnet34_device_bytes(const sd_resnet34* h);
 int sd_resnet34_destroy(sd_resnet34* h);
 
+/* ------------------------------------------------------------------ SimAM-ResNet34 embeddings
+ * Replaces SimAM_ResNet34_ASP(in_planes=64, embed_dim=256, acoustic_dim=80, dropout=0, speech_encoder=False)
+ * (egs/alimeeting/ts_vad2/samresnet_wespeaker.py:21-160, pooling_layers_wespeaker.py:146-168) as the target-speaker
+ * embedding extractor of generate_chunk_speaker_embedding_from_wespeaker_for_diarization.py:
+ *   construction  :119-120
+ *   forward(x)    :131-133 / samresnet_wespeaker.py:143-160
+ * State-dict keys are the standalone module's (front.conv1.*, front.bn1.*, front.layer1..4.*.{conv1, bn1, conv2,
+ * bn2, downsample.0, downsample.1}.*, pooling.attention.{0, 2, 3}.*, bottleneck.*).  The encoder-only form
+ * (speech_encoder=True with forward(x, get_time_out=True), :146-153) raises NameError in the reference (it reads an
+ * undefined `out`), so there is nothing to reproduce and it is not built. */
+typedef struct sd_simam_resnet34 sd_simam_resnet34;
+
+typedef struct {
+  int in_planes;       /* 64 only (the stem's and stage 1's channels) */
+  int embed_dim;       /* 256 (a positive multiple of 8) */
+  int acoustic_dim;    /* 80 only */
+  int max_batch;       /* workspace: chunks per forward (extract_embed batch_size 96)      */
+  int max_frames;      /* workspace: fbank frames per chunk (598 for 6 s)                  */
+  int precision;       /* 0: fp32 (exact-f32 MFMA), 1: bf16 trunk (ASP and the bottleneck stay fp32) */
+} sd_simam_resnet34_config;
+
+/* samresnet_wespeaker.py:135-141; in_planes != 64 or acoustic_dim != 80 gives SD_ERR_INVALID */
+int sd_simam_resnet34_create(const sd_simam_resnet34_config* cfg, sd_simam_resnet34** out);
+/* load_state_dict (generate_chunk_..._wespeaker_...py:125; strict here) */
+int sd_simam_resnet34_set_param(sd_simam_resnet34* h, const char* name, const float* host_data, const int64_t* shape,
+                                int ndim);
+int sd_simam_resnet34_finalize(sd_simam_resnet34* h);
+/* samresnet_wespeaker.py:143-160.  feats: device (B, T, 80) fbank; emb: device (B, embed_dim) or NULL =
+ * bottleneck(pooling(front(x))); front_out: device (B, T', 5120) channel-last fp32 or NULL, T' = three times
+ * (n - 1) / 2 + 1 applied to T, channel c * 10 + f: the front's map as ASP.forward flattens it
+ * (pooling_layers_wespeaker.py:162), transposed.  T == 8 (T' = 1) is valid: the softmax weight is 1 and sg =
+ * sqrt(1e-5).  T < 8 gives SD_ERR_SHAPE: the trunk's kernels are exercised from 8 frames on. */
+int sd_simam_resnet34_forward(sd_simam_resnet34* h, const float* feats, int B, int T, float* emb, float* front_out,
+                              void* stream);
+/* Diagnostics (tools/simam_probe.py): what sd_simam_resnet34 handles finalized from now on build.  0 (the default):
+ * the model above; 1: the same trunk with plain BasicBlocks, NOT SimAM-ResNet34 (prices the SimAM kernels, DESIGN.md
+ * section 5c).  Never set in production code. */
+int sd_debug_simam_variant(int variant);
+int64_t sd_simam_resnet34_device_bytes(const sd_simam_resnet34* h);
+int sd_simam_resnet34_destroy(sd_simam_resnet34* h);
+
 /* ------------------------------------------------------------------ ECAPA-TDNN embeddings
  * Replaces ECAPA_TDNN_GLOB_c1024(feat_dim=80, embed_dim=192, pooling_func="ASTP")
  * (egs/alimeeting/ts_vad2/ecapa_tdnn_wespeaker.py:161-271, pooling_layers_wespeaker.py:91-144) as the target-speaker
@@ -536,8 +577,12 @@ int sd_op_conv1d(const float* x, int B, int T, int Cin, const float* w, const fl
 /* nn.Conv2d (Cin % 32 == 0) on NHWC x (B, H, W, Cin), weight (Cout, Cin, kh, kw) -> NHWC out. */
 int sd_op_conv2d(const float* x, int B, int H, int W, int Cin, const float* w, int Cout, int kh,
                  int kw, int sh, int sw, int ph, int pw, float* out, int precision, void* stream);
+/* The ResNet stems (Cin = 1, 3x3, pad 1 + folded BN + ReLU; resnet_wespeaker.py:127-128, samresnet_wespeaker.py:82-85):
+ * fbank (B, T, F) fp32, w (C, 1, 3, 3) fp32, C = 32 or 64 -> out NHWC (B, F, T, C), fp32 or bf16 bits (out_bf16). */
+int sd_op_stem_conv(const float* fbank, int B, int T, int F, const float* w, const float* alpha, const float* beta,
+                    int C, void* out, int out_bf16, void* stream);
 /* One 3x3, pad-1 convolution of the ResNet34 trunk on a bf16 NHWC map x (B, H, W, Cin), weight fp32 (Cout, Cin, 3, 3)
- * (rounded to bf16), Cin and Cout in {32, 64, 128, 256}, stride 1 or 2 (both axes): out bf16 NHWC (B, Ho, Wo, Cout) =
+ * (rounded to bf16), Cin and Cout in {32, 64, 128, 256, 512}, stride 1 or 2 (both axes): out bf16 NHWC (B, Ho, Wo, Cout) =
  * relu(conv * alpha + beta [+ res]), res bf16 NHWC like out or NULL.  sc_w (Cout, Cin, 1, 1) or NULL: the block's
  * 1x1 shortcut at the same stride, sc_out bf16 = conv1x1 * sc_alpha + sc_beta (no ReLU).  use_generic 0: res_conv.hip
  * (the shortcut from the centre tap of the same launch); 1: the same arguments through conv_gemm. */
@@ -564,6 +609,19 @@ int sd_op_res2_chain(const void* x, int B, int T, int dilation, const float* w, 
  * T < 2 gives SD_ERR_SHAPE (the reference's variance of one frame is NaN). */
 int sd_op_astp_pool(const void* x, int x_bf16, int B, int T, const float* w1, const float* b1, const float* w2,
                     const float* b2, float* stats, void* stream);
+/* ASP (pooling_layers_wespeaker.py:146-168) on a channel-last map x (B, T, C), C % 64 == 0, fp32 or bf16 bits (x_bf16):
+ * stats (B, 2 C) fp32 = [mu = sum_t a x | sqrt(clamp(sum_t a x^2 - mu^2, 1e-5))] with a = softmax over T of
+ * w2 bn(relu(w1 x + b1)) + b2.  w1 fp32 (128, C), b1 (128), bn_s / bn_h (128) the folded BatchNorm1d that follows the
+ * ReLU, w2 (C, 128), b2 (C).  The two linears run in fp32 and the statistics in fp64 whatever x's type.  T == 1 is
+ * valid: mu = x and the second half is sqrt(1e-5) exactly.  A NaN poisons the statistics of its own channel only (the
+ * attention GEMM's ReLU is a maximum, which drops it; the bottleneck then spreads it over the item's embedding). */
+int sd_op_asp_pool(const void* x, int x_bf16, int B, int T, int C, const float* w1, const float* b1, const float* bn_s,
+                   const float* bn_h, const float* w2, const float* b2, float* stats, void* stream);
+/* The SimAM gate, shortcut and ReLU of a SimAM BasicBlock (samresnet_wespeaker.py:57-70) on an NHWC map y (B, H, W, C),
+ * C % 64 == 0, dtype 0 fp32 / 1 bf16 bits: out (NHWC, y's type) = relu(y * sigmoid((y - mean)^2 / (4 (v + 1e-4)) + 0.5)
+ * + residual), mean and v = sum (y - mean)^2 / (H W - 1) per (b, c) in fp64 and a fixed order; residual NHWC like y, or
+ * NULL.  A NaN stays in its (b, c) channel; an item's result does not depend on the batch. */
+int sd_op_simam(const void* y, const void* residual, int dtype, int B, int H, int W, int C, void* out, void* stream);
 /* TS-VAD speaker input through proj_layer (model.py:212-217, 870-876), the stage of configurations with
  * 2 * speaker_embed_dim != transformer_embed_dim: out[(b, spk, t), :] = w [ts[b, spk] | relu(bn(mix[b, t]))] + bias
  * + pe[t], with w (E, 2 SE) split on its input axis (one GEMM over the B * NS embeddings, one over the B * Tmix mix

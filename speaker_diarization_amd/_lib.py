@@ -96,6 +96,17 @@ class Resnet34Config(ctypes.Structure):
     ]
 
 
+class SimamResnet34Config(ctypes.Structure):
+    _fields_ = [
+        ("in_planes", c_int),
+        ("embed_dim", c_int),
+        ("acoustic_dim", c_int),
+        ("max_batch", c_int),
+        ("max_frames", c_int),
+        ("precision", c_int),
+    ]
+
+
 class EcapaConfig(ctypes.Structure):
     _fields_ = [
         ("channels", c_int),
@@ -151,6 +162,8 @@ _SIGS = {
     "sd_ssnd_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_campp_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_resnet34_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sd_simam_resnet34_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sd_debug_simam_variant": (c_int, [c_int]),
     "sd_ecapa_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_ecapa_debug_stats": (c_int, [c_void_p, POINTER(c_void_p)]),
     "sd_eda_input_stride": (c_int, [c_void_p]),
@@ -204,6 +217,11 @@ _SIGS = {
                                  c_int, c_void_p]),
     "sd_op_astp_pool": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
+    "sd_op_asp_pool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
+    "sd_op_simam": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sd_op_stem_conv": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                c_void_p]),
     "sd_op_speaker_input_proj": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                          c_int, c_void_p]),
@@ -223,7 +241,8 @@ _SIGS = {
 # The handle lifecycle, the same five calls for every model kind (include/sdiar.h): create -> set_param* -> finalize
 # -> <the kind's forward calls>* -> destroy, device_bytes at any time.
 KINDS = {"tsvad": TsvadConfig, "tsvad_stream": TsvadStreamConfig, "eda": EdaConfig, "fseend": FseendConfig,
-         "campp": CamppConfig, "resnet34": Resnet34Config, "ecapa": EcapaConfig, "ssnd": SsndConfig}
+         "campp": CamppConfig, "resnet34": Resnet34Config, "simam_resnet34": SimamResnet34Config,
+         "ecapa": EcapaConfig, "ssnd": SsndConfig}
 for _kind, _conf in KINDS.items():
     _SIGS[f"sd_{_kind}_create"] = (c_int, [POINTER(_conf), POINTER(c_void_p)])
     _SIGS[f"sd_{_kind}_set_param"] = (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int])

@@ -63,19 +63,20 @@ ConvL load_conv_bn(ParamStore& ps, DeviceArena& arena, bool bf16, const std::str
   return L;
 }
 
-ResBlockL load_res_block(ParamStore& ps, DeviceArena& arena, bool bf16, const std::string& p, int stride, bool has_sc) {
+ResBlockL load_res_block(ParamStore& ps, DeviceArena& arena, bool bf16, const std::string& p, int stride, bool has_sc,
+                         const std::string& sc_key) {
   ResBlockL rb;
   rb.stride = stride;
   rb.c1 = load_conv_bn(ps, arena, bf16, p + "conv1.weight", p + "bn1");
   rb.c2 = load_conv_bn(ps, arena, bf16, p + "conv2.weight", p + "bn2");
   rb.has_sc = has_sc;
-  if (has_sc) rb.sc = load_conv_bn(ps, arena, bf16, p + "shortcut.0.weight", p + "shortcut.1");
+  if (has_sc) rb.sc = load_conv_bn(ps, arena, bf16, p + sc_key + ".0.weight", p + sc_key + ".1");
   return rb;
 }
 
 float* run_res_block(const ResBlockL& rb, float* const bufs[3], float* cur, bool bf, int B, int& H, int& W, int sw,
                      const std::function<bool(const ConvGemmArgs& p, float* t2)>& conv1,
-                     const std::function<void(ConvGemmArgs& r)>& conv2, hipStream_t st) {
+                     const std::function<void(ConvGemmArgs& r)>& conv2, hipStream_t st, const ResBlockIO& io) {
   float* others[2];
   int k = 0;
   for (int i = 0; i < 3; ++i) if (bufs[i] != cur) others[k++] = bufs[i];
@@ -92,12 +93,23 @@ float* run_res_block(const ResBlockL& rb, float* const bufs[3], float* cur, bool
     outb = cur;   // the block's input is no longer needed
   }
   ConvGemmArgs r = conv2d(Tens{t1, bf}, B, p.Ho, p.Wo, rb.c2, 1, 1, 1, 1, Tens{outb, bf});
-  r.res = res; r.res_bf16 = bf; r.res_ld = rb.c2.w.N;
-  r.act = kActRelu;
-  conv2(r);
   H = p.Ho;
   W = p.Wo;
-  return outb;
+  if (rb.simam) {
+    conv2(r);   // Y = bn2(conv2(.)) alone
+    SimamArgs g;
+    g.y = outb; g.res = res; g.bf16 = bf; g.B = B; g.H = H; g.W = W; g.C = r.N;
+    g.out = outb; g.o_sb = r.o_sb; g.o_sh = r.o_sh; g.o_sw = r.o_sw; g.o_sn = r.o_sn;   // in place
+    if (io.out) { g.out = io.out; g.o_sb = io.o_sb; g.o_sh = io.o_sh; g.o_sw = io.o_sw; g.o_sn = io.o_sn; }
+    g.partial = io.simam_partial; g.stat = io.simam_stat;
+    simam_gate(g, st);
+    return static_cast<float*>(g.out);
+  }
+  r.res = res; r.res_bf16 = bf; r.res_ld = rb.c2.w.N;
+  r.act = kActRelu;
+  if (io.out) { r.out = io.out; r.o_sb = io.o_sb; r.o_sh = io.o_sh; r.o_sw = io.o_sw; r.o_sn = io.o_sn; }
+  conv2(r);
+  return static_cast<float*>(r.out);
 }
 
 // ------------------------------------------------------------------------------ CamTrunk

@@ -33,23 +33,34 @@ ConvGemmArgs conv2d(Tens in, int B, int H, int W, const ConvL& L, int sh, int sw
 ConvL load_conv_bn(ParamStore& ps, DeviceArena& arena, bool bf16, const std::string& wname,
                    const std::string& bn, const std::string& bias = "");
 
-// BasicResBlock of the CAM++ FCM head (cam_pplus_wespeaker.py:236-268) and of the ResNet34 trunk
-// (resnet_wespeaker.py:35-67): conv3x3 + BN + ReLU, conv3x3 + BN, + (1x1 conv + BN shortcut | input), ReLU.
+// BasicResBlock of the CAM++ FCM head (cam_pplus_wespeaker.py:236-268), of the ResNet34 trunk
+// (resnet_wespeaker.py:35-67) and, with `simam`, of SimAM-ResNet34 (samresnet_wespeaker.py:21-70): conv3x3 + BN +
+// ReLU, conv3x3 + BN [SimAM gate], + (1x1 conv + BN shortcut | input), ReLU.
 struct ResBlockL {
   ConvL c1, c2, sc;
   bool has_sc = false;
   int stride = 1;
+  bool simam = false;
 };
-// Reads `p`{conv1.weight, bn1, conv2.weight, bn2} and, with has_sc, `p`{shortcut.0.weight, shortcut.1}.
-ResBlockL load_res_block(ParamStore& ps, DeviceArena& arena, bool bf16, const std::string& p, int stride, bool has_sc);
+// Reads `p`{conv1.weight, bn1, conv2.weight, bn2} and, with has_sc, `p`{<sc_key>.0.weight, <sc_key>.1}.
+ResBlockL load_res_block(ParamStore& ps, DeviceArena& arena, bool bf16, const std::string& p, int stride, bool has_sc,
+                         const std::string& sc_key = "shortcut");
+// Where a block's output goes instead of a rotating buffer: element strides of (b, h, w, c); the map's type follows
+// the trunk's precision.  simam_partial / simam_stat: the SimAM blocks' scratch (SimamArgs), unused by plain blocks.
+struct ResBlockIO {
+  float* out = nullptr;
+  int64_t o_sb = 0, o_sh = 0, o_sw = 0, o_sn = 1;
+  void *simam_partial = nullptr, *simam_stat = nullptr;
+};
 // One block over the (B, H, W, C) map in `cur`, one of the three rotating buffers; H / W become the output map's
-// and the buffer that holds it is returned.  sw: conv1's and the shortcut's stride along W (rb.stride along H).
-// The trunk chooses the kernels: conv1(p, t2) launches conv1 + BN + ReLU and returns whether it also wrote the
-// shortcut branch to t2 (else conv_gemm computes it); conv2(r) launches conv2 + BN + residual + ReLU and may
-// redirect r's output first.
+// and the buffer that holds it is returned (io.out when that is set).  sw: conv1's and the shortcut's stride along W
+// (rb.stride along H).  The trunk chooses the kernels: conv1(p, t2) launches conv1 + BN + ReLU and returns whether it
+// also wrote the shortcut branch to t2 (else conv_gemm computes it); conv2(r) launches conv2 + BN and r's epilogue:
+// + residual + ReLU, or for a SimAM block nothing (the gate, the residual and the ReLU follow in simam_gate).
 float* run_res_block(const ResBlockL& rb, float* const bufs[3], float* cur, bool bf, int B, int& H, int& W, int sw,
                      const std::function<bool(const ConvGemmArgs& p, float* t2)>& conv1,
-                     const std::function<void(ConvGemmArgs& r)>& conv2, hipStream_t st);
+                     const std::function<void(ConvGemmArgs& r)>& conv2, hipStream_t st,
+                     const ResBlockIO& io = ResBlockIO());
 
 class CamTrunk {
  public:

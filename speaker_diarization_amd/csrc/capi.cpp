@@ -17,6 +17,7 @@
 #include "tsvad.h"
 #include "campp.h"
 #include "resemb.h"
+#include "simam_emb.h"
 #include "ecapa.h"
 #include "tsvad_stream.h"
 #include "ssnd.h"
@@ -41,6 +42,7 @@ struct sd_fseend : Handle<sd::FsEendModel> {};
 struct sd_fseend_stream : Handle<sd::FsEendStream> {};
 struct sd_campp : Handle<sd::CamppModel> {};
 struct sd_resnet34 : Handle<sd::ResEmbModel> {};
+struct sd_simam_resnet34 : Handle<sd::SimamEmbModel> {};
 struct sd_ecapa : Handle<sd::EcapaModel> {};
 struct sd_ssnd : Handle<sd::SsndModel> {};
 
@@ -581,6 +583,51 @@ int64_t sd_resnet34_device_bytes(const sd_resnet34* h) { return device_bytes(h);
 
 int sd_resnet34_destroy(sd_resnet34* h) { return destroy(h); }
 
+int sd_simam_resnet34_create(const sd_simam_resnet34_config* c, sd_simam_resnet34** out) {
+  return guard([&] {
+    SD_CHECK(c && out, sd::kErrInvalid, "null argument");
+    SD_CHECK(c->precision == 0 || c->precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    SD_CHECK(c->in_planes == 64 && c->acoustic_dim == 80, sd::kErrInvalid,
+             "SimAM_ResNet34_ASP (MI355X backend) supports in_planes 64 and acoustic_dim 80 only");
+    SD_CHECK(c->embed_dim >= 8 && c->embed_dim % 8 == 0, sd::kErrInvalid, "embed_dim must be a positive multiple of 8");
+    SD_CHECK(c->max_batch > 0 && c->max_frames >= 8, sd::kErrInvalid, "bad workspace sizes");
+    sd::SimamEmbConfig t;
+    t.in_planes = c->in_planes;
+    t.embed_dim = c->embed_dim;
+    t.acoustic_dim = c->acoustic_dim;
+    t.max_batch = c->max_batch;
+    t.max_frames = c->max_frames;
+    t.bf16 = c->precision == 1;
+    create(out, false, t);
+  });
+}
+
+int sd_simam_resnet34_set_param(sd_simam_resnet34* h, const char* name, const float* data, const int64_t* shape,
+                                int ndim) {
+  return set_param(h, name, data, shape, ndim);
+}
+
+int sd_simam_resnet34_finalize(sd_simam_resnet34* h) { return finalize(h); }
+
+int sd_simam_resnet34_forward(sd_simam_resnet34* h, const float* feats, int B, int T, float* emb, float* front_out,
+                              void* stream) {
+  return guard([&] {
+    SD_CHECK(h && feats && (emb || front_out), sd::kErrInvalid, "null argument");
+    h->model->forward(feats, B, T, emb, front_out, S(stream));
+  });
+}
+
+int sd_debug_simam_variant(int variant) {
+  return guard([&] {
+    SD_CHECK(variant == 0 || variant == 1, sd::kErrInvalid, "simam variant must be 0 or 1");
+    sd::simam_debug_variant(variant);
+  });
+}
+
+int64_t sd_simam_resnet34_device_bytes(const sd_simam_resnet34* h) { return device_bytes(h); }
+
+int sd_simam_resnet34_destroy(sd_simam_resnet34* h) { return destroy(h); }
+
 int sd_ecapa_create(const sd_ecapa_config* c, sd_ecapa** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
@@ -818,6 +865,49 @@ int sd_op_astp_pool(const void* x, int x_bf16, int B, int T, const float* w1, co
     a.ctx = static_cast<float*>(ctx.p); a.cv = static_cast<float*>(cv.p); a.x32 = static_cast<float*>(x32.p);
     a.h = static_cast<float*>(hh.p); a.e = static_cast<float*>(e.p);
     sd::astp_pool(a, st);
+  });
+}
+
+int sd_op_asp_pool(const void* x, int x_bf16, int B, int T, int C, const float* w1, const float* b1, const float* bn_s,
+                   const float* bn_h, const float* w2, const float* b2, float* stats, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && w1 && b1 && bn_s && bn_h && w2 && b2 && stats && B >= 1 && T >= 1 && C >= 64 && C % 64 == 0,
+             sd::kErrInvalid, "asp_pool: bad argument");
+    constexpr int H = 128;
+    const size_t rows = (size_t)B * T;
+    Scratch w1p((size_t)H * C * 4, st), w2p((size_t)C * H * 4, st);
+    sd::pack_weight(w1, H, C, 1, w1p.p, false, st);
+    sd::pack_weight(w2, C, H, 1, w2p.p, false, st);
+    const size_t gemm_rows = std::max<size_t>(rows, sd::kAspMinRows);
+    Scratch x32(x_bf16 ? rows * C * 4 : 4, st), hh(gemm_rows * H * 4, st), e(gemm_rows * C * 4, st);
+    sd::AspArgs a;
+    a.x = x; a.x_bf16 = x_bf16 != 0; a.B = B; a.T = T; a.C = C;
+    a.w1 = w1p.p; a.b1 = b1; a.bn_s = bn_s; a.bn_h = bn_h; a.w2 = w2p.p; a.b2 = b2; a.stats = stats;
+    a.x32 = static_cast<float*>(x32.p); a.h = static_cast<float*>(hh.p); a.e = static_cast<float*>(e.p);
+    sd::asp_pool(a, st);
+  });
+}
+
+int sd_op_simam(const void* y, const void* residual, int dtype, int B, int H, int W, int C, void* out, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(y && out && (dtype == 0 || dtype == 1) && B >= 1 && H >= 1 && W >= 1 && C >= 64 && C % 64 == 0,
+             sd::kErrInvalid, "simam: bad argument");
+    Scratch partial((size_t)B * sd::simam_tiles(H * W) * C * 24, st), stat((size_t)B * C * 16, st);
+    sd::SimamArgs a;
+    a.y = y; a.res = residual; a.bf16 = dtype == 1; a.B = B; a.H = H; a.W = W; a.C = C;
+    a.out = out; a.o_sb = (int64_t)H * W * C; a.o_sh = (int64_t)W * C; a.o_sw = C; a.o_sn = 1;
+    a.partial = partial.p; a.stat = stat.p;
+    sd::simam_gate(a, st);
+  });
+}
+
+int sd_op_stem_conv(const float* fbank, int B, int T, int F, const float* w, const float* alpha, const float* beta,
+                    int C, void* out, int out_bf16, void* stream) {
+  return guard([&] {
+    SD_CHECK(fbank && w && alpha && beta && out && B >= 1 && T >= 1 && F >= 1, sd::kErrInvalid, "stem_conv: bad argument");
+    sd::fcm_conv1(fbank, B, T, F, w, alpha, beta, out, out_bf16 != 0, S(stream), C);
   });
 }
 

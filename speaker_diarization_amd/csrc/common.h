@@ -54,6 +54,12 @@ __device__ __forceinline__ uint16_t f2bf_bits(float f) {
   return (uint16_t)(u >> 16);
 }
 
+// ReLU as torch.relu: negative (and -0, -Inf) -> 0, NaN and +Inf pass (fmaxf would drop the NaN).
+__device__ __forceinline__ float relu_keep_nan(float v) {
+  const uint32_t u = __float_as_uint(v);
+  return (u >= 0x80000000u && u <= 0xff800000u) ? 0.f : v;
+}
+
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));

@@ -14,6 +14,8 @@
 //
 // All maps are channel-last (B, T, C) rows, fp32 or bf16 bits; every kernel addresses a window's frames through its
 // own (b, t), so a tile never reads another window's frames.
+#include <algorithm>
+
 #include "common.h"
 #include "kernels.h"
 #include "prof.h"
@@ -249,11 +251,14 @@ __global__ __launch_bounds__(256) void astp_tanh_kernel(float* __restrict__ h, c
 }
 
 // Softmax over time per (window, channel) of the scores e, then the weighted statistics in fp64:
-// stats (B, 2 C) = [sum_t a x | sqrt(max(sum_t a x^2 - mean^2, 1e-7))], a = softmax_t(e).
-template <bool BF>
+// stats (B, 2 C) = [m = sum_t a x | sqrt(max(var, clamp))], a = softmax_t(e).  ASTP: var = sum_t a x^2 - m^2, clamp 1e-7.
+// ASP (CENTRED): var = sum_t a (x - m)^2 in a second pass over the (L2-resident) rows, clamp the fp32 1e-5: the
+// difference of squares keeps 1e-10 absolute in fp64 at a mean of 1000, which is the whole variance of a channel of
+// std 0.01 to five digits only; the centred sum is exact for a constant channel and for T == 1.
+template <bool BF, bool CENTRED>
 __global__ __launch_bounds__(256) void astp_softmax_stats_kernel(const act_t<BF>* __restrict__ x,
                                                                  const float* __restrict__ e, int T, int C,
-                                                                 float* __restrict__ stats) {
+                                                                 double clamp, float* __restrict__ stats) {
   __shared__ double red[3][4][64];
   __shared__ float redm[4][64];
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6, b = blockIdx.y;
@@ -276,13 +281,25 @@ __global__ __launch_bounds__(256) void astp_softmax_stats_kernel(const act_t<BF>
   red[1][g][lane] = s1;
   red[2][g][lane] = s2;
   __syncthreads();
+  const double w = red[0][0][lane] + red[0][1][lane] + red[0][2][lane] + red[0][3][lane];
+  const double m = (red[1][0][lane] + red[1][1][lane] + red[1][2][lane] + red[1][3][lane]) / w;
+  double var = (red[2][0][lane] + red[2][1][lane] + red[2][2][lane] + red[2][3][lane]) / w - m * m;
+  if constexpr (CENTRED) {
+    __syncthreads();   // every wave has read the first pass's sums
+    double sc = 0.0;
+    for (int t = g; t < T; t += 4) {
+      const double d = (double)ld_act(x, base + (int64_t)t * C) - m;
+      sc += exp((double)(e[base + (int64_t)t * C] - mx)) * d * d;
+    }
+    red[2][g][lane] = sc;
+    __syncthreads();
+    var = (red[2][0][lane] + red[2][1][lane] + red[2][2][lane] + red[2][3][lane]) / w;
+  }
   if (g == 0) {
-    const double w = red[0][0][lane] + red[0][1][lane] + red[0][2][lane] + red[0][3][lane];
-    const double m = (red[1][0][lane] + red[1][1][lane] + red[1][2][lane] + red[1][3][lane]) / w;
-    const double q = (red[2][0][lane] + red[2][1][lane] + red[2][2][lane] + red[2][3][lane]) / w;
-    const double var = q - m * m;
     stats[(int64_t)b * 2 * C + c] = (float)m;
-    stats[(int64_t)b * 2 * C + C + c] = (float)sqrt(var > 1e-7 ? var : 1e-7);
+    // ASP keeps a NaN variance, as torch.clamp does; ASTP's expression clamps it, as it always has
+    const double cl = CENTRED ? (var < clamp ? clamp : var) : (var > clamp ? var : clamp);
+    stats[(int64_t)b * 2 * C + C + c] = (float)sqrt(cl);
   }
 }
 
@@ -398,14 +415,55 @@ void astp_pool(const AstpArgs& a, hipStream_t st) {
   ConvGemmArgs p = linear_args(a.h, (int)rows, H, H, a.w2, C, a.e, C);
   p.beta = a.b2;
   conv_gemm(p, false, st);
-  ProfScope prof("astp_softmax_stats", 0.0, (double)rows * C * 2.0 * ((a.x_bf16 ? 2.0 : 4.0) + 4.0), st);
-  if (a.x_bf16)
-    hipLaunchKernelGGL(astp_softmax_stats_kernel<true>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(a.x), a.e,
-                       a.T, C, a.stats);
+  softmax_stats(a.x, a.x_bf16, a.e, a.B, a.T, C, false, a.stats, st);
+}
+
+void softmax_stats(const void* x, bool x_bf16, const float* e, int B, int T, int C, bool asp, float* stats,
+                   hipStream_t st) {
+  SD_CHECK(x && e && stats && B >= 1 && B <= 65535 && T >= 1 && C >= 64 && C % 64 == 0, kErrInvalid,
+           "softmax_stats: C must be a multiple of 64, 1 <= B <= 65535, T >= 1");
+  const dim3 grid(C / 64, B);
+  ProfScope prof("astp_softmax_stats", 0.0, (double)B * T * C * 2.0 * ((x_bf16 ? 2.0 : 4.0) + 4.0), st);
+  // ASP's clamp is the fp32 constant the reference's float tensors see, so T == 1 gives its sqrt(1e-5) bit for bit
+  const double clamp = asp ? (double)1e-5f : 1e-7;
+  const uint16_t* xb = static_cast<const uint16_t*>(x);
+  const float* xf = static_cast<const float*>(x);
+  if (x_bf16 && asp)
+    hipLaunchKernelGGL((astp_softmax_stats_kernel<true, true>), grid, dim3(256), 0, st, xb, e, T, C, clamp, stats);
+  else if (x_bf16)
+    hipLaunchKernelGGL((astp_softmax_stats_kernel<true, false>), grid, dim3(256), 0, st, xb, e, T, C, clamp, stats);
+  else if (asp)
+    hipLaunchKernelGGL((astp_softmax_stats_kernel<false, true>), grid, dim3(256), 0, st, xf, e, T, C, clamp, stats);
   else
-    hipLaunchKernelGGL(astp_softmax_stats_kernel<false>, grid, dim3(256), 0, st, static_cast<const float*>(a.x), a.e,
-                       a.T, C, a.stats);
+    hipLaunchKernelGGL((astp_softmax_stats_kernel<false, false>), grid, dim3(256), 0, st, xf, e, T, C, clamp, stats);
   SD_LAUNCH_CHECK();
+}
+
+void asp_pool(const AspArgs& a, hipStream_t st) {
+  constexpr int H = 128;
+  SD_CHECK(a.x && a.w1 && a.b1 && a.bn_s && a.bn_h && a.w2 && a.b2 && a.stats && a.h && a.e, kErrInvalid,
+           "asp_pool: null argument");
+  SD_CHECK(a.B >= 1 && a.B <= 65535 && a.T >= 1 && a.C >= 64 && a.C % 64 == 0, kErrInvalid,
+           "asp_pool: C must be a multiple of 64, 1 <= B <= 65535, T >= 1");
+  SD_CHECK(!a.x_bf16 || a.x32, kErrInvalid, "asp_pool: a bf16 map needs the fp32 scratch copy");
+  const int64_t rows = (int64_t)a.B * a.T;
+  SD_CHECK(rows * a.C < (1ll << 31), kErrInvalid, "asp_pool: map out of range");
+  const float* x32 = static_cast<const float*>(a.x);
+  if (a.x_bf16) {
+    bf16_to_f32(a.x, rows * a.C, a.x32, st);
+    x32 = a.x32;
+  }
+  // attention.0 -> ReLU -> attention.2 (BatchNorm1d AFTER the ReLU: the post-activation affine, never folded)
+  ConvGemmArgs p = linear_args(x32, (int)rows, a.C, a.C, a.w1, H, a.h, H);
+  p.beta = a.b1; p.act = kActRelu; p.post_scale = a.bn_s; p.post_shift = a.bn_h;
+  conv_gemm(p, false, st);
+  // attention.3, on at least kAspMinRows rows (h and e hold that many; the surplus rows are scratch nobody reads):
+  // conv_gemm hands <= 16 rows to the skinny kernel, whose sums are ordered differently, and a chunk's embedding must
+  // not depend on how many chunks share the call
+  ConvGemmArgs q = linear_args(a.h, (int)std::max<int64_t>(rows, kAspMinRows), H, H, a.w2, a.C, a.e, a.C);
+  q.beta = a.b2;
+  conv_gemm(q, false, st);
+  softmax_stats(a.x, a.x_bf16, a.e, a.B, a.T, a.C, true, a.stats, st);
 }
 
 }  // namespace sd

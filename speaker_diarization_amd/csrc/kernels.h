@@ -117,7 +117,7 @@ struct FcmFuse {
 bool fcm_fused_supported(const ConvGemmArgs& p, const FcmFuse& f);
 void conv_fcm3x3_fused(const ConvGemmArgs& p, const FcmFuse& f, hipStream_t st);
 // ResNet34 trunk 3x3 convs (res_conv.hip): bf16 NHWC in, pad 1, stride 1 or 2 in BOTH axes, Cin / Cout in
-// {32, 64, 128, 256}, folded BN + optional bf16 residual + ReLU (NaN kept), bf16 out (NHWC as 16-B stores, or any
+// {32, 64, 128, 256, 512}, folded BN + optional bf16 residual + ReLU (NaN kept), bf16 out (NHWC as 16-B stores, or any
 // o_s* strides per element).  ResFuse: the block's 1x1 shortcut at the same stride (+ its BN, no ReLU) from the
 // centre tap's staged pixels, stored NHWC to sc_out.
 struct ResFuse {
@@ -150,9 +150,10 @@ ConvGemmArgs linear_args(const void* A, int M, int K, int lda, const void* Wt, i
 
 // ---------------------------------------------------------------- fcm / cam++
 // First FCM conv (Cin = 1, 3x3, pad 1) + folded BN + ReLU.  fbank (B, T, F) ->
-// NHWC (B, F, T, 32).  cam_pplus_wespeaker.py:277-301.
-void fcm_conv1(const float* fbank, int B, int T, int F, const float* w /*32x9*/,
-               const float* alpha, const float* beta, void* out, bool out_bf16, hipStream_t st);
+// NHWC (B, F, T, C), C = 32 (cam_pplus_wespeaker.py:277-301, the ResNet34 stem) or 64 (the SimAM-ResNet34 stem,
+// samresnet_wespeaker.py:82-85, 118).
+void fcm_conv1(const float* fbank, int B, int T, int F, const float* w /*Cx9*/,
+               const float* alpha, const float* beta, void* out, bool out_bf16, hipStream_t st, int C = 32);
 
 // CAMLayer context gate (cam_pplus_wespeaker.py:106-123):
 // ctx[b,s,c] = mean_t x[b,t,c] + mean_{t in seg s} x[b,t,c];
@@ -248,6 +249,49 @@ struct AstpArgs {
   float *x32 = nullptr, *h = nullptr, *e = nullptr;   // scratch (B T, 1536) (bf16 x only), (B T, 128), (B T, 1536)
 };
 void astp_pool(const AstpArgs& a, hipStream_t st);
+// The pooling both attentive heads end with: a = softmax over T of the scores e (B, T, C) fp32, then in fp64 and a
+// fixed order stats (B, 2 C) = [m = sum_t a x | sqrt(max(var, clamp))] over x (B, T, C) channel-last, C % 64 == 0.
+// ASTP (asp false): var = sum_t a x^2 - m^2, clamp 1e-7.  ASP: var = sum_t a (x - m)^2, clamp the fp32 1e-5; T == 1
+// gives weight 1, m = x and the second half sqrt(1e-5) exactly, and a NaN variance stays NaN (torch.clamp keeps it).
+void softmax_stats(const void* x, bool x_bf16, const float* e, int B, int T, int C, bool asp, float* stats,
+                   hipStream_t st);
+// ASP (pooling_layers_wespeaker.py:146-168) over x (B, T, C) channel-last: e = W2 bn(relu(W1 x + b1)) + b2 on the
+// exact fp32 GEMM (bf16x3 under a GemmX3Scope) whatever x's type, the BatchNorm1d as the post-activation affine
+// (bn_s, bn_h), then softmax_stats with the clamp 1e-5.  Unlike ASTP there is no global context and T == 1 is valid.
+struct AspArgs {
+  const void* x = nullptr;
+  bool x_bf16 = false;
+  int B = 0, T = 0, C = 0;
+  const void* w1 = nullptr;    // packed fp32 [128][C]: attention.0.weight
+  const float* b1 = nullptr;
+  const float *bn_s = nullptr, *bn_h = nullptr;   // attention.2 folded
+  const void* w2 = nullptr;    // packed fp32 [C][128]: attention.3.weight
+  const float* b2 = nullptr;
+  float* stats = nullptr;      // (B, 2 C)
+  // scratch (B T, C) (bf16 x only), (R, 128), (R, C) with R = max(B T, kAspMinRows)
+  float *x32 = nullptr, *h = nullptr, *e = nullptr;
+};
+constexpr int kAspMinRows = 17;
+void asp_pool(const AspArgs& a, hipStream_t st);
+
+// ---------------------------------------------------------------- simam (simam.hip)
+// SimAM gate + shortcut + ReLU of a SimAM BasicBlock (samresnet_wespeaker.py:57-70) on an NHWC map y (B, H, W, C),
+// bf16 or fp32, C % 64 == 0: out = relu(y * sigmoid((y - mean)^2 / (4 (v + 1e-4)) + 0.5) + res), mean and v = sum (y -
+// mean)^2 / (H W - 1) per (b, c) in fp64 and a fixed order (no atomics; an item's result does not depend on the
+// batch), NaN kept in its channel.  res: NHWC like y, or null.  out: y's type at element strides o_s* of (b, h, w, c);
+// NHWC strides may alias y.  partial: scratch of B * simam_tiles(H W) * C records of (n, mean, M2) doubles (24 bytes),
+// item b's records at b times the per-item size; stat: scratch of B * C * 16 bytes.
+struct SimamArgs {
+  const void* y = nullptr;
+  const void* res = nullptr;
+  bool bf16 = false;
+  int B = 0, H = 0, W = 0, C = 0;
+  void* out = nullptr;
+  int64_t o_sb = 0, o_sh = 0, o_sw = 0, o_sn = 1;
+  void *partial = nullptr, *stat = nullptr;
+};
+int simam_tiles(int HW);
+void simam_gate(const SimamArgs& a, hipStream_t st);
 
 // ---------------------------------------------------------------- norms
 // y = LN(x) * g + b over the last dim D; rows of x at stride ldx, y at ldy.

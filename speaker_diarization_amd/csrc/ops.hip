@@ -20,16 +20,16 @@ ConvGemmArgs linear_args(const void* A, int M, int K, int lda, const void* Wt, i
 }
 
 // ------------------------------------------------------------------ FCM stem
-template <bool OBF>
+template <bool OBF, int C>
 __global__ __launch_bounds__(256) void fcm_conv1_kernel(const float* __restrict__ fb, int B, int T,
                                                         int F, const float* __restrict__ w,
                                                         const float* __restrict__ alpha,
                                                         const float* __restrict__ beta,
                                                         void* __restrict__ out) {
-  __shared__ float ws[32 * 9];
-  __shared__ float al[32], be[32];
-  for (int i = threadIdx.x; i < 32 * 9; i += blockDim.x) ws[i] = w[i];
-  if (threadIdx.x < 32) { al[threadIdx.x] = alpha[threadIdx.x]; be[threadIdx.x] = beta[threadIdx.x]; }
+  __shared__ float ws[C * 9];
+  __shared__ float al[C], be[C];
+  for (int i = threadIdx.x; i < C * 9; i += blockDim.x) ws[i] = w[i];
+  if (threadIdx.x < C) { al[threadIdx.x] = alpha[threadIdx.x]; be[threadIdx.x] = beta[threadIdx.x]; }
   __syncthreads();
   int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t total = (int64_t)B * F * T;
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void fcm_conv1_kernel(const float* __restrict_
       x[i * 3 + j] = (ff >= 0 && ff < F && tt >= 0 && tt < T) ? fb[((int64_t)b * T + tt) * F + ff] : 0.f;
     }
 #pragma unroll
-  for (int c8 = 0; c8 < 4; ++c8) {
+  for (int c8 = 0; c8 < C / 8; ++c8) {
     float v[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -63,25 +63,34 @@ __global__ __launch_bounds__(256) void fcm_conv1_kernel(const float* __restrict_
       pk.y = (uint32_t)f2bf_bits(v[2]) | ((uint32_t)f2bf_bits(v[3]) << 16);
       pk.z = (uint32_t)f2bf_bits(v[4]) | ((uint32_t)f2bf_bits(v[5]) << 16);
       pk.w = (uint32_t)f2bf_bits(v[6]) | ((uint32_t)f2bf_bits(v[7]) << 16);
-      reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(out) + idx * 32)[c8] = pk;
+      reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(out) + idx * C)[c8] = pk;
     } else {
-      float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + idx * 32);
+      float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + idx * C);
       o[2 * c8] = make_float4(v[0], v[1], v[2], v[3]);
       o[2 * c8 + 1] = make_float4(v[4], v[5], v[6], v[7]);
     }
   }
 }
 
-void fcm_conv1(const float* fbank, int B, int T, int F, const float* w, const float* alpha,
-               const float* beta, void* out, bool out_bf16, hipStream_t st) {
-  int64_t total = (int64_t)B * F * T;
-  ProfScope prof("fcm_conv1", 2.0 * total * 32 * 9, 4.0 * total * 33, st);
+template <int C>
+static void launch_fcm_conv1(const float* fbank, int B, int T, int F, const float* w, const float* alpha,
+                             const float* beta, void* out, bool out_bf16, hipStream_t st) {
+  const int64_t total = (int64_t)B * F * T;
+  const dim3 grid((unsigned)cdiv((int)total, 256));
   if (out_bf16)
-    hipLaunchKernelGGL(fcm_conv1_kernel<true>, dim3((unsigned)cdiv((int)total, 256)), dim3(256), 0, st,
-                       fbank, B, T, F, w, alpha, beta, out);
+    hipLaunchKernelGGL((fcm_conv1_kernel<true, C>), grid, dim3(256), 0, st, fbank, B, T, F, w, alpha, beta, out);
   else
-    hipLaunchKernelGGL(fcm_conv1_kernel<false>, dim3((unsigned)cdiv((int)total, 256)), dim3(256), 0, st,
-                       fbank, B, T, F, w, alpha, beta, out);
+    hipLaunchKernelGGL((fcm_conv1_kernel<false, C>), grid, dim3(256), 0, st, fbank, B, T, F, w, alpha, beta, out);
+}
+
+void fcm_conv1(const float* fbank, int B, int T, int F, const float* w, const float* alpha,
+               const float* beta, void* out, bool out_bf16, hipStream_t st, int C) {
+  SD_CHECK(C == 32 || C == 64, kErrInvalid, "fcm_conv1: 32 or 64 output channels");
+  const int64_t total = (int64_t)B * F * T;
+  SD_CHECK(total > 0 && total < (1ll << 31), kErrInvalid, "fcm_conv1: map out of range");
+  ProfScope prof("fcm_conv1", 2.0 * total * C * 9, 4.0 * total * (C + 1), st);
+  if (C == 32) launch_fcm_conv1<32>(fbank, B, T, F, w, alpha, beta, out, out_bf16, st);
+  else launch_fcm_conv1<64>(fbank, B, T, F, w, alpha, beta, out, out_bf16, st);
   SD_LAUNCH_CHECK();
 }
 

@@ -1,5 +1,5 @@
 // ResNet34 trunk 3x3 convolutions (resnet_wespeaker.py BasicBlock) for gfx950: bf16 NHWC maps, pad 1, stride 1
-// or 2 in BOTH axes, Cin / Cout in {32, 64, 128, 256}, fp32 accumulation on v_mfma_f32_16x16x32_bf16.
+// or 2 in BOTH axes, Cin / Cout in {32, 64, 128, 256, 512}, fp32 accumulation on v_mfma_f32_16x16x32_bf16.
 //
 // A workgroup (4 waves) owns an output patch of TH x TW <= 128 pixels (chosen per map so that narrow maps still
 // fill their tiles, res_geom below) times NT = 32 or 64 output channels, and walks Cin in slabs of 32 channels:
@@ -50,12 +50,6 @@ template <int S>
 constexpr int res_max_pos() { return res_xper<S>() * kThreads / 4; }
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// ReLU as torch.relu: negative (and -0, -Inf) -> 0, NaN and +Inf pass (fmaxf would drop the NaN).
-__device__ __forceinline__ float relu_keep_nan(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u >= 0x80000000u && u <= 0xff800000u) ? 0.f : v;
-}
 
 template <int WM, int WN, int PB, int S, bool SC>
 __global__ __launch_bounds__(kThreads) void res_conv_kernel(ConvGemmArgs p, ResFuse f, ResGeom g) {
@@ -299,7 +293,8 @@ void launch_res(const ConvGemmArgs& p, const ResFuse& f, hipStream_t st) {
   hipLaunchKernelGGL((res_conv_kernel<WM, WN, PB, S, SC>), dim3((unsigned)blocks), dim3(kThreads), smem, st, p, f, g);
 }
 
-bool res_chan_ok(int c) { return c == 32 || c == 64 || c == 128 || c == 256; }
+// The kernel streams the weights per 32-channel slab, so the width is bounded only by what has been tested.
+bool res_chan_ok(int c) { return c == 32 || c == 64 || c == 128 || c == 256 || c == 512; }
 
 }  // namespace
 
@@ -317,7 +312,9 @@ bool res_conv_runs(const ConvGemmArgs& p) {
 // (tools/res_conv_probe.py at B = 64): the stride-1 convs of stages 2-4 and the stage-2
 // opener.  Refused, so conv_gemm serves them: 32 -> 32 stride 1 (fcm_conv.hip's ring kernel is 1.4x faster), the
 // stage-3 / stage-4 openers 64 -> 128 and 128 -> 256 at stride 2 (gemm_dma + a separate shortcut launch is 1.3x
-// faster), and every class that was not measured.
+// faster), and every class that was not measured.  The base-64 trunk's classes (SimAM-ResNet34: 64 -> 64 on the 80-row
+// map, 512 -> 512, the 64 -> 128 / 128 -> 256 / 256 -> 512 openers) were measured on their own at B = 96, 598 frames
+//  and the same rule matches that table: every stride-1 class here, every opener to conv_gemm.
 bool res_conv_supported(const ConvGemmArgs& p) {
   if (!res_conv_runs(p)) return false;
   if (p.sh == 1) return p.Cin == p.N && p.Cin >= 64;

@@ -175,6 +175,95 @@ class ResNet34(_lib.Handle):
     __call__ = forward
 
 
+class SimAM_ResNet34_ASP(_lib.Handle):
+    """egs/alimeeting/ts_vad2/samresnet_wespeaker.py:134-160 with speech_encoder=False: the WeSpeaker SimAM-ResNet34
+    embedding extractor (SimAM BasicBlocks at 64/128/256/512 channels, ASP pooling, bottleneck) run by libsdiar
+    (`sd_simam_resnet34_*`).  Same constructor arguments and standalone state_dict keys; forward(x) -> (B, embed_dim).
+    The encoder-only form is not built: the reference's forward(x, get_time_out=True) raises NameError (:150 reads an
+    undefined `out`), so there is no behaviour to reproduce."""
+    kind = "simam_resnet34"
+    _NO_TIME_OUT = ("the reference's SimAM_ResNet34_ASP.forward(x, get_time_out=True) raises NameError "
+                    "(samresnet_wespeaker.py:150 reads an undefined `out`): the encoder-only form is not built")
+
+    def __init__(self, in_planes: int = 64, embed_dim: int = 256, acoustic_dim: int = 80, dropout: float = 0,
+                 speech_encoder: bool = False, *, device=None, precision: str = "bf16", max_batch: int = 96,
+                 max_frames: int = 598):
+        if speech_encoder:
+            raise ValueError("speech_encoder=True builds no pooling head, and " + self._NO_TIME_OUT)
+        if in_planes != 64:
+            raise ValueError(f"the MI355X SimAM_ResNet34_ASP supports in_planes 64 only, got {in_planes}")
+        if acoustic_dim != 80:
+            raise ValueError(f"the MI355X SimAM_ResNet34_ASP supports acoustic_dim 80 only, got {acoustic_dim}")
+        if dropout:
+            raise ValueError("the MI355X SimAM_ResNet34_ASP is inference only (dropout 0, the extractor script's setting)")
+        code = _lib.precision_code(precision, ("bf16", "fp32"))
+        self.device = _lib.hip_device(device, "SimAM_ResNet34_ASP")
+        self.in_planes, self.embed_dim, self.acoustic_dim = in_planes, embed_dim, acoustic_dim
+        self.feat_dim = acoustic_dim
+        self.embedding_size = embed_dim      # what extract_embed sizes its output with
+        self.precision, self.max_batch, self.max_frames = precision, max_batch, max_frames
+        self._create(_lib.SimamResnet34Config(in_planes=in_planes, embed_dim=embed_dim, acoustic_dim=acoustic_dim,
+                                              max_batch=max_batch, max_frames=max_frames, precision=code))
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        if not strict:
+            raise ValueError("the MI355X backend only supports strict=True loading")
+        self._load(unwrap_checkpoint(state_dict, kind="simam_resnet34"))
+        return self
+
+    def eval(self):
+        return self
+
+    def to(self, device):
+        import torch
+        if torch.device(device) != self.device:
+            raise ValueError("re-create the model on the target device")
+        return self
+
+    @property
+    def device_bytes(self) -> int:
+        return self._device_bytes()
+
+    out_frames = staticmethod(ResNet34.out_frames)
+
+    def forward(self, x, get_time_out: bool = False, out=None):
+        """x (B, T, 80) -> (B, embed_dim) (samresnet_wespeaker.py:156-160).  T >= 8 (ValueError below: the trunk's
+        kernels are exercised from 8 frames on); T == 8 gives one pooled frame and finite embeddings."""
+        import torch
+        if get_time_out:
+            raise ValueError(self._NO_TIME_OUT)
+        B, T, F = x.shape
+        if F != self.feat_dim:
+            raise ValueError(f"expected {self.feat_dim}-dim fbank, got {F}")
+        if T < 8:
+            raise ValueError(f"SimAM_ResNet34_ASP needs at least 8 fbank frames, got {T}")
+        x = x.to(self.device, torch.float32).contiguous()
+        if B > self.max_batch:
+            parts = [self.forward(x[s:s + self.max_batch], out=None if out is None else out[s:s + self.max_batch])
+                     for s in range(0, B, self.max_batch)]
+            return out if out is not None else torch.cat(parts)
+        if out is None:
+            out = torch.empty(B, self.embed_dim, device=self.device, dtype=torch.float32)
+        _lib.call("sd_simam_resnet34_forward", self._h, _lib.ptr(x), B, T, _lib.ptr(out), None,
+                  _lib.stream_ptr(self.device))
+        return out
+
+    __call__ = forward
+
+    def front(self, x):
+        """x (B, T, 80) -> the front's map (B, 5120, T') as ASP.forward flattens it (pooling_layers_wespeaker.py:162),
+        channel c * 10 + f: what the pooling head reads (tests and diagnostics)."""
+        import torch
+        B, T, F = x.shape
+        if F != self.feat_dim or T < 8 or B > self.max_batch:
+            raise ValueError("front: (B <= max_batch, T >= 8, 80) fbank expected")
+        x = x.to(self.device, torch.float32).contiguous()
+        fo = torch.empty(B, self.out_frames(T), 5120, device=self.device, dtype=torch.float32)
+        _lib.call("sd_simam_resnet34_forward", self._h, _lib.ptr(x), B, T, None, _lib.ptr(fo),
+                  _lib.stream_ptr(self.device))
+        return fo.permute(0, 2, 1)
+
+
 class ECAPA_TDNN_GLOB_c1024(_lib.Handle):
     """egs/alimeeting/ts_vad2/ecapa_tdnn_wespeaker.py:161-254, 264-271 with speech_encoder=False: ECAPA-TDNN at 1024
     channels with global-context ASTP, bn and linear, run by libsdiar (`sd_ecapa_*`).  Same constructor arguments and

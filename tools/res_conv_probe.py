@@ -1,7 +1,7 @@
 """res_conv probe: sd_op_res_conv with use_generic 0 (res_conv.hip) and 1 (conv_gemm) on the ResNet34 trunk's layer
 shapes of a B = 64, rs_len 4 batch (398 fbank frames).
 
-    python tools/res_conv_probe.py [--batch 64] [--rounds 5] [--reps 5] [--out FILE]
+    python tools/res_conv_probe.py [--batch 64] [--rounds 5] [--reps 5] [--out FILE] [--trunk resnet34|simam]
 Per shape: the stride-1 convs carry the residual, the stride-2 block openers the fused 1x1 shortcut (the generic
 arm runs it as a second conv_gemm).  Kernel time is the library's HIP-event timers (every family the call launched,
 summed), after a warm-up call of both arms; the arms alternate round by round and each arm's spread over the rounds
@@ -21,6 +21,9 @@ from speaker_diarization_amd import _lib  # noqa: E402
 # (H, W, Cin, Cout, stride): the distinct 3x3 convs of ResNet34 on an (80, 398) fbank map
 SHAPES = [(80, 398, 32, 32, 1), (80, 398, 32, 64, 2), (40, 199, 64, 64, 1), (40, 199, 64, 128, 2),
           (20, 100, 128, 128, 1), (20, 100, 128, 256, 2), (10, 50, 256, 256, 1)]
+# --trunk simam: the distinct 3x3 convs of SimAM-ResNet34 (base width 64) on an (80, 598) map, the extractor's 6 s chunk
+SHAPES_SIMAM = [(80, 598, 64, 64, 1), (80, 598, 64, 128, 2), (40, 299, 128, 128, 1), (40, 299, 128, 256, 2),
+                (20, 150, 256, 256, 1), (20, 150, 256, 512, 2), (10, 75, 512, 512, 1)]
 BF16_PEAK_TFLOPS = 2500.0   # dense bf16 MFMA peak of an MI355X
 
 
@@ -81,9 +84,10 @@ if __name__ == "__main__":
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--trunk", choices=("resnet34", "simam"), default="resnet34")
     a = ap.parse_args()
     fh = open(a.out, "w") if a.out else None
-    for shape in SHAPES:
+    for shape in (SHAPES if a.trunk == "resnet34" else SHAPES_SIMAM):
         r = probe(a.batch, *shape, rounds=a.rounds, reps=a.reps)
         line = json.dumps(r)
         print(line, flush=True)
