@@ -259,6 +259,51 @@ int sd_debug_simam_variant(int variant);
 int64_t sd_simam_resnet34_device_bytes(const sd_simam_resnet34* h);
 int sd_simam_resnet34_destroy(sd_simam_resnet34* h);
 
+/* ------------------------------------------------------------------ ERes2NetV2 embeddings
+ * Replaces ERes2NetV2(feat_dim=80, embedding_size=192, m_channels=64, baseWidth, scale, expansion, pooling_func="TSTP",
+ * two_emb_layer=False) (egs/alimeeting/ts_vad2/ERes2NetV2.py:162-255, fusion.py:10-30,
+ * pooling_layers_3d_speaker.py:40-57), the 3D-Speaker extractor
+ * generate_chunk_speaker_embedding_from_modelscope_for_diarization.py:110-136 builds for
+ * iic/speech_eres2netv2w24s4ep4_sv_zh-cn_16k-common (baseWidth 24, scale 4, expansion 4) and runs on 6 s chunks
+ * (:271-300); (26, 2, 2) is the class's default (egs/magicdata-ramc/ots_vad/model.py:496-534).  Parameters under the
+ * reference state_dict names (conv1, bn1, layerN.M.{conv1, bn1, convs.i, bns.i, fuse_models.j.local_att.{0,1,3,4},
+ * conv3, bn3, shortcut.{0,1}}.*, layer3_ds.weight, fuse34.local_att.{0,1,3,4}.*, seg_1.*).  two_emb_layer=True, the
+ * other pooling functions and other size triples are not built. */
+typedef struct sd_eres2netv2 sd_eres2netv2;
+
+typedef struct {
+  int feat_dim;        /* 80 only */
+  int embedding_size;  /* 192 in the recipe; a positive multiple of 8 */
+  int m_channels;      /* 64 only */
+  int base_width;      /* (base_width, scale, expansion) = (26, 2, 2) or (24, 4, 4) */
+  int scale;
+  int expansion;
+  int max_batch;       /* workspace: chunks per forward (extract_embed batch_size 96)      */
+  int max_frames;      /* workspace: fbank frames per chunk (598 for 6 s)                  */
+  int precision;       /* 0: fp32 (exact-f32 MFMA), 1: bf16 trunk (fuse34's blend, TSTP and seg_1 stay fp32) */
+} sd_eres2netv2_config;
+
+/* ERes2NetV2.__init__ (ERes2NetV2.py:163-226); an unsupported field gives SD_ERR_INVALID */
+int sd_eres2netv2_create(const sd_eres2netv2_config* cfg, sd_eres2netv2** out);
+/* load_state_dict (generate_chunk_...modelscope...py:133; strict here) */
+int sd_eres2netv2_set_param(sd_eres2netv2* h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+int sd_eres2netv2_finalize(sd_eres2netv2* h);
+/* ERes2NetV2.forward (ERes2NetV2.py:236-255).  feats: device (B, T, 80) fbank; emb: device (B, embedding_size) or NULL =
+ * seg_1(TSTP(fuse34(out4, layer3_ds(out3)))).  frame_out: device (B, T', 5120 * expansion) channel-last fp32 or NULL:
+ * get_frame_level_feat (egs/magicdata-ramc/ots_vad/ERes2NetV2.py:253-258), the fuse34 map, channel f * C + c (the
+ * reference transposes to (B, T, F, C) and flattens), transposed; frame25_out: device (B, T3, 5120 * expansion) or
+ * NULL: get_frame_level_feat_frame_rate25 (:259-272), out3 in the same order.
+ * T3 = twice, T' = three times (n - 1) / 2 + 1 applied to T.  T == 8 (T' = 1) gives the reference's NaN standard
+ * deviations and an all-NaN embedding.  T < 8 gives SD_ERR_SHAPE. */
+int sd_eres2netv2_forward(sd_eres2netv2* h, const float* feats, int B, int T, float* emb, float* frame_out,
+                          float* frame25_out, void* stream);
+/* Diagnostics (tools/eres2net_probe.py): which bf16 GEMM kernel serves the Hardtanh(0, 20) epilogue from now on.  0 (the
+ * default): the shipped rule; 1: always the register-staged kernel (the first form measured).
+ * Never set in production code. */
+int sd_debug_clamp_route(int route);
+int64_t sd_eres2netv2_device_bytes(const sd_eres2netv2* h);
+int sd_eres2netv2_destroy(sd_eres2netv2* h);
+
 /* ------------------------------------------------------------------ ECAPA-TDNN embeddings
  * Replaces ECAPA_TDNN_GLOB_c1024(feat_dim=80, embed_dim=192, pooling_func="ASTP")
  * (egs/alimeeting/ts_vad2/ecapa_tdnn_wespeaker.py:161-271, pooling_layers_wespeaker.py:91-144) as the target-speaker
@@ -622,6 +667,19 @@ int sd_op_asp_pool(const void* x, int x_bf16, int B, int T, int C, const float* 
  * + residual), mean and v = sum (y - mean)^2 / (H W - 1) per (b, c) in fp64 and a fixed order; residual NHWC like y, or
  * NULL.  A NaN stays in its (b, c) channel; an item's result does not depend on the batch. */
 int sd_op_simam(const void* y, const void* residual, int dtype, int B, int H, int W, int C, void* out, void* stream);
+/* The 3x3 slice conv of an ERes2NetV2 block (ERes2NetV2.py:73-83) on MFMA, bf16: x NHWC (B, H, W, ldx) bf16 bits whose
+ * channels [x_coff, x_coff + width) are the input slice; add (NULL, or a map of row length ld_add) channels [add_coff,
+ * ..) are summed on load; w (width, width, 3, 3), alpha, beta (width) fp32 device arrays; out NHWC (B, H, W, ldo) bf16:
+ * channels [o_coff, o_coff + width) = clamp(alpha conv(x [+ add]) + beta, 0, 20) with NaN kept and +inf -> 20, every
+ * other channel untouched.  width even; offsets and row lengths even (4-byte aligned slices). */
+int sd_op_res2_conv3x3(const void* x, int B, int H, int W, int ldx, int x_coff, int width, const void* add, int ld_add,
+                       int add_coff, const float* w, const float* alpha, const float* beta, void* out, int ldo,
+                       int o_coff, void* stream);
+/* AFF(channels C, r 4) per pixel (fusion.py:10-30): x, y, out (P, C) rows, dtype 0 fp32 / 1 bf16 bits; w1 (I, 2 C),
+ * w2 (C, I) fp32 device arrays; (a1, c1) (I) and (a2, c2) (C) the conv bias + eval BatchNorm folded to scale and
+ * shift.  out = x (1 + tanh att) + y (1 - tanh att), att = a2 (w2 SiLU(a1 (w1 [x | y]) + c1)) + c2, in fp32. */
+int sd_op_aff_gate(const void* x, const void* y, int dtype, int64_t P, int C, int I, const float* w1, const float* a1,
+                   const float* c1, const float* w2, const float* a2, const float* c2, void* out, void* stream);
 /* TS-VAD speaker input through proj_layer (model.py:212-217, 870-876), the stage of configurations with
  * 2 * speaker_embed_dim != transformer_embed_dim: out[(b, spk, t), :] = w [ts[b, spk] | relu(bn(mix[b, t]))] + bias
  * + pe[t], with w (E, 2 SE) split on its input axis (one GEMM over the B * NS embeddings, one over the B * Tmix mix

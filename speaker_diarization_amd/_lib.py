@@ -107,6 +107,20 @@ class SimamResnet34Config(ctypes.Structure):
     ]
 
 
+class Eres2netv2Config(ctypes.Structure):
+    _fields_ = [
+        ("feat_dim", c_int),
+        ("embedding_size", c_int),
+        ("m_channels", c_int),
+        ("base_width", c_int),
+        ("scale", c_int),
+        ("expansion", c_int),
+        ("max_batch", c_int),
+        ("max_frames", c_int),
+        ("precision", c_int),
+    ]
+
+
 class EcapaConfig(ctypes.Structure):
     _fields_ = [
         ("channels", c_int),
@@ -164,6 +178,8 @@ _SIGS = {
     "sd_resnet34_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sd_simam_resnet34_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_debug_simam_variant": (c_int, [c_int]),
+    "sd_eres2netv2_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sd_debug_clamp_route": (c_int, [c_int]),
     "sd_ecapa_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_ecapa_debug_stats": (c_int, [c_void_p, POINTER(c_void_p)]),
     "sd_eda_input_stride": (c_int, [c_void_p]),
@@ -220,6 +236,10 @@ _SIGS = {
     "sd_op_asp_pool": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p]),
     "sd_op_simam": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sd_op_res2_conv3x3": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "sd_op_aff_gate": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p]),
     "sd_op_stem_conv": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                 c_void_p]),
     "sd_op_speaker_input_proj": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
@@ -242,7 +262,7 @@ _SIGS = {
 # -> <the kind's forward calls>* -> destroy, device_bytes at any time.
 KINDS = {"tsvad": TsvadConfig, "tsvad_stream": TsvadStreamConfig, "eda": EdaConfig, "fseend": FseendConfig,
          "campp": CamppConfig, "resnet34": Resnet34Config, "simam_resnet34": SimamResnet34Config,
-         "ecapa": EcapaConfig, "ssnd": SsndConfig}
+         "eres2netv2": Eres2netv2Config, "ecapa": EcapaConfig, "ssnd": SsndConfig}
 for _kind, _conf in KINDS.items():
     _SIGS[f"sd_{_kind}_create"] = (c_int, [POINTER(_conf), POINTER(c_void_p)])
     _SIGS[f"sd_{_kind}_set_param"] = (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int])

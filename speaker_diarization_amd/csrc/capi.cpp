@@ -18,6 +18,7 @@
 #include "campp.h"
 #include "resemb.h"
 #include "simam_emb.h"
+#include "eres2net.h"
 #include "ecapa.h"
 #include "tsvad_stream.h"
 #include "ssnd.h"
@@ -43,6 +44,7 @@ struct sd_fseend_stream : Handle<sd::FsEendStream> {};
 struct sd_campp : Handle<sd::CamppModel> {};
 struct sd_resnet34 : Handle<sd::ResEmbModel> {};
 struct sd_simam_resnet34 : Handle<sd::SimamEmbModel> {};
+struct sd_eres2netv2 : Handle<sd::ERes2NetV2Model> {};
 struct sd_ecapa : Handle<sd::EcapaModel> {};
 struct sd_ssnd : Handle<sd::SsndModel> {};
 
@@ -628,6 +630,58 @@ int64_t sd_simam_resnet34_device_bytes(const sd_simam_resnet34* h) { return devi
 
 int sd_simam_resnet34_destroy(sd_simam_resnet34* h) { return destroy(h); }
 
+int sd_eres2netv2_create(const sd_eres2netv2_config* c, sd_eres2netv2** out) {
+  return guard([&] {
+    SD_CHECK(c && out, sd::kErrInvalid, "null argument");
+    SD_CHECK(c->precision == 0 || c->precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    SD_CHECK(c->feat_dim == 80 && c->m_channels == 64, sd::kErrInvalid,
+             "ERes2NetV2 (MI355X backend) supports feat_dim 80 and m_channels 64 only");
+    SD_CHECK((c->base_width == 26 && c->scale == 2 && c->expansion == 2) ||
+                 (c->base_width == 24 && c->scale == 4 && c->expansion == 4),
+             sd::kErrInvalid,
+             "ERes2NetV2 (MI355X backend) builds (baseWidth, scale, expansion) = (26, 2, 2) or (24, 4, 4) only");
+    SD_CHECK(c->embedding_size >= 8 && c->embedding_size % 8 == 0, sd::kErrInvalid,
+             "embedding_size must be a positive multiple of 8");
+    SD_CHECK(c->max_batch > 0 && c->max_frames >= 8, sd::kErrInvalid, "bad workspace sizes");
+    sd::ERes2NetV2Config t;
+    t.feat_dim = c->feat_dim;
+    t.embedding_size = c->embedding_size;
+    t.m_channels = c->m_channels;
+    t.base_width = c->base_width;
+    t.scale = c->scale;
+    t.expansion = c->expansion;
+    t.max_batch = c->max_batch;
+    t.max_frames = c->max_frames;
+    t.bf16 = c->precision == 1;
+    create(out, false, t);
+  });
+}
+
+int sd_eres2netv2_set_param(sd_eres2netv2* h, const char* name, const float* data, const int64_t* shape, int ndim) {
+  return set_param(h, name, data, shape, ndim);
+}
+
+int sd_eres2netv2_finalize(sd_eres2netv2* h) { return finalize(h); }
+
+int sd_eres2netv2_forward(sd_eres2netv2* h, const float* feats, int B, int T, float* emb, float* frame_out,
+                          float* frame25_out, void* stream) {
+  return guard([&] {
+    SD_CHECK(h && feats && (emb || frame_out || frame25_out), sd::kErrInvalid, "null argument");
+    h->model->forward(feats, B, T, emb, frame_out, frame25_out, S(stream));
+  });
+}
+
+int sd_debug_clamp_route(int route) {
+  return guard([&] {
+    SD_CHECK(route == 0 || route == 1, sd::kErrInvalid, "clamp route must be 0 or 1");
+    sd::clamp_route_debug(route);
+  });
+}
+
+int64_t sd_eres2netv2_device_bytes(const sd_eres2netv2* h) { return device_bytes(h); }
+
+int sd_eres2netv2_destroy(sd_eres2netv2* h) { return destroy(h); }
+
 int sd_ecapa_create(const sd_ecapa_config* c, sd_ecapa** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
@@ -900,6 +954,66 @@ int sd_op_simam(const void* y, const void* residual, int dtype, int B, int H, in
     a.out = out; a.o_sb = (int64_t)H * W * C; a.o_sh = (int64_t)W * C; a.o_sw = C; a.o_sn = 1;
     a.partial = partial.p; a.stat = stat.p;
     sd::simam_gate(a, st);
+  });
+}
+
+namespace {
+// a device fp32 array of n floats on the host (test ops only: synchronises the stream)
+std::vector<float> to_host(const float* d, size_t n, hipStream_t st) {
+  std::vector<float> h(n);
+  SD_HIP(hipStreamSynchronize(st));
+  SD_HIP(hipMemcpy(h.data(), d, n * sizeof(float), hipMemcpyDeviceToHost));
+  return h;
+}
+}  // namespace
+
+int sd_op_res2_conv3x3(const void* x, int B, int H, int W, int ldx, int x_coff, int width, const void* add, int ld_add,
+                       int add_coff, const float* w, const float* alpha, const float* beta, void* out, int ldo,
+                       int o_coff, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && w && alpha && beta && out && width >= 2 && width <= 512, sd::kErrInvalid, "res2_conv3x3: bad argument");
+    const int Cp = sd::res2_padded(width);
+    const std::vector<float> hw = to_host(w, (size_t)width * width * 9, st), ha = to_host(alpha, width, st),
+                             hb = to_host(beta, width, st);
+    std::vector<float> pw((size_t)Cp * 9 * Cp, 0.f), pa(Cp, 0.f), pb(Cp, 0.f);
+    for (int n = 0; n < width; ++n) {
+      pa[n] = ha[n];
+      pb[n] = hb[n];
+      for (int c = 0; c < width; ++c)
+        for (int t = 0; t < 9; ++t) pw[((size_t)n * 9 + t) * Cp + c] = hw[((size_t)n * width + c) * 9 + t];
+    }
+    sd::DeviceArena arena;   // freed once the stream has drained, below
+    const sd::PackedW k = sd::upload_packed(arena, pw, Cp, Cp, 3, 3, true);
+    sd::Res2ConvArgs a;
+    a.x = x; a.ldx = ldx; a.x_coff = x_coff;
+    a.add = add; a.ld_add = ld_add; a.add_coff = add_coff;
+    a.B = B; a.H = H; a.W = W; a.width = width;
+    a.w = k.w; a.alpha = arena.upload(pa); a.beta = arena.upload(pb);
+    a.out = out; a.ldo = ldo; a.o_coff = o_coff;
+    sd::res2_conv3x3(a, st);
+    SD_HIP(hipStreamSynchronize(st));
+  });
+}
+
+int sd_op_aff_gate(const void* x, const void* y, int dtype, int64_t P, int C, int I, const float* w1, const float* a1,
+                   const float* c1, const float* w2, const float* a2, const float* c2, void* out, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && y && out && w1 && a1 && c1 && w2 && a2 && c2 && (dtype == 0 || dtype == 1) && P >= 1 && C >= 2 &&
+                 C % 2 == 0 && C <= 224 && I >= 1 && I <= 52,
+             sd::kErrInvalid, "aff_gate: bad argument");
+    const sd::AffPacked k =
+        sd::aff_pack(to_host(w1, (size_t)I * 2 * C, st).data(), to_host(a1, I, st).data(), to_host(c1, I, st).data(),
+                     to_host(w2, (size_t)C * I, st).data(), to_host(a2, C, st).data(), to_host(c2, C, st).data(), C, I, C);
+    sd::DeviceArena arena;
+    sd::AffGateArgs a;
+    a.x = x; a.ldx = C; a.y = y; a.ldy = C; a.out = out; a.ldo = C;
+    a.bf16 = dtype == 1; a.P = P; a.C = C; a.I = I;
+    a.w1 = arena.upload(k.w1); a.a1 = arena.upload(k.a1); a.c1 = arena.upload(k.c1);
+    a.w2 = arena.upload(k.w2); a.a2 = arena.upload(k.a2); a.c2 = arena.upload(k.c2);
+    sd::aff_gate(a, st);
+    SD_HIP(hipStreamSynchronize(st));
   });
 }
 

@@ -131,13 +131,16 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
 }
 
-enum Act : int { kActNone = 0, kActRelu = 1, kActSigmoid = 2, kActSilu = 3 };
+// kActClamp20: nn.Hardtanh(0, 20) (ERes2NetV2.py:21-24), NaN kept, +inf -> 20.  conv_gemm's exact kernels and, in bf16,
+// the LDS-DMA and the register-staged kernels apply it (conv_gemm_bf16 routes it to one of the two).
+enum Act : int { kActNone = 0, kActRelu = 1, kActSigmoid = 2, kActSilu = 3, kActClamp20 = 4 };
 
 __device__ __forceinline__ float apply_act(float v, int act) {
   switch (act) {
     case kActRelu: return fmaxf(v, 0.f);
     case kActSigmoid: return 1.f / (1.f + expf(-v));
     case kActSilu: return v / (1.f + expf(-v));
+    case kActClamp20: return v < 0.f ? 0.f : (v > 20.f ? 20.f : v);
     default: return v;
   }
 }

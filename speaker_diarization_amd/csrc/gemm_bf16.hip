@@ -276,6 +276,11 @@ void launch(const ConvGemmArgs& p, hipStream_t st) {
 
 }  // namespace
 
+namespace {
+int g_clamp_route = 0;
+}
+void clamp_route_debug(int route) { g_clamp_route = route; }
+
 void conv_gemm_bf16(const ConvGemmArgs& p, hipStream_t st) {
   SD_CHECK(p.K == p.kh * p.kw * p.Cin, kErrInvalid, "conv_gemm: K != kh*kw*Cin");
   SD_CHECK(p.Cin % 8 == 0 && p.K % 8 == 0, kErrInvalid, "conv_gemm(bf16): Cin must be a multiple of 8");
@@ -291,7 +296,9 @@ void conv_gemm_bf16(const ConvGemmArgs& p, hipStream_t st) {
                        (p.res ? (p.res_bf16 ? 2.0 : 4.0) * M * p.N : 0.0);
   // Path selection first, so the live timer (bench.py roofline) is keyed by the kernel that runs.
   enum Path { kFcm, kAreg, kRing, kStream, kDma, kReg } path = kReg;
-  if (p.post_scale)                       // the post-activation affine: the ring GEMM's wide form, or this file's kernel
+  if (p.act == kActClamp20)               // the clamp epilogue: the LDS-DMA kernel and this file's (apply_act at run time)
+    path = (g_clamp_route == 0 && gemm_dma_supported(p)) ? kDma : kReg;
+  else if (p.post_scale)                  // the post-activation affine: the ring GEMM's wide form, or this file's kernel
     path = gemm_ring_supported(p) ? kRing : kReg;
   else if (fcm_conv_supported(p))         // CAM++ FCM 3x3 32->32 convs (fcm_conv.hip)
     path = kFcm;

@@ -92,6 +92,9 @@ struct GemmX3Scope {
   bool prev;
 };
 void conv_gemm_bf16(const ConvGemmArgs& p, hipStream_t st);   // bf16-MFMA production kernel
+// Measurement only (tools/eres2net_probe.py, sd_debug_clamp_route): which bf16 kernel serves act == kActClamp20.  0: the
+// shipped rule (the LDS-DMA kernel where gemm_dma_supported, else the register-staged one); 1: always the latter.
+void clamp_route_debug(int route);
 bool gemm_dma_supported(const ConvGemmArgs& p);               // bf16 A, no prologue, taps==1 or Cin%64==0
 // Split-K: the split count worth using for p on the gemm_dma path (1 = none), and the launch writing
 // ksplit fp32 row-major (M x N) slabs to `slabs` (the consumer sums them, e.g. add_layernorm's t_slabs).
@@ -195,8 +198,10 @@ void stats_pool(const void* x, bool x_bf16, int B, int T, int C, const float* s,
                 float* stats, float* tout, hipStream_t st);
 // ResNet34 TSTP (pooling_layers_wespeaker.py:66-88) over x (B, T, C) channel-last (C % 64 == 0), no BN / ReLU:
 // stats (B, 2C) = [mean_t x | sqrt(unbiased var_t x + 1e-7)] (nullable); tout (B, T, C) = x in fp32 (nullable).
-// NaN stays in its channel; T == 1 gives NaN stds (tstp_pool.hip).
-void tstp_pool(const void* x, bool x_bf16, int B, int T, int C, float* stats, float* tout, hipStream_t st);
+// NaN stays in its channel; T == 1 gives NaN stds (tstp_pool.hip).  eps: 1e-7 is WeSpeaker's; 3D-Speaker's TSTP
+// (pooling_layers_3d_speaker.py:52) adds 1e-8.
+void tstp_pool(const void* x, bool x_bf16, int B, int T, int C, float* stats, float* tout, hipStream_t st,
+               double eps = 1e-7);
 // y (B, N) = x (B, K) w^T + bias, fp32 FMA with a summation order fixed by K alone (a row's result does not depend
 // on B): the ResNet34 head's seg_1 / seg_2 (resnet_wespeaker.py:176-180).  w (N, K) row-major, K % 4 == 0.
 void seg_linear(const float* x, int B, int K, const float* w, const float* bias, int N, float* y, hipStream_t st);
@@ -292,6 +297,63 @@ struct SimamArgs {
 };
 int simam_tiles(int HW);
 void simam_gate(const SimamArgs& a, hipStream_t st);
+
+// ---------------------------------------------------------------- eres2net (eres2net.hip)
+// The 3x3 slice conv of a Res2Net block (ERes2NetV2.py:73-83, 140-151), bf16 on MFMA: pad 1, stride 1, `width` -> `width`
+// channels (even, <= 512) on NHWC maps of B x H x W pixels.  Reads channels [x_coff, x_coff + width) of rows of ldx
+// elements, plus (add != null) channels [add_coff, ..) of `add` summed on load in fp32; writes clamp(alpha conv + beta, 0,
+// 20) with NaN kept and +inf -> 20 to channels [o_coff, o_coff + width) of rows of ldo elements and touches no other
+// channel.  Offsets and row lengths need 4-byte alignment only (16-byte aligned slices load 16 B per lane).  w: bf16
+// Wt[Cp][9 * Cp], Cp = res2_padded(width), tap-major like conv_gemm's packing of the zero-padded (Cp, Cp, 3, 3) weight;
+// alpha / beta: Cp floats.
+struct Res2ConvArgs {
+  const void* x = nullptr;
+  int ldx = 0, x_coff = 0;
+  const void* add = nullptr;
+  int ld_add = 0, add_coff = 0;
+  int B = 0, H = 0, W = 0, width = 0;
+  const void* w = nullptr;
+  const float *alpha = nullptr, *beta = nullptr;
+  void* out = nullptr;
+  int ldo = 0, o_coff = 0;
+};
+__host__ __device__ inline int res2_padded(int width) { return (width + 31) / 32 * 32; }
+bool res2_conv_supported(const Res2ConvArgs& a);
+void res2_conv3x3(const Res2ConvArgs& a, hipStream_t st);
+// The in-block attentional fusion AFF(channels C, r 4) (fusion.py:10-30) per pixel, one pass: h = SiLU(a1 (W1 [x | y]) +
+// c1), att = a2 (W2 h) + c2, out = x (1 + tanh att) + y (1 - tanh att); the two conv biases and eval BatchNorms are
+// folded into (a1, c1) and (a2, c2).  x / y / out: C-channel slices (4-byte aligned) of rows of P pixels, bf16 or fp32;
+// out may alias x or y.  SiLU, tanh and every sum are fp32.  The weights are aff_pack's images, with Cp == C.
+struct AffGateArgs {
+  const void* x = nullptr;
+  int ldx = 0, x_coff = 0;
+  const void* y = nullptr;
+  int ldy = 0, y_coff = 0;
+  void* out = nullptr;
+  int ldo = 0, o_coff = 0;
+  bool bf16 = false;
+  int64_t P = 0;
+  int C = 0, I = 0;
+  const float *w1 = nullptr, *a1 = nullptr, *c1 = nullptr, *w2 = nullptr, *a2 = nullptr, *c2 = nullptr;
+};
+int aff_ipt(int I);   // hidden units per thread: I <= 52 padded to 4 * aff_ipt(I)
+struct AffPacked {
+  std::vector<float> w1, a1, c1, w2, a2, c2;
+};
+// Host images of W1 (I, 2 C), W2 (C, I) and the folded affines for slices padded from C to Cp channels (pad channels:
+// zero weights and a2 = c2 = 0, so att = 0 and out = x + y = 0 there).
+AffPacked aff_pack(const float* w1, const float* a1, const float* c1, const float* w2, const float* a2,
+                   const float* c2, int C, int I, int Cp);
+void aff_gate(const AffGateArgs& a, hipStream_t st);
+// fuse34's blend: out = x (1 + tanh att) + y (1 - tanh att) over NHWC pixel rows x / y (row lengths ldx / ldy, bf16 or
+// fp32), att (B H W, C) fp32, out fp32 at element strides o_s* of (b, h, w, c).
+void aff_blend(const void* x, int ldx, const void* y, int ldy, bool bf16, const float* att, int B, int H, int W, int C,
+               float* out, int64_t o_sb, int64_t o_sh, int64_t o_sw, int64_t o_sn, hipStream_t st);
+// x[p, 0..C) += y[p, 0..C) over P pixel rows of lengths ldx / ldy (the pointers at their channel slice).
+void slice_add(void* x, int ldx, const void* y, int ldy, bool bf16, int64_t P, int C, hipStream_t st);
+// NHWC (B, H, W, C) -> fp32 (B, W, H * C) with channel h * C + c (get_frame_level_feat's transpose(1, 3) + flatten,
+// channel-last).
+void nhwc_to_frames(const void* x, bool bf16, int B, int H, int W, int C, float* out, hipStream_t st);
 
 // ---------------------------------------------------------------- norms
 // y = LN(x) * g + b over the last dim D; rows of x at stride ldx, y at ldy.

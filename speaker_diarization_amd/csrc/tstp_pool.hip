@@ -1,7 +1,8 @@
 // ResNet34 pooled head prologue: TSTP (temporal statistics pooling, egs/alimeeting/ts_vad2/
 // pooling_layers_wespeaker.py:66-88): stats = [mean_t x | sqrt(var_t x (unbiased) + 1e-7)] over the stage-4 map
 // x (B, T', C) channel-last (C = 2560, channel c * 10 + f: TSTP flattens (C, F) the same way), plus the fp32
-// time-out map when asked for.
+// time-out map when asked for.  The epsilon is an argument: 3D-Speaker's TSTP (pooling_layers_3d_speaker.py:52, ERes2NetV2)
+// adds 1e-8.
 //
 // stats_pool's layout: one workgroup owns 64 channels of one batch row, its 4 waves split the time axis, so every
 // wave load is 64 consecutive channels of one frame (128 B bf16 / 256 B fp32).  Two passes over the (small,
@@ -20,7 +21,8 @@ constexpr int kGroups = 4;
 
 template <bool BF>
 __global__ __launch_bounds__(256) void tstp_pool_kernel(const act_t<BF>* __restrict__ x, int T, int C,
-                                                        float* __restrict__ stats, float* __restrict__ tout) {
+                                                        float* __restrict__ stats, float* __restrict__ tout,
+                                                        double eps) {
   __shared__ double red[kGroups][64];
   const int lane = threadIdx.x & 63;
   const int g = threadIdx.x >> 6;
@@ -48,7 +50,7 @@ __global__ __launch_bounds__(256) void tstp_pool_kernel(const act_t<BF>* __restr
   if (g == 0) {
     const double var = (red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]) / (double)(T - 1);
     stats[(int64_t)b * 2 * C + c] = (float)mean;
-    stats[(int64_t)b * 2 * C + C + c] = (float)sqrt(var + 1e-7);
+    stats[(int64_t)b * 2 * C + C + c] = (float)sqrt(var + eps);
   }
 }
 
@@ -117,7 +119,8 @@ void seg_linear(const float* x, int B, int K, const float* w, const float* bias,
   SD_LAUNCH_CHECK();
 }
 
-void tstp_pool(const void* x, bool x_bf16, int B, int T, int C, float* stats, float* tout, hipStream_t st) {
+void tstp_pool(const void* x, bool x_bf16, int B, int T, int C, float* stats, float* tout, hipStream_t st,
+               double eps) {
   SD_CHECK(x && C >= 64 && C % 64 == 0 && B >= 1 && B <= 65535 && T >= 1, kErrInvalid,
            "tstp_pool: C must be a multiple of 64, 1 <= B <= 65535, T >= 1");
   if (!stats && !tout) return;
@@ -127,10 +130,10 @@ void tstp_pool(const void* x, bool x_bf16, int B, int T, int C, float* stats, fl
   const dim3 grid(C / 64, B);
   if (x_bf16)
     hipLaunchKernelGGL(tstp_pool_kernel<true>, grid, dim3(256), 0, st, static_cast<const uint16_t*>(x), T, C, stats,
-                       tout);
+                       tout, eps);
   else
     hipLaunchKernelGGL(tstp_pool_kernel<false>, grid, dim3(256), 0, st, static_cast<const float*>(x), T, C, stats,
-                       tout);
+                       tout, eps);
   SD_LAUNCH_CHECK();
 }
 

@@ -10,7 +10,10 @@ Drop-in for the step before TS-VAD inference:
   * `ECAPA_TDNN_GLOB_c1024` — egs/alimeeting/ts_vad2/ecapa_tdnn_wespeaker.py:161-271: the WeSpeaker ECAPA-TDNN
     extractor of generate_chunk_speaker_embedding_from_ecapa_tdnn_for_diarization.py:95-172 (192-d embeddings,
     attentive statistics pooling with the global context), run by libsdiar (`sd_ecapa_*`); `extract_embed` drives
-    any of the three models.
+    any of the models.
+  * `ERes2NetV2` — egs/alimeeting/ts_vad2/ERes2NetV2.py:162-255: the 3D-Speaker extractor of
+    generate_chunk_speaker_embedding_from_modelscope_for_diarization.py:110-136 (192-d embeddings), run by libsdiar
+    (`sd_eres2netv2_*`).
   * `FBank` — the extractor's FBank (generate_chunk_speaker_embedding_from_modelscope_for_
     diarization.py:307-331): kaldi fbank with the povey window, dither 0, no 2^15 scale,
     mean_nor over the chunk.
@@ -264,6 +267,115 @@ class SimAM_ResNet34_ASP(_lib.Handle):
         return fo.permute(0, 2, 1)
 
 
+class ERes2NetV2(_lib.Handle):
+    """egs/alimeeting/ts_vad2/ERes2NetV2.py:162-255: the 3D-Speaker ERes2NetV2 embedding extractor (Res2Net blocks with
+    Hardtanh(0, 20), AFF gates in layers 3-4, layer3_ds + fuse34, TSTP with eps 1e-8, seg_1) run by libsdiar
+    (`sd_eres2netv2_*`).  Same constructor arguments and state_dict keys; forward(x) -> (B, embedding_size), and the two
+    frame-level outputs of egs/magicdata-ramc/ots_vad/ERes2NetV2.py.  Built at (baseWidth, scale, expansion) = (26, 2, 2)
+    (the class default) and (24, 4, 4) (iic/speech_eres2netv2w24s4ep4_sv_zh-cn_16k-common,
+    generate_chunk_speaker_embedding_from_modelscope_for_diarization.py:110-136)."""
+    kind = "eres2netv2"
+    TRIPLES = ((26, 2, 2), (24, 4, 4))
+
+    def __init__(self, feat_dim: int = 80, embedding_size: int = 192, m_channels: int = 64, baseWidth: int = 26,
+                 scale: int = 2, expansion: int = 2, pooling_func: str = "TSTP", two_emb_layer: bool = False,
+                 *, device=None, precision: str = "bf16", max_batch: int = 96, max_frames: int = 598):
+        if two_emb_layer:
+            raise ValueError("the MI355X ERes2NetV2 builds two_emb_layer=False only (the extractor's setting)")
+        if pooling_func != "TSTP":
+            raise ValueError(f"the MI355X ERes2NetV2 builds TSTP pooling only, got {pooling_func}")
+        if (baseWidth, scale, expansion) not in self.TRIPLES:
+            raise ValueError("the MI355X ERes2NetV2 builds (baseWidth, scale, expansion) = (26, 2, 2) or (24, 4, 4) only, "
+                             f"got {(baseWidth, scale, expansion)}")
+        if feat_dim != 80:
+            raise ValueError(f"the MI355X ERes2NetV2 supports feat_dim 80 only, got {feat_dim}")
+        if m_channels != 64:
+            raise ValueError(f"the MI355X ERes2NetV2 supports m_channels 64 only, got {m_channels}")
+        code = _lib.precision_code(precision, ("bf16", "fp32"))
+        self.device = _lib.hip_device(device, "ERes2NetV2")
+        self.feat_dim, self.embedding_size, self.m_channels = feat_dim, embedding_size, m_channels
+        self.baseWidth, self.scale, self.expansion = baseWidth, scale, expansion
+        self.frame_channels = 5120 * expansion     # 512 e x 10 rows, and 256 e x 20 rows
+        self.precision, self.max_batch, self.max_frames = precision, max_batch, max_frames
+        self._create(_lib.Eres2netv2Config(feat_dim=feat_dim, embedding_size=embedding_size, m_channels=m_channels,
+                                           base_width=baseWidth, scale=scale, expansion=expansion,
+                                           max_batch=max_batch, max_frames=max_frames, precision=code))
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        if not strict:
+            raise ValueError("the MI355X backend only supports strict=True loading")
+        self._load(unwrap_checkpoint(state_dict, kind="eres2netv2"))
+        return self
+
+    def eval(self):
+        return self
+
+    def to(self, device):
+        import torch
+        if torch.device(device) != self.device:
+            raise ValueError("re-create the model on the target device")
+        return self
+
+    @property
+    def device_bytes(self) -> int:
+        return self._device_bytes()
+
+    out_frames = staticmethod(ResNet34.out_frames)
+
+    @staticmethod
+    def frames25(T: int) -> int:
+        for _ in range(2):
+            T = (T - 1) // 2 + 1
+        return T
+
+    def _input(self, x):
+        import torch
+        B, T, F = x.shape
+        if F != self.feat_dim:
+            raise ValueError(f"expected {self.feat_dim}-dim fbank, got {F}")
+        if T < 8:
+            raise ValueError(f"ERes2NetV2 needs at least 8 fbank frames, got {T}")
+        return x.to(self.device, torch.float32).contiguous()
+
+    def forward(self, x, out=None):
+        """x (B, T, 80) -> (B, embedding_size) (ERes2NetV2.py:236-255).  T >= 8; T == 8 pools one frame and gives the
+        reference's all-NaN embedding (the unbiased variance of one frame)."""
+        import torch
+        x = self._input(x)
+        B, T, _ = x.shape
+        if B > self.max_batch:
+            parts = [self.forward(x[s:s + self.max_batch], out=None if out is None else out[s:s + self.max_batch])
+                     for s in range(0, B, self.max_batch)]
+            return out if out is not None else torch.cat(parts)
+        if out is None:
+            out = torch.empty(B, self.embedding_size, device=self.device, dtype=torch.float32)
+        _lib.call("sd_eres2netv2_forward", self._h, _lib.ptr(x), B, T, _lib.ptr(out), None, None,
+                  _lib.stream_ptr(self.device))
+        return out
+
+    __call__ = forward
+
+    def _frames(self, x, which: int):
+        import torch
+        x = self._input(x)
+        B, T, _ = x.shape
+        if B > self.max_batch:
+            return torch.cat([self._frames(x[s:s + self.max_batch], which) for s in range(0, B, self.max_batch)])
+        Tn = self.out_frames(T) if which == 0 else self.frames25(T)
+        fo = torch.empty(B, Tn, self.frame_channels, device=self.device, dtype=torch.float32)
+        _lib.call("sd_eres2netv2_forward", self._h, _lib.ptr(x), B, T, None, _lib.ptr(fo) if which == 0 else None,
+                  _lib.ptr(fo) if which == 1 else None, _lib.stream_ptr(self.device))
+        return fo.permute(0, 2, 1)
+
+    def get_frame_level_feat(self, x):
+        """x (B, T, 80) -> the fuse34 map (B, 5120 e, T'), channel f * C + c (ots_vad/ERes2NetV2.py:253-258)."""
+        return self._frames(x, 0)
+
+    def get_frame_level_feat_frame_rate25(self, x):
+        """x (B, T, 80) -> out3 (B, 5120 e, T3), channel f * C + c (ots_vad/ERes2NetV2.py:259-272)."""
+        return self._frames(x, 1)
+
+
 class ECAPA_TDNN_GLOB_c1024(_lib.Handle):
     """egs/alimeeting/ts_vad2/ecapa_tdnn_wespeaker.py:161-254, 264-271 with speech_encoder=False: ECAPA-TDNN at 1024
     channels with global-context ASTP, bn and linear, run by libsdiar (`sd_ecapa_*`).  Same constructor arguments and
@@ -396,8 +508,9 @@ def extract_embed(wav, model, length_embedding: float = 6.0, step_embedding: flo
     """wav: 1-D float samples in [-1, 1) (numpy or tensor; soundfile values cast to float32
     like torch.FloatTensor at :283) -> (n_chunks, E) float32 embeddings on the model device.
     model: CAMPPlus, ResNet34 (generate_chunk_speaker_embedding_from_wespeaker_for_diarization.py:143-176, the
-    same chunk loop; the last element of the model's tuple is kept, :132-133) or ECAPA_TDNN_GLOB_c1024
-    (generate_chunk_speaker_embedding_from_ecapa_tdnn_for_diarization.py:142-172, the same loop again).  A file too short for ResNet34's
+    same chunk loop; the last element of the model's tuple is kept, :132-133), ECAPA_TDNN_GLOB_c1024
+    (generate_chunk_speaker_embedding_from_ecapa_tdnn_for_diarization.py:142-172, the same loop again) or ERes2NetV2 (the
+    modelscope script's own entry, :110-136, through the loop at :271-304).  A file too short for ResNet34's
     three stride-2 stages (at most 8 fbank frames) yields the reference's all-NaN embedding."""
     import torch
     dev = model.device

@@ -199,6 +199,52 @@ def simam_resnet34_layout(embed_dim: int = 256) -> list:
     return k
 
 
+def eres2netv2_layout(base_width: int = 26, scale: int = 2, expansion: int = 2, embedding_size: int = 192) -> list:
+    """Key layout of ERes2NetV2(feat_dim=80, embedding_size, m_channels=64, baseWidth, scale, expansion,
+    pooling_func="TSTP", two_emb_layer=False) (ERes2NetV2.py:162-226; the modelscope extractor script builds it at (24, 4,
+    4), generate_chunk_speaker_embedding_from_modelscope_for_diarization.py:110-136): Res2Net blocks [3, 4, 6, 3] at
+    planes 64 .. 512 with `scale` slice convs of width floor(planes baseWidth / 64), AFF gates between the slices in
+    layers 3-4 (fusion.py:10-22: Conv2d with bias, BatchNorm2d, SiLU, Conv2d with bias, BatchNorm2d), a shortcut pair in
+    every block whose input differs from planes * expansion, layer3_ds, fuse34 and seg_1 on the TSTP statistics."""
+    k: list = []
+
+    def aff(p: str, c: int):
+        k.append((p + "local_att.0.weight", (c // 4, 2 * c, 1, 1), "er_att1"))
+        k.append((p + "local_att.0.bias", (c // 4,), "small"))
+        _bn(k, p + "local_att.1", c // 4)
+        k.append((p + "local_att.3.weight", (c, c // 4, 1, 1), "er_att2"))
+        k.append((p + "local_att.3.bias", (c,), "small"))
+        _bn(k, p + "local_att.4", c)
+
+    k.append(("conv1.weight", (64, 1, 3, 3), "rn_conv"))
+    _bn(k, "bn1", 64)
+    cin = 64
+    for layer, (planes, n) in enumerate(((64, 3), (128, 4), (256, 6), (512, 3)), start=1):
+        width = planes * base_width // 64
+        for blk in range(n):
+            q = f"layer{layer}.{blk}."
+            k.append((q + "conv1.weight", (width * scale, cin, 1, 1), "er_conv1"))
+            _bn(k, q + "bn1", width * scale, kind="er")
+            for i in range(scale):
+                k.append((f"{q}convs.{i}.weight", (width, width, 3, 3), "er_conv"))
+            for i in range(scale):
+                _bn(k, f"{q}bns.{i}", width, kind="er")
+            if layer >= 3:
+                for j in range(scale - 1):
+                    aff(f"{q}fuse_models.{j}.", width)
+            k.append((q + "conv3.weight", (planes * expansion, width * scale, 1, 1), "er_conv3"))
+            _bn(k, q + "bn3", planes * expansion)
+            if (blk == 0 and layer > 1) or cin != planes * expansion:
+                k.append((q + "shortcut.0.weight", (planes * expansion, cin, 1, 1), "er_sc"))
+                _bn(k, q + "shortcut.1", planes * expansion)
+            cin = planes * expansion
+    k.append(("layer3_ds.weight", (512 * expansion, 256 * expansion, 3, 3), "er_ds"))
+    aff("fuse34.", 512 * expansion)
+    k.append(("seg_1.weight", (embedding_size, 10240 * expansion), "er_seg"))
+    k.append(("seg_1.bias", (embedding_size,), "small"))
+    return k
+
+
 def _conv_relu_bn(k: list, p: str, cout: int, cin: int, taps: int, kind: str):
     """Conv1dReluBn (ecapa_tdnn_wespeaker.py:85-108): conv with bias, ReLU, then BatchNorm."""
     k.append((p + "conv.weight", (cout, cin, taps), kind))
@@ -379,6 +425,15 @@ SAM_BN2_BIAS = 0.1
 SAM_GAIN = {"sam_conv2": 0.3, "sam_att1": 1.0, "sam_att2": 1.0}
 
 
+# Seeded ERes2NetV2 init (eres2netv2_layout): He-normal times a per-role gain, and a positive shift on the BatchNorms
+# in front of a Hardtanh(0, 20) (kinds er_*), chosen so that tests/golden/make_golden_eres2net.py's assertions on the
+# reference run hold for every case: the clamp at 20 fires on a share of the elements but not everywhere, and the AFF
+# gates' tanh neither vanishes nor saturates.
+ER_GAIN = {"er_conv1": 0.8, "er_conv": 1.0, "er_conv3": 0.6, "er_sc": 0.6, "er_att1": 0.15, "er_att2": 0.5,
+           "er_ds": 0.5, "er_seg": 0.1}
+ER_BN_BIAS = 0.3
+
+
 def _init(rng: np.random.Generator, shape: Shape, kind: str) -> np.ndarray:
     if kind == "nbt":
         return np.array(0, dtype=np.int64)
@@ -400,6 +455,12 @@ def _init(rng: np.random.Generator, shape: Shape, kind: str) -> np.ndarray:
         v = rng.standard_normal(n) * (EC_GAIN[kind] * np.sqrt(2.0 / fan_in))
     elif kind in SAM_GAIN:                # SimAM-ResNet34 conv2 / ASP attention: He-normal times a per-role gain
         v = rng.standard_normal(n) * (SAM_GAIN[kind] * np.sqrt(2.0 / fan_in))
+    elif kind in ER_GAIN:                 # ERes2NetV2 convs: He-normal times a per-role gain
+        v = rng.standard_normal(n) * (ER_GAIN[kind] * np.sqrt(2.0 / fan_in))
+    elif kind in ("er_w", "er_m", "er_v"):
+        return _init(rng, shape, "bn" + kind[2:])
+    elif kind == "er_b":
+        v = ER_BN_BIAS + rng.standard_normal(n) * 0.05
     elif kind in ("sam_w", "sam_m", "sam_v"):   # SimAM-ResNet34 bn2: the generic BatchNorm statistics ...
         return _init(rng, shape, "bn" + kind[3:])
     elif kind == "sam_b":                 # ... with a positive shift (SAM_BN2_BIAS)
@@ -611,6 +672,12 @@ def resnet34_embed_state_dict(seed: int = 777, embed_dim: int = 256, two_emb_lay
 def simam_resnet34_state_dict(seed: int = 777, embed_dim: int = 256):
     """Seeded weights for a standalone SimAM_ResNet34_ASP extractor (keys front.*, pooling.attention.*, bottleneck.*)."""
     return synthetic_state_dict(simam_resnet34_layout(embed_dim), seed)
+
+
+def eres2netv2_state_dict(seed: int = 777, base_width: int = 26, scale: int = 2, expansion: int = 2,
+                          embedding_size: int = 192):
+    """Seeded ERes2NetV2 weights under the reference key names (eres2netv2_layout)."""
+    return synthetic_state_dict(eres2netv2_layout(base_width, scale, expansion, embedding_size), seed)
 
 
 def ecapa_embed_state_dict(seed: int = 777, embed_dim: int = 192):
