@@ -67,7 +67,12 @@ typedef struct {
                                      3: "ecapa_channel_1024_wespeaker" (ECAPA_TDNN_GLOB_c1024 trunk + Conv1d(1536 ->
                                         speaker_embed_dim, k5, stride 4, pad 2), model.py:631-654), single/multi_backend
                                         "transformer"; any window of 1 .. max_fbank_frames frames runs, T fbank frames
-                                        give (T - 1) / 4 + 1 mix frames */
+                                        give (T - 1) / 4 + 1 mix frames
+                                     4: "ReDimNetB2" (egs/magicdata-ramc/ts_vad2/model.py:694-715: ReDimNetB2 trunk on
+                                        72-bin fbank + Conv1d(1152 -> speaker_embed_dim, k5, stride 4, pad 2)),
+                                        single/multi_backend "transformer"; ref_speech is (B, T, 72); the MagicData
+                                        length rule (:1296-1309): mix frames within 3 of the label length, zero-padded
+                                        after the ReLU or cut, SD_ERR_SHAPE beyond */
   int max_num_speaker;            /* TSVADDataConfig.max_num_speaker (4)                     */
   int rs_len;                     /* seconds; PositionalEncoding max_len = rs_len * 25       */
   int max_batch;                  /* workspace sizing                                        */
@@ -336,6 +341,65 @@ int sd_ecapa_forward(sd_ecapa* h, const float* feats, int B, int T, float* emb, 
 int sd_ecapa_debug_stats(const sd_ecapa* h, void** ptr);
 int64_t sd_ecapa_device_bytes(const sd_ecapa* h);
 int sd_ecapa_destroy(sd_ecapa* h);
+
+/* ------------------------------------------------------------------ ReDimNetB2 embeddings
+ * Replaces ReDimNetB2(feat_dim=72, embed_dim=192, pooling_func="ASTP", two_emb_layer=False)
+ * (egs/magicdata-ramc/ts_vad2/redimnet_wespeaker.py:925-948 over ReDimNet :793-872 and ReDimNetBone :623-790,
+ * pooling_layers_wespeaker.py:91-144) as the target-speaker embedding extractor of
+ * egs/magicdata-ramc/ts_vad2/generate_chunk_speaker_embedding_from_wespeaker_for_diarization.py (72-bin povey fbank).
+ * State-dict keys are the module's (backbone.inputs_weights.*, backbone.stem.*, backbone.stage0..5.*,
+ * pool.linear1/2.*, seg_1.*). */
+typedef struct sd_redimnet sd_redimnet;
+
+typedef struct {
+  int feat_dim;        /* 72 only */
+  int embed_dim;       /* 192 (a multiple of 4) */
+  int max_batch;       /* workspace: chunks per forward (the extractor's batch size 96)    */
+  int max_frames;      /* workspace: fbank frames per chunk (598 for 6 s)                  */
+  int precision;       /* 0: fp32 (exact-f32 MFMA), 1: bf16 maps (LayerNorms, softmax, ASTP and seg_1 stay fp32),
+                          2: bf16x3 (fp32 tensors, split-bf16 GEMMs) */
+} sd_redimnet_config;
+
+/* redimnet_wespeaker.py:925-948 (ReDimNet.__init__ :795-845); feat_dim != 72 gives SD_ERR_INVALID */
+int sd_redimnet_create(const sd_redimnet_config* cfg, sd_redimnet** out);
+/* load_state_dict (strict here) */
+int sd_redimnet_set_param(sd_redimnet* h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+int sd_redimnet_finalize(sd_redimnet* h);
+/* ReDimNet.forward (:861-872) and get_frame_level_feat (:855-859).  feats: device (B, T, 72) fbank; emb: device
+ * (B, embed_dim) or NULL = seg_1(pool(backbone(x))), the second element of the reference's pair; frames: device
+ * (B, T, 1152) channel-last fp32 or NULL, channel f * c + ch as to1d orders it (:758-761; the time axis is not
+ * subsampled).  emb with T == 1 is refused with SD_ERR_SHAPE: the reference's unbiased variance of a single
+ * frame (ASTP's global context) is NaN; frames work from T == 1. */
+int sd_redimnet_forward(sd_redimnet* h, const float* feats, int B, int T, float* emb, float* frames, void* stream);
+/* Tests and tools/redimnet_probe.py only: 1 runs the 2-D ConvNeXt-like blocks of a bf16 handle as the generic arm
+ * (grouped-conv kernel + conv_gemm) instead of the single-launch kernel; 0 restores the default.  fp32 / bf16x3
+ * handles always run the generic arm. */
+int sd_redimnet_debug_generic(sd_redimnet* h, int on);
+int64_t sd_redimnet_device_bytes(const sd_redimnet* h);
+int sd_redimnet_destroy(sd_redimnet* h);
+
+/* Test-only single ops of the ReDimNetB2 trunk (csrc/redimnet.hip); every pointer is a device pointer.
+ * precision as above; maps are bf16 at precision 1, else fp32.
+ * sd_op_redim_block2d: ConvNeXtLikeBlock dim 2 (:135-165) on x (B, T, 1152 / c, c): dw_w (c, 4, 3, 3) + dw_b, the eval
+ *   BatchNorm2d as (bn_s, bn_h), pw_w (c, c) + pw_b; use_generic 0 needs precision 1.
+ * sd_op_redim_dwconv1d: depthwise conv (hC, k) + bias, BatchNorm1d as (bn_s, bn_h), erf GELU on x (B, T, hC) fp32.
+ * sd_op_redim_stage_mix: y = sum_k w[k] x[k] over n stacked maps x (n, rows, 1152), w (n, 1152) already softmaxed.
+ * sd_op_redim_stem: stem conv (16, 3, 3) + bias + channels-first LayerNorm (g, beta) of fbank (B, T, 72).
+ * sd_op_astp_pool_c: sd_op_astp_pool at C channels (C % 64 == 0), w1 (128, 3 C), w2 (C, 128). */
+int sd_op_redim_block2d(const void* x, int B, int T, int c, const float* dw_w, const float* dw_b, const float* bn_s,
+                        const float* bn_h, const float* pw_w, const float* pw_b, void* out, int use_generic,
+                        int precision, void* stream);
+int sd_op_redim_dwconv1d(const float* x, int B, int T, int hC, int k, const float* w, const float* bias,
+                         const float* bn_s, const float* bn_h, void* out, int out_bf16, void* stream);
+int sd_op_redim_stage_mix(const void* x, int n, int64_t rows, const float* w, void* out, int bf16, void* stream);
+int sd_op_redim_stem(const float* fbank, int B, int T, const float* w, const float* bias, const float* g,
+                     const float* beta, void* out, int out_bf16, void* stream);
+int sd_op_astp_pool_c(const void* x, int x_bf16, int B, int T, int C, const float* w1, const float* b1, const float* w2,
+                      const float* b2, float* stats, void* stream);
+/* sd_op_attention with an explicit softmax scale instead of (D / nh)^-0.5: heads zero-padded to a width the kernel has
+ * keep the scale of their true width (ReDimNetB2's 24 / 36 / 72 in 32 / 48 / 96).  precision as sd_op_attention's. */
+int sd_op_attention_scaled(const float* qkv, int S, int T, int D, int nh, float scale, float* out, int precision,
+                           void* stream);
 
 /* ------------------------------------------------------------------ SSND
  * Replaces SSNDModel.infer (egs/alimeeting/ssnd/ssnd_model.py:752-776) with extractor

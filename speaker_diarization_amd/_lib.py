@@ -131,6 +131,16 @@ class EcapaConfig(ctypes.Structure):
     ]
 
 
+class RedimnetConfig(ctypes.Structure):
+    _fields_ = [
+        ("feat_dim", c_int),
+        ("embed_dim", c_int),
+        ("max_batch", c_int),
+        ("max_frames", c_int),
+        ("precision", c_int),
+    ]
+
+
 class SsndConfig(ctypes.Structure):
     _fields_ = [(n, c_int) for n in (
         "max_batch", "max_fbank_frames", "max_speakers", "feat_dim", "emb_dim", "q_det_aux_dim", "q_rep_aux_dim",
@@ -182,6 +192,18 @@ _SIGS = {
     "sd_debug_clamp_route": (c_int, [c_int]),
     "sd_ecapa_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_ecapa_debug_stats": (c_int, [c_void_p, POINTER(c_void_p)]),
+    "sd_redimnet_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sd_redimnet_debug_generic": (c_int, [c_void_p, c_int]),
+    "sd_op_attention_scaled": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
+    "sd_op_redim_block2d": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "sd_op_redim_dwconv1d": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int, c_void_p]),
+    "sd_op_redim_stage_mix": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
+    "sd_op_redim_stem": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                 c_void_p]),
+    "sd_op_astp_pool_c": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
     "sd_eda_input_stride": (c_int, [c_void_p]),
     "sd_eda_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p]),
@@ -262,7 +284,7 @@ _SIGS = {
 # -> <the kind's forward calls>* -> destroy, device_bytes at any time.
 KINDS = {"tsvad": TsvadConfig, "tsvad_stream": TsvadStreamConfig, "eda": EdaConfig, "fseend": FseendConfig,
          "campp": CamppConfig, "resnet34": Resnet34Config, "simam_resnet34": SimamResnet34Config,
-         "eres2netv2": Eres2netv2Config, "ecapa": EcapaConfig, "ssnd": SsndConfig}
+         "eres2netv2": Eres2netv2Config, "ecapa": EcapaConfig, "redimnet": RedimnetConfig, "ssnd": SsndConfig}
 for _kind, _conf in KINDS.items():
     _SIGS[f"sd_{_kind}_create"] = (c_int, [POINTER(_conf), POINTER(c_void_p)])
     _SIGS[f"sd_{_kind}_set_param"] = (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int])

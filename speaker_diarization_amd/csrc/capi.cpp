@@ -20,6 +20,7 @@
 #include "simam_emb.h"
 #include "eres2net.h"
 #include "ecapa.h"
+#include "redimnet.h"
 #include "tsvad_stream.h"
 #include "ssnd.h"
 
@@ -46,6 +47,7 @@ struct sd_resnet34 : Handle<sd::ResEmbModel> {};
 struct sd_simam_resnet34 : Handle<sd::SimamEmbModel> {};
 struct sd_eres2netv2 : Handle<sd::ERes2NetV2Model> {};
 struct sd_ecapa : Handle<sd::EcapaModel> {};
+struct sd_redimnet : Handle<sd::RedimNetModel> {};
 struct sd_ssnd : Handle<sd::SsndModel> {};
 
 namespace {
@@ -189,7 +191,7 @@ int sd_probe_lstm_handoff(int steps, float* us_per_step, void* stream) {
 int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
-    SD_CHECK(c->variant >= 0 && c->variant <= 3, sd::kErrInvalid, "unknown TS-VAD variant");
+    SD_CHECK(c->variant >= 0 && c->variant <= 4, sd::kErrInvalid, "unknown TS-VAD variant");
     SD_CHECK(c->precision >= 0 && c->precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
     SD_CHECK(c->max_batch > 0 && c->max_fbank_frames > 0, sd::kErrInvalid, "bad workspace sizes");
     SD_CHECK(c->max_num_speaker > 0 && c->num_transformer_layer >= 1 && c->transformer_ffn_embed_dim > 0 &&
@@ -723,6 +725,52 @@ int64_t sd_ecapa_device_bytes(const sd_ecapa* h) { return device_bytes(h); }
 
 int sd_ecapa_destroy(sd_ecapa* h) { return destroy(h); }
 
+int sd_redimnet_create(const sd_redimnet_config* c, sd_redimnet** out) {
+  return guard([&] {
+    SD_CHECK(c && out, sd::kErrInvalid, "null argument");
+    SD_CHECK(c->precision >= 0 && c->precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
+    SD_CHECK(c->feat_dim == 72, sd::kErrInvalid, "ReDimNetB2 (MI355X backend) supports feat_dim 72 only");
+    SD_CHECK(c->embed_dim >= 4 && c->embed_dim % 4 == 0, sd::kErrInvalid, "embed_dim must be a positive multiple of 4");
+    SD_CHECK(c->max_batch > 0 && c->max_frames >= 2, sd::kErrInvalid, "bad workspace sizes");
+    // the trunk counts pixel rows (B T 72) and map values per launch in int
+    SD_CHECK((int64_t)c->max_batch * c->max_frames * sd::kRedimCF < (1ll << 31), sd::kErrInvalid,
+             "max_batch * max_frames * 1152 must be below 2^31");
+    sd::RedimNetConfig t;
+    t.feat_dim = c->feat_dim;
+    t.embed_dim = c->embed_dim;
+    t.max_batch = c->max_batch;
+    t.max_frames = c->max_frames;
+    t.bf16 = c->precision == 1;
+    create(out, c->precision == 2, t);
+  });
+}
+
+int sd_redimnet_set_param(sd_redimnet* h, const char* name, const float* data, const int64_t* shape, int ndim) {
+  return set_param(h, name, data, shape, ndim);
+}
+
+int sd_redimnet_finalize(sd_redimnet* h) { return finalize(h); }
+
+int sd_redimnet_forward(sd_redimnet* h, const float* feats, int B, int T, float* emb, float* frames, void* stream) {
+  return guard([&] {
+    const sd::GemmX3Scope x3(h && h->x3);
+    SD_CHECK(h && feats && (emb || frames), sd::kErrInvalid, "null argument");
+    h->model->forward(feats, B, T, emb, frames, S(stream));
+  });
+}
+
+int sd_redimnet_debug_generic(sd_redimnet* h, int on) {
+  return guard([&] {
+    SD_CHECK(h, sd::kErrInvalid, "null handle");
+    SD_CHECK(on == 0 || on == 1, sd::kErrInvalid, "on must be 0 or 1");
+    h->model->set_generic(on != 0);
+  });
+}
+
+int64_t sd_redimnet_device_bytes(const sd_redimnet* h) { return device_bytes(h); }
+
+int sd_redimnet_destroy(sd_redimnet* h) { return destroy(h); }
+
 int sd_ssnd_create(const sd_ssnd_config* c, sd_ssnd** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
@@ -894,13 +942,14 @@ int sd_op_res2_chain(const void* x, int B, int T, int dilation, const float* w, 
   });
 }
 
-int sd_op_astp_pool(const void* x, int x_bf16, int B, int T, const float* w1, const float* b1, const float* w2,
-                    const float* b2, float* stats, void* stream) {
+int sd_op_astp_pool_c(const void* x, int x_bf16, int B, int T, int C, const float* w1, const float* b1, const float* w2,
+                      const float* b2, float* stats, void* stream) {
   return guard([&] {
     hipStream_t st = S(stream);
     SD_CHECK(x && w1 && b1 && w2 && b2 && stats && B >= 1, sd::kErrInvalid, "astp_pool: bad argument");
+    SD_CHECK(C >= 64 && C % 64 == 0, sd::kErrInvalid, "astp_pool: C must be a multiple of 64");
     SD_CHECK(T >= 2, sd::kErrShape, "ASTP needs at least 2 frames (the unbiased variance of one frame is NaN)");
-    constexpr int C = 1536, H = 128;
+    constexpr int H = 128;
     const size_t rows = (size_t)B * T;
     // linear1.weight (128, 3 C) split on its input axis: the per-frame half (packed for conv_gemm) and the context half
     Scratch halves((size_t)3 * H * C * 4, st), w1x((size_t)H * C * 4, st), w2p((size_t)C * H * 4, st);
@@ -918,9 +967,89 @@ int sd_op_astp_pool(const void* x, int x_bf16, int B, int T, const float* w1, co
     a.w1x = w1x.p; a.w1c = hc; a.b1 = b1; a.w2 = w2p.p; a.b2 = b2; a.stats = stats;
     a.ctx = static_cast<float*>(ctx.p); a.cv = static_cast<float*>(cv.p); a.x32 = static_cast<float*>(x32.p);
     a.h = static_cast<float*>(hh.p); a.e = static_cast<float*>(e.p);
+    a.C = C;
     sd::astp_pool(a, st);
   });
 }
+
+int sd_op_astp_pool(const void* x, int x_bf16, int B, int T, const float* w1, const float* b1, const float* w2,
+                    const float* b2, float* stats, void* stream) {
+  return sd_op_astp_pool_c(x, x_bf16, B, T, 1536, w1, b1, w2, b2, stats, stream);
+}
+
+int sd_op_redim_block2d(const void* x, int B, int T, int c, const float* dw_w, const float* dw_b, const float* bn_s,
+                        const float* bn_h, const float* pw_w, const float* pw_b, void* out, int use_generic,
+                        int precision, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && dw_w && dw_b && bn_s && bn_h && pw_w && pw_b && out && B >= 1 && T >= 1, sd::kErrInvalid,
+             "redim_block2d: bad argument");
+    SD_CHECK(c == 16 || c == 32 || c == 64 || c == 128, sd::kErrInvalid, "redim_block2d: c must be 16, 32, 64 or 128");
+    SD_CHECK(precision >= 0 && precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
+    SD_CHECK(use_generic || precision == 1, sd::kErrInvalid,
+             "redim_block2d: the fused kernel is bf16 (precision 1); fp32 and bf16x3 take use_generic 1");
+    const bool bf = precision == 1;
+    const sd::GemmX3Scope x3(precision == 2);
+    // fold on the host, as the model's load does
+    std::vector<float> w((size_t)c * 36), b(c), s(c), h(c), dw, dwb;
+    SD_HIP(hipStreamSynchronize(st));
+    SD_HIP(hipMemcpy(w.data(), dw_w, w.size() * 4, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(b.data(), dw_b, (size_t)c * 4, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(s.data(), bn_s, (size_t)c * 4, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(h.data(), bn_h, (size_t)c * 4, hipMemcpyDeviceToHost));
+    sd::redim_pack_dw(w.data(), b.data(), s.data(), h.data(), c, dw, dwb);
+    Scratch d_dw(dw.size() * 4, st), d_b(dwb.size() * 4, st), tmp((size_t)B * T * sd::kRedimCF * (bf ? 2 : 4), st);
+    SD_HIP(hipMemcpy(d_dw.p, dw.data(), dw.size() * 4, hipMemcpyHostToDevice));
+    SD_HIP(hipMemcpy(d_b.p, dwb.data(), dwb.size() * 4, hipMemcpyHostToDevice));
+    PackedScratch pw(pw_w, c, c, 1, bf, st);
+    sd::RedimBlock2dW W;
+    W.dw = static_cast<const float*>(d_dw.p); W.dw_b = static_cast<const float*>(d_b.p);
+    W.pw = pw.p; W.pw_b = pw_b;
+    sd::redim_block2d(x, B, T, c, W, tmp.p, out, bf, use_generic != 0, st);
+  });
+}
+
+int sd_op_redim_dwconv1d(const float* x, int B, int T, int hC, int k, const float* w, const float* bias,
+                         const float* bn_s, const float* bn_h, void* out, int out_bf16, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && w && bias && bn_s && bn_h && out && B >= 1 && T >= 1 && hC >= 1 && k >= 1 && k <= 59 && k % 2 == 1,
+             sd::kErrInvalid, "redim_dwconv1d: bad argument");
+    std::vector<float> hw((size_t)hC * k), hb(hC), s(hC), h(hC), wt((size_t)hC * k), fb(hC);
+    SD_HIP(hipStreamSynchronize(st));
+    SD_HIP(hipMemcpy(hw.data(), w, hw.size() * 4, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(hb.data(), bias, (size_t)hC * 4, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(s.data(), bn_s, (size_t)hC * 4, hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(h.data(), bn_h, (size_t)hC * 4, hipMemcpyDeviceToHost));
+    for (int ch = 0; ch < hC; ++ch) {
+      for (int j = 0; j < k; ++j) wt[(size_t)j * hC + ch] = (float)((double)hw[(size_t)ch * k + j] * s[ch]);
+      fb[ch] = (float)((double)hb[ch] * s[ch] + h[ch]);
+    }
+    Scratch d_w(wt.size() * 4, st), d_b(fb.size() * 4, st);
+    SD_HIP(hipMemcpy(d_w.p, wt.data(), wt.size() * 4, hipMemcpyHostToDevice));
+    SD_HIP(hipMemcpy(d_b.p, fb.data(), fb.size() * 4, hipMemcpyHostToDevice));
+    sd::redim_dwconv1d(x, B, T, hC, k, static_cast<const float*>(d_w.p), static_cast<const float*>(d_b.p), out,
+                       out_bf16 != 0, st);
+  });
+}
+
+int sd_op_redim_stage_mix(const void* x, int n, int64_t rows, const float* w, void* out, int bf16, void* stream) {
+  return guard([&] {
+    SD_CHECK(x && w && out && n >= 2 && n <= sd::RedimMixArgs::kMax && rows >= 1, sd::kErrInvalid,
+             "redim_stage_mix: 2 to 7 inputs, rows >= 1");
+    sd::RedimMixArgs a;
+    a.n = n;
+    a.w = w;
+    for (int k = 0; k < n; ++k) a.x[k] = static_cast<const char*>(x) + (size_t)k * rows * sd::kRedimCF * (bf16 ? 2 : 4);
+    sd::redim_stage_mix(a, rows, out, bf16 != 0, S(stream));
+  });
+}
+
+int sd_op_redim_stem(const float* fbank, int B, int T, const float* w, const float* bias, const float* g,
+                     const float* beta, void* out, int out_bf16, void* stream) {
+  return guard([&] { sd::redim_stem(fbank, B, T, w, bias, g, beta, out, out_bf16 != 0, S(stream)); });
+}
+
 
 int sd_op_asp_pool(const void* x, int x_bf16, int B, int T, int C, const float* w1, const float* b1, const float* bn_s,
                    const float* bn_h, const float* w2, const float* b2, float* stats, void* stream) {
@@ -1184,11 +1313,11 @@ int sd_op_res_conv(const void* x, int B, int H, int W, int Cin, const float* w, 
 namespace {
 void op_attention(const float* qkv, int S_, int T, int D, int nh, int causal, int causal_delay, const int* key_len,
                   int chunk, int left, float* out, int precision, hipStream_t st, int* mask_dump = nullptr,
-                  int grid_c = 0) {
+                  int grid_c = 0, float scale = 0.f) {
   SD_CHECK(precision >= 0 && precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
   sd::AttnArgs a;
   a.qkv = qkv; a.S = S_; a.T = T; a.D = D; a.nh = nh; a.ld_qkv = 3 * D;
-  a.out = out; a.ldo = D; a.scale = 1.f / std::sqrt((float)(D / nh));
+  a.out = out; a.ldo = D; a.scale = scale > 0.f ? scale : 1.f / std::sqrt((float)(D / nh));
   a.causal = causal; a.causal_delay = causal_delay; a.key_len = key_len;
   a.chunk = chunk; a.left = left;
   a.mask_dump = mask_dump;
@@ -1210,6 +1339,14 @@ void op_attention(const float* qkv, int S_, int T, int D, int nh, int causal, in
 int sd_op_attention(const float* qkv, int S_, int T, int D, int nh, int causal, int causal_delay,
                     const int* key_len, float* out, int precision, void* stream) {
   return guard([&] { op_attention(qkv, S_, T, D, nh, causal, causal_delay, key_len, 0, -1, out, precision, S(stream)); });
+}
+
+int sd_op_attention_scaled(const float* qkv, int S_, int T, int D, int nh, float scale, float* out, int precision,
+                           void* stream) {
+  return guard([&] {
+    SD_CHECK(qkv && out && scale > 0.f, sd::kErrInvalid, "attention_scaled: bad argument");
+    op_attention(qkv, S_, T, D, nh, 0, 0, nullptr, 0, -1, out, precision, S(stream), nullptr, 0, scale);
+  });
 }
 
 int sd_op_attention_grid(const float* qkv, int S_, int T, int C, int D, int nh, int causal, int causal_delay,

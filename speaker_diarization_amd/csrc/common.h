@@ -133,7 +133,16 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
 
 // kActClamp20: nn.Hardtanh(0, 20) (ERes2NetV2.py:21-24), NaN kept, +inf -> 20.  conv_gemm's exact kernels and, in bf16,
 // the LDS-DMA and the register-staged kernels apply it (conv_gemm_bf16 routes it to one of the two).
-enum Act : int { kActNone = 0, kActRelu = 1, kActSigmoid = 2, kActSilu = 3, kActClamp20 = 4 };
+// kActGelu: nn.GELU() (erf form); kActGeluTanh: the tanh form ("NewGELU", redimnet_wespeaker.py:56-61).  conv_gemm's
+// exact kernels, the skinny kernel and, in bf16, the register-staged kernel apply them (conv_gemm_bf16 routes them there).
+enum Act : int {
+  kActNone = 0, kActRelu = 1, kActSigmoid = 2, kActSilu = 3, kActClamp20 = 4, kActGelu = 5, kActGeluTanh = 6
+};
+
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
+__device__ __forceinline__ float gelu_tanh(float v) {
+  return 0.5f * v * (1.f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v)));
+}
 
 __device__ __forceinline__ float apply_act(float v, int act) {
   switch (act) {
@@ -141,6 +150,8 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     case kActSigmoid: return 1.f / (1.f + expf(-v));
     case kActSilu: return v / (1.f + expf(-v));
     case kActClamp20: return v < 0.f ? 0.f : (v > 20.f ? 20.f : v);
+    case kActGelu: return gelu_erf(v);
+    case kActGeluTanh: return gelu_tanh(v);
     default: return v;
   }
 }

@@ -387,9 +387,11 @@ void ecapa_se_apply(const void* x, int ldx, const void* y, const float* gate, in
 }
 
 void astp_pool(const AstpArgs& a, hipStream_t st) {
-  constexpr int C = 1536, H = 128;
+  constexpr int H = 128;
+  const int C = a.C;
   SD_CHECK(a.x && a.w1x && a.w1c && a.b1 && a.w2 && a.b2 && a.stats && a.ctx && a.cv && a.h && a.e, kErrInvalid,
            "astp_pool: null argument");
+  SD_CHECK(C >= 64 && C % 64 == 0, kErrInvalid, "astp_pool: C must be a multiple of 64");
   SD_CHECK(a.B >= 1 && a.B <= 65535, kErrInvalid, "astp_pool: 1 <= B <= 65535");
   SD_CHECK(a.T >= 2, kErrShape, "ASTP needs at least 2 frames (the unbiased variance of one frame is NaN)");
   SD_CHECK(!a.x_bf16 || a.x32, kErrInvalid, "astp_pool: a bf16 map needs the fp32 scratch copy");

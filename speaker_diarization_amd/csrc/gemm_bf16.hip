@@ -298,6 +298,8 @@ void conv_gemm_bf16(const ConvGemmArgs& p, hipStream_t st) {
   enum Path { kFcm, kAreg, kRing, kStream, kDma, kReg } path = kReg;
   if (p.act == kActClamp20)               // the clamp epilogue: the LDS-DMA kernel and this file's (apply_act at run time)
     path = (g_clamp_route == 0 && gemm_dma_supported(p)) ? kDma : kReg;
+  else if (p.act == kActGelu || p.act == kActGeluTanh)   // the GELU epilogues: this file's kernel (apply_act at run time)
+    path = kReg;
   else if (p.post_scale)                  // the post-activation affine: the ring GEMM's wide form, or this file's kernel
     path = gemm_ring_supported(p) ? kRing : kReg;
   else if (fcm_conv_supported(p))         // CAM++ FCM 3x3 32->32 convs (fcm_conv.hip)

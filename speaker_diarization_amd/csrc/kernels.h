@@ -252,6 +252,8 @@ struct AstpArgs {
   float* stats = nullptr;      // (B, 3072)
   float *ctx = nullptr, *cv = nullptr;   // scratch (B, 3072), (B, 128)
   float *x32 = nullptr, *h = nullptr, *e = nullptr;   // scratch (B T, 1536) (bf16 x only), (B T, 128), (B T, 1536)
+  // channels of x, C % 64 == 0: 1536 (ECAPA) or 1152 (ReDimNetB2); every 1536 / 3072 above scales with it
+  int C = 1536;
 };
 void astp_pool(const AstpArgs& a, hipStream_t st);
 // The pooling both attentive heads end with: a = softmax over T of the scores e (B, T, C) fp32, then in fp64 and a
@@ -354,6 +356,54 @@ void slice_add(void* x, int ldx, const void* y, int ldy, bool bf16, int64_t P, i
 // NHWC (B, H, W, C) -> fp32 (B, W, H * C) with channel h * C + c (get_frame_level_feat's transpose(1, 3) + flatten,
 // channel-last).
 void nhwc_to_frames(const void* x, bool bf16, int B, int H, int W, int C, float* out, hipStream_t st);
+
+// ---------------------------------------------------------------- redimnet (redimnet.hip)
+// ReDimNetB2 (redimnet_wespeaker.py:623-790) keeps every map channel-last as (B, T, 1152) with 1-D channel f * c + ch
+// (to1d's order, :758-761): the 2-D view (B, T, f, c) of a stage is the same memory, so to1d / to2d cost nothing.
+constexpr int kRedimCF = 1152;   // C * F = 16 * 72 at every stage
+// ConvNeXtLikeBlock, dim 2 (:135-165) on a (B, T, f, c) map, c in {16, 32, 64, 128}, f = 1152 / c: grouped 3x3 conv (4
+// channels per group, zero "same" padding at the time and the frequency edges of each window) + BatchNorm2d + erf GELU
+// + 1x1 conv + bias + skip.  dw: the grouped conv with the BatchNorm folded in, fp32, laid out
+// [tap = df * 3 + dt][group][out 4][in 4] (redim_pack_dw); dw_b: c folded biases.  pw: conv_gemm's packed Wt[c][c]
+// (bf16 bits or fp32), pw_b: c.
+struct RedimBlock2dW {
+  const float *dw = nullptr, *dw_b = nullptr;
+  const void* pw = nullptr;
+  const float* pw_b = nullptr;
+};
+// torch's (c, 4, 3, 3) grouped weight (kernel axes: frequency, time), its bias and the folded BatchNorm (s, h) ->
+// the dw / dw_b images above
+void redim_pack_dw(const float* w, const float* bias, const float* s, const float* h, int c, std::vector<float>& dw,
+                   std::vector<float>& dw_b);
+// The whole block in ONE launch (bf16 maps): a workgroup stages 8 time rows + a one-row halo of one window in LDS,
+// runs the grouped conv + GELU on the VALU into a second LDS map and the pointwise conv on MFMA, adds bias and skip
+// from the staged tile: one read and one write of the map.  out must not alias x.
+void redim_block2d_fused(const void* x, int B, int T, int c, const RedimBlock2dW& W, void* out, hipStream_t st);
+// The generic arm's first half: h = gelu(conv3x3_grouped(x) + b) to a map of x's type (fp32 or bf16); the pointwise
+// conv, bias and skip follow on conv_gemm with its residual.
+void redim_gconv3x3(const void* x, bool bf16, int B, int T, int c, const float* dw, const float* dw_b, void* h,
+                    hipStream_t st);
+// Both arms behind one call: generic (the only form of fp32 / bf16x3) or fused (bf16).  tmp: a map for the generic arm.
+void redim_block2d(const void* x, int B, int T, int c, const RedimBlock2dW& W, void* tmp, void* out, bool bf16,
+                   bool generic, hipStream_t st);
+// The front half of ConvNeXtLikeBlock, dim 1 (:586-607): depthwise conv over time (odd k <= 59, zero "same" padding
+// inside each window) + BatchNorm1d + erf GELU on x (B, T, hC) fp32, hC % 48 == 0 -> y (fp32 or bf16).  wt: (k, hC)
+// fp32 with the BatchNorm folded in, bias: hC folded.
+void redim_dwconv1d(const float* x, int B, int T, int hC, int k, const float* wt, const float* bias, void* y,
+                    bool y_bf16, hipStream_t st);
+// weigth1d (:768-772): y[r, ch] = sum_k w[k, ch] x_k[r, ch] over n = 2..7 maps of `rows` x 1152, w = softmax over k of
+// inputs_weights[i] (n, 1152) fp32, computed at upload.
+struct RedimMixArgs {
+  static constexpr int kMax = 7;
+  const void* x[kMax] = {};
+  int n = 0;
+  const float* w = nullptr;
+};
+void redim_stage_mix(const RedimMixArgs& a, int64_t rows, void* y, bool bf16, hipStream_t st);
+// stem (:670-673): Conv2d(1 -> 16, 3x3, same) on the (72, T) fbank map + channels-first LayerNorm over the 16
+// channels (eps 1e-6), written as (B, T, 72, 16).  w: (16, 3, 3) torch order (frequency, time), fp32.
+void redim_stem(const float* fbank, int B, int T, const float* w, const float* bias, const float* g, const float* beta,
+                void* out, bool out_bf16, hipStream_t st);
 
 // ---------------------------------------------------------------- norms
 // y = LN(x) * g + b over the last dim D; rows of x at stride ldx, y at ldy.

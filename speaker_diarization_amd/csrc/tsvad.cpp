@@ -6,11 +6,13 @@
 //          variants 0, 1: CAM++ FCM head + xvector[:-2]       cam_pplus_wespeaker.py:271-399
 //          variant 2 (speech_encoder_type resnet34_wespeaker, model.py:584-606): ResNet34 trunk (resnet.h)
 //          variant 3 (ecapa_channel_1024_wespeaker, model.py:631-654): ECAPA-TDNN trunk (ecapa.h)
+//          variant 4 (ReDimNetB2, egs/magicdata-ramc/ts_vad2/model.py:694-715): ReDimNetB2 trunk on 72-bin fbank
+//                    (redimnet.h), get_frame_level_feat (:1246-1262)
 //     -> speech_down_or_up (down_gemm) -> mix (B, T3, SE)
 //          variants 0, 1: conv + BN + ReLU                    model.py:385-395 / 406-416
 //          variant 2: SpeechFeatUpsample2 transposed conv + BN + ReLU (model.py:114-134)
-//          variant 3: conv k5 stride 4 pad 2 + BN + ReLU (model.py:641-654)
-//     -> transformer_backend, variants 0, 2 and 3 (forward_common, model.py:758-897):
+//          variants 3, 4: conv k5 stride 4 pad 2 + BN + ReLU (model.py:641-654; magicdata :703-715)
+//     -> transformer_backend, variants 0, 2, 3 and 4 (forward_common, model.py:758-897):
 //          [ts_embed | mix] + PE, 2-layer transformer per speaker (batched over speakers)
 //          -> backend_down conv(1536->384, k5)+BN+ReLU -> PE -> 2-layer transformer -> fc
 //        ots_vad_backend, variant 1 (forward_common_ots_vad, model.py:669-756):
@@ -50,6 +52,14 @@ void TsvadModel::build() {
   } else if (cfg_.variant == 3) {
     ecapa_ = std::make_unique<EcapaTrunk>();
     ecapa_->load(ps_, arena_, se, cfg_.bf16);   // ecapa_tdnn_wespeaker.py:161-209 (no pool / bn / linear keys)
+  } else if (cfg_.variant == 4) {
+    redim_ = std::make_unique<RedimTrunk>();
+    redim_->load(ps_, arena_, se, cfg_.bf16);   // redimnet_wespeaker.py:623-790
+    // ReDimNetB2(feat_dim=72, embed_dim=192, pooling_func="ASTP") is built whole (model.py:694-697); its pooling head
+    // is not on the get_frame_level_feat path
+    for (const char* k : {"pool.linear1.weight", "pool.linear1.bias", "pool.linear2.weight", "pool.linear2.bias",
+                          "seg_1.weight", "seg_1.bias"})
+      ps_.mark(se + k);
   } else {
     cam_ = std::make_unique<CamTrunk>();
     cam_->load(ps_, arena_, se, cfg_.bf16);   // cam_pplus_wespeaker.py:271-372
@@ -99,6 +109,14 @@ void TsvadModel::build() {
     down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
     SD_CHECK(down_.w.N == cfg_.speaker_embed_dim && down_.w.Cin == EcapaTrunk::kChannels && down_.w.kw == 5, kErrParam,
              "speech_down_or_up.0.weight must be (speaker_embed_dim, 1536, 5)");
+    SD_CHECK(ps_.get("speech_down_or_up.0.bias").numel() == cfg_.speaker_embed_dim, kErrParam,
+             "speech_down_or_up.0.bias size");
+    down_bn_ = bn_only("speech_down_or_up.1.bn");
+  } else if (cfg_.variant == 4) {
+    // Conv1d(1152 -> D, k5, stride 4, pad 2) (magicdata model.py:703-715) on the frame-level map: no prologue
+    down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
+    SD_CHECK(down_.w.N == cfg_.speaker_embed_dim && down_.w.Cin == RedimTrunk::kChannels && down_.w.kw == 5, kErrParam,
+             "speech_down_or_up.0.weight must be (speaker_embed_dim, 1152, 5)");
     SD_CHECK(ps_.get("speech_down_or_up.0.bias").numel() == cfg_.speaker_embed_dim, kErrParam,
              "speech_down_or_up.0.bias size");
     down_bn_ = bn_only("speech_down_or_up.1.bn");
@@ -185,6 +203,7 @@ void TsvadModel::alloc_workspace() {
   const int64_t Bm = cfg_.max_batch, NS = cfg_.max_num_speaker, E = cfg_.embed_dim;
   if (res_) res_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
   else if (ecapa_) ecapa_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
+  else if (redim_) redim_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
   else cam_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
   mix_ = ws(g.mix_elems);
   mixg_ = ws(g.mix_elems);
@@ -255,7 +274,7 @@ void TsvadModel::debug_buffer(int which, void** ptr, int64_t* bytes) const {
   }
 }
 
-// forward_common's back end from the mix embeddings on (model.py:856-897), shared by variants 0, 2 and 3: mix_ holds
+// forward_common's back end from the mix embeddings on (model.py:856-897), shared by variants 0, 2, 3 and 4: mix_ holds
 // speech_down_or_up's conv + bias (B, T3, SE); its BatchNorm1D + ReLU are applied on load (sd_bn).
 void TsvadModel::transformer_backend(const float* ts, int T3, int B, int Tl, float* logits, hipStream_t st,
                                      const BnRelu& sd_bn, const BnRelu& bd_bn) {
@@ -340,6 +359,14 @@ void TsvadModel::check_label_frames(int T3, int Tl) const {
     SD_CHECK(std::abs(T3 - Tl) <= 3, kErrShape, diff);
     return;
   }
+  if (cfg_.variant == 4) {
+    // egs/magicdata-ramc/ts_vad2/model.py:1296-1309: |gap| <= 3; a short encoder output is zero-padded by 1 to 3
+    // frames after the ReLU (the consumers read mix rows >= T3 as zeros), a long one is cut at the label length
+    SD_CHECK(std::abs(T3 - Tl) <= 3, kErrShape,
+             diff + ", label len: " + std::to_string(Tl) + ", ref_speech len: " + std::to_string(T3));
+    SD_CHECK(Tl <= pe_len_, kErrShape, "label length exceeds positional-encoding max_len");
+    return;
+  }
   // model.py:849-854; with the ResNet34 encoder the reference's own -1 branch raises too (its pad call is
   // misspelt: AttributeError)
   SD_CHECK(T3 - Tl <= 2 && T3 - Tl >= -1, kErrShape, diff);
@@ -371,6 +398,10 @@ void TsvadModel::run_sliced(int B, bool two, hipStream_t st,
 
 Tens TsvadModel::trunk_forward(const float* ref, int Bh, int Tf, hipStream_t s, int b0) const {
   if (ecapa_) return ecapa_->forward(ref, Bh, Tf, s, b0);
+  if (redim_) {
+    SD_CHECK(b0 == 0, kErrInvalid, "the ReDimNetB2 trunk runs over the whole batch");
+    return redim_->forward(ref, Bh, Tf, s);
+  }
   return res_ ? res_->forward(ref, Bh, Tf, s, b0) : cam_->forward(ref, Bh, Tf, s, b0);
 }
 
@@ -381,6 +412,8 @@ ConvGemmArgs TsvadModel::down_gemm(Tens x, int Bh, int Tf, float* out) const {
   if (res_) return cam_conv1d(x, Bh, ResTrunk::out_frames(Tf), ResTrunk::kChannels, down_, 1, 1, 1, Tens{out, false}, 2 * SE);
   // ECAPA: k5 stride-4 pad-2 conv over the unsubsampled (Bh, Tf, 1536) map
   if (ecapa_) return cam_conv1d(x, Bh, Tf, EcapaTrunk::kChannels, down_, 4, 2, 1, Tens{out, false}, SE);
+  // ReDimNetB2: the same conv over the unsubsampled (Bh, Tf, 1152) frame-level map
+  if (redim_) return cam_conv1d(x, Bh, Tf, RedimTrunk::kChannels, down_, 4, 2, 1, Tens{out, false}, SE);
   // CAM++: k5 stride-2 pad-2 conv, out_nonlinear's BN-ReLU fused as its prologue
   return cam_conv1d(x, Bh, CamTrunk::out_frames(Tf), CamTrunk::kChannels, down_, 2, 2, 1, Tens{out, false}, SE);
 }
@@ -396,8 +429,8 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   SD_CHECK(forward_batch >= 0 && force >= 0 && force <= 3, kErrInvalid, "forward: bad forward_batch / force");
   require_finalized();
   SD_CHECK(B >= 1 && B <= cfg_.max_batch, kErrInvalid, "batch exceeds max_batch");
-  // ECAPA never subsamples inside the trunk: any window of at least one frame runs
-  SD_CHECK(Tf >= (cfg_.variant == 3 ? 1 : 8) && Tf <= cfg_.max_fbank_frames, kErrInvalid,
+  // ECAPA and ReDimNetB2 never subsample inside the trunk: any window of at least one frame runs
+  SD_CHECK(Tf >= (cfg_.variant >= 3 ? 1 : 8) && Tf <= cfg_.max_fbank_frames, kErrInvalid,
            "fbank frames exceed max_fbank_frames");
   raise_if_set();
   const int T3 = mix_frames(Tf);
@@ -410,7 +443,7 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   // Under the libsdiar kernel timer (bench.py's extra profiled step) the forward stays on one stream, so
   // each kernel's HIP-event time is its own and not shared with the other slice's kernels.
   static const bool one_stream_env = getenv("SDIAR_CAM_ONE_STREAM") != nullptr;
-  const bool two = !(one_stream_env || prof_enabled()) && B >= 384;
+  const bool two = !(one_stream_env || prof_enabled()) && B >= 384 && !redim_;   // RedimTrunk takes no window slice
   // ---------------- BatchNorm1D's NaN bypass: which windows hold a non-finite input, which reference forwards
   // (groups of forward_batch windows) therefore skip the BatchNorm (from the inputs alone, so first: the window
   // slices below then need nothing from each other until the LSTM)
@@ -420,7 +453,7 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   int* grp_sd = nonfinite_ + 2 * cfg_.max_batch;
   int* grp_bd = nonfinite_ + 3 * cfg_.max_batch;
   zero_fill(nonfinite_, 4 * (size_t)cfg_.max_batch * sizeof(int), st);
-  nonfinite_windows(ref, B, (int64_t)Tf * 80, G, win_fb, grp_sd, grp_bd, st);
+  nonfinite_windows(ref, B, (int64_t)Tf * feat_dim(), G, win_fb, grp_sd, grp_bd, st);
   nonfinite_windows(ts, B, (int64_t)NS * SE, G, win_ts, nullptr, cfg_.variant != 1 ? grp_bd : nullptr, st);
   if (force & 1) fill_u32(grp_sd, (size_t)cfg_.max_batch * sizeof(int), 1u, st);
   if (force & 3) fill_u32(grp_bd, (size_t)cfg_.max_batch * sizeof(int), 1u, st);

@@ -5,6 +5,7 @@
 #include <vector>
 #include "campp.h"
 #include "ecapa.h"
+#include "redimnet.h"
 #include "resnet.h"
 
 namespace sd {
@@ -13,6 +14,8 @@ struct TsvadConfig {
   int variant = 0;            // 0: CAM++ + transformer (model.py:758-897); 1: CAM++_ots_vad (669-756);
                               // 2: resnet34_wespeaker + SpeechFeatUpsample2 + transformer (584-606, 114-134)
                               // 3: ecapa_channel_1024_wespeaker + conv k5 stride 4 + transformer (631-654)
+                              // 4: ReDimNetB2 on 72-bin fbank + conv k5 stride 4 + transformer
+                              //    (egs/magicdata-ramc/ts_vad2/model.py:694-715, 1246-1262, 1296-1309)
   int max_num_speaker = 4;
   int rs_len = 4;
   int max_batch = 64;
@@ -36,7 +39,7 @@ class TsvadModel : public ModelCore {
   // Raises kErrInvalid for a configuration the runner does not build (sd_tsvad_create calls it): with
   // speaker_embed_dim * 2 != embed_dim the reference inserts proj_layer (model.py:212-217), built for variants 0, 2 and 3.
   static void validate(const TsvadConfig& c);
-  // ref_speech (B, T_fb, 80) fbank, target_speech (B, NS, speaker_embed_dim), logits out (B, NS, T_lab).
+  // ref_speech (B, T_fb, 80) fbank ((B, T_fb, 72) for variant 4), target_speech (B, NS, speaker_embed_dim), logits out (B, NS, T_lab).
   // forward_batch: windows per reference forward call, the scope of BatchNorm1D's NaN bypass (model.py:161-171),
   // i.e. the batch a NaN window disables speech_down_or_up's / backend_down's BatchNorm for; 0: the whole call.
   // force: the call is part of a larger reference batch that holds a non-finite input elsewhere: bit 0 skips
@@ -94,10 +97,12 @@ class TsvadModel : public ModelCore {
   std::unique_ptr<CamTrunk> cam_;   // CAM++, variants 0 and 1
   std::unique_ptr<ResTrunk> res_;   // ResNet34, variant 2
   std::unique_ptr<EcapaTrunk> ecapa_;   // ECAPA-TDNN c1024, variant 3
+  std::unique_ptr<RedimTrunk> redim_;   // ReDimNetB2, variant 4
+  int feat_dim() const { return cfg_.variant == 4 ? RedimTrunk::kF : 80; }   // mel bins of ref_speech
   // frames of the speech_down_or_up output for T_fb fbank frames (the conv's stride 2, the upsampler's 2 T', or
-  // ECAPA's stride 4 on the unsubsampled time axis)
+  // ECAPA's and ReDimNetB2's stride 4 on the unsubsampled time axis)
   int mix_frames(int Tf) const {
-    if (cfg_.variant == 3) return (Tf - 1) / 4 + 1;
+    if (cfg_.variant == 3 || cfg_.variant == 4) return (Tf - 1) / 4 + 1;
     return cfg_.variant == 2 ? 2 * ResTrunk::out_frames(Tf) : (CamTrunk::out_frames(Tf) - 1) / 2 + 1;
   }
   // the back end of forward_common (variant 0's; also behind the ResNet34 and ECAPA encoders)

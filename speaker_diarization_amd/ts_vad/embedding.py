@@ -461,6 +461,92 @@ class ECAPA_TDNN_GLOB_c1024(_lib.Handle):
         return out
 
 
+class ReDimNetB2(_lib.Handle):
+    """egs/magicdata-ramc/ts_vad2/redimnet_wespeaker.py:925-948 (ReDimNet :793-872): the WeSpeaker ReDimNetB2 embedding
+    extractor (stem, six stages of ConvNeXt-like 2-D blocks and a conv + attention time-context block on a (B, T, 1152)
+    map that is never subsampled, ASTP with the global context, seg_1) run by libsdiar (`sd_redimnet_*`).  Same
+    constructor arguments and state_dict keys; forward(x) -> (tensor(0.0), embed_a), the reference's pair;
+    get_frame_level_feat(x) -> (B, T, 1152).  Use with extract_embed(..., n_mels=72).  Deviation: forward with T < 2
+    raises (AssertionError) where the reference returns a non-finite embedding; get_frame_level_feat works from T = 1."""
+    kind = "redimnet"
+
+    def __init__(self, feat_dim: int = 72, embed_dim: int = 192, pooling_func: str = "ASTP", two_emb_layer: bool = False,
+                 *, device=None, precision: str = "bf16", max_batch: int = 96, max_frames: int = 598):
+        if feat_dim != 72:
+            raise ValueError(f"the MI355X ReDimNetB2 supports feat_dim 72 only, got {feat_dim}")
+        if pooling_func != "ASTP":
+            raise ValueError(f"the MI355X ReDimNetB2 builds ASTP pooling only, got {pooling_func}")
+        if two_emb_layer:
+            raise ValueError("the MI355X ReDimNetB2 builds two_emb_layer=False only (the extractor's setting)")
+        code = _lib.precision_code(precision)
+        self.device = _lib.hip_device(device, "ReDimNetB2")
+        self.feat_dim, self.embed_dim, self.two_emb_layer = feat_dim, embed_dim, False
+        self.embedding_size = embed_dim      # what extract_embed sizes its output with
+        self.precision, self.max_batch, self.max_frames = precision, max_batch, max_frames
+        self._create(_lib.RedimnetConfig(feat_dim=feat_dim, embed_dim=embed_dim, max_batch=max_batch,
+                                         max_frames=max_frames, precision=code))
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        if not strict:
+            raise ValueError("the MI355X backend only supports strict=True loading")
+        self._load(unwrap_checkpoint(state_dict, kind="redimnet"))
+        return self
+
+    def eval(self):
+        return self
+
+    def to(self, device):
+        import torch
+        if torch.device(device) != self.device:
+            raise ValueError("re-create the model on the target device")
+        return self
+
+    @property
+    def device_bytes(self) -> int:
+        return self._device_bytes()
+
+    def _input(self, x):
+        import torch
+        if x.dim() != 3 or x.shape[2] != self.feat_dim:
+            raise ValueError(f"expected (B, T, {self.feat_dim}) fbank, got {tuple(x.shape)}")
+        return x.to(self.device, torch.float32).contiguous()
+
+    def forward(self, x, out=None):
+        """x (B, T, 72) -> (tensor(0.0), embed_a (B, embed_dim)) (redimnet_wespeaker.py:861-872).  T >= 2."""
+        import torch
+        if x.dim() == 3 and x.shape[1] < 2:
+            raise AssertionError("ReDimNetB2 embeddings need at least 2 fbank frames (ASTP's unbiased variance of one "
+                                 "frame is NaN)")
+        x = self._input(x)
+        B, T, _ = x.shape
+        if B > self.max_batch:
+            parts = [self.forward(x[s:s + self.max_batch], None if out is None else out[s:s + self.max_batch])[1]
+                     for s in range(0, B, self.max_batch)]
+            return torch.tensor(0.0), (out if out is not None else torch.cat(parts))
+        if out is None:
+            out = torch.empty(B, self.embed_dim, device=self.device, dtype=torch.float32)
+        _lib.call("sd_redimnet_forward", self._h, _lib.ptr(x), B, T, _lib.ptr(out), None, _lib.stream_ptr(self.device))
+        return torch.tensor(0.0), out
+
+    __call__ = forward
+
+    def get_frame_level_feat(self, x):
+        """x (B, T, 72) -> (B, T, 1152), channel f * c + ch (redimnet_wespeaker.py:855-859)."""
+        import torch
+        x = self._input(x)
+        B, T, _ = x.shape
+        if B > self.max_batch:
+            return torch.cat([self.get_frame_level_feat(x[s:s + self.max_batch]) for s in range(0, B, self.max_batch)])
+        fo = torch.empty(B, T, 1152, device=self.device, dtype=torch.float32)
+        _lib.call("sd_redimnet_forward", self._h, _lib.ptr(x), B, T, None, _lib.ptr(fo), _lib.stream_ptr(self.device))
+        return fo
+
+    def use_generic_blocks(self, on: bool):
+        """Tests and tools/redimnet_probe.py: run the 2-D blocks of a bf16 model as the generic arm."""
+        _lib.call("sd_redimnet_debug_generic", self._h, int(bool(on)))
+        return self
+
+
 def kaldi_fbank_povey(wav, n_mels: int = 80, out=None):
     """Kaldi.fbank(wav, num_mel_bins, sample_frequency=16000, dither=0) (povey window,
     samples as read, no 2^15 scale): 1-D float32 CUDA tensor -> (n_frames, n_mels)."""

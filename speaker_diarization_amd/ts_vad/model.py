@@ -69,7 +69,7 @@ class TSVADModel(_lib.Handle):
     # ------------------------------------------------------------------ forward
     def forward(self, ref_speech, target_speech, labels, num_updates: int = 0, out=None, check: bool = True,
                 forward_batch: int = 0, _force: int = 0):
-        """ref_speech (B, T_fb, 80), target_speech (B, NS, speaker_embed_dim), labels (B, NS, T) (only
+        """ref_speech (B, T_fb, 80) ((B, T_fb, 72) with the ReDimNetB2 speech encoder), target_speech (B, NS, speaker_embed_dim), labels (B, NS, T) (only
         labels.size(-1) is read, model.py:681/770) -> logits (B, NS, T).  check: wait for the
         stream and raise RuntimeError in this call if the BiLSTM's persistent recurrence lost
         co-residency (its logits are NaN); check=False defers that to status().
@@ -82,7 +82,7 @@ class TSVADModel(_lib.Handle):
         import torch
         B, T_fb, F = ref_speech.shape
         T_lab = labels if isinstance(labels, int) else labels.size(-1)
-        assert F == 80, "CAM++ expects 80-dim fbank"
+        assert F == self.cfg.n_mels, f"{self.cfg.speech_encoder_type} expects {self.cfg.n_mels}-dim fbank"
         ref = ref_speech.to(self.device, torch.float32).contiguous()
         ts = target_speech.to(self.device, torch.float32).contiguous()
         assert ts.shape == (B, self.max_num_speaker, self.cfg.speaker_embed_dim)

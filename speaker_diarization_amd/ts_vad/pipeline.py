@@ -88,7 +88,7 @@ class TSVADPipeline:
         fn = _plan_i32(plan, "fn", plan.fbank_n[w0:w1], dev, w0, w1)
         batches = self.device_batches(plan, w0, w1)
         ts_all = _ts_block(ts, dev, NS, max(b1 - b0 for b0, b1, _, _ in batches))
-        feats = kaldi_fbank(wav[s0:s1])
+        feats = kaldi_fbank(wav[s0:s1], n_mels=getattr(self.cfg, "n_mels", 80))   # 72 bins for the ReDimNetB2 encoder
         for b0, b1, T_out, T_lab in batches:
             ref = window_cmn(feats, fstart[b0 - w0:b1 - w0], fn[b0 - w0:b1 - w0], T_out)
             dst = out[b0 - w0:b1 - w0]

@@ -43,6 +43,12 @@ class TSVADConfig:
     sample_rate: int = 16000
 
     @property
+    def n_mels(self) -> int:
+        """Mel bins of ref_speech: ReDimNetB2 reads 72-bin fbank (egs/magicdata-ramc/ts_vad2/model.py:694-697), every
+        other speech encoder built here 80."""
+        return 72 if self.speech_encoder_type == "ReDimNetB2" else 80
+
+    @property
     def variant(self) -> int:
         if self.ots_vad_style == "v1":
             if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) != (
@@ -55,13 +61,16 @@ class TSVADConfig:
         if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) == (
                 "ecapa_channel_1024_wespeaker", "transformer", "transformer"):
             return 3
+        if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) == (
+                "ReDimNetB2", "transformer", "transformer"):
+            return 4
         if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) != (
                 "CAM++", "transformer", "transformer"):
             raise ValueError(
                 f"unsupported TS-VAD configuration {self.speech_encoder_type}/"
                 f"{self.single_backend_type}/{self.multi_backend_type} (MI355X backend builds CAM++ "
-                "with transformer or conformer_ots_vad/lstm_ots_vad, resnet34_wespeaker and "
-                "ecapa_channel_1024_wespeaker with transformer)")
+                "with transformer or conformer_ots_vad/lstm_ots_vad, resnet34_wespeaker, "
+                "ecapa_channel_1024_wespeaker and ReDimNetB2 with transformer)")
         return 0
 
     @staticmethod
@@ -291,6 +300,67 @@ def ecapa_embed_layout(embed_dim: int = 192) -> list:
     return k
 
 
+# ReDimNetB2 stages_setup (redimnet_wespeaker.py:934-941): (stride, 2-D blocks, 1-D reduction), and the depthwise kernel
+# sizes of TimeContextBlock1d's "conv+att" form (:586-607).
+REDIM_STAGES = ((1, 2, 12), (2, 2, 12), (1, 3, 12), (2, 4, 8), (1, 4, 8), (2, 4, 4))
+REDIM_KERNELS = (7, 19, 31, 59)
+REDIM_CF = 1152
+
+
+def redimnet_layout(prefix: str = "", embed_dim: int = 192) -> list:
+    """Key layout of ReDimNetB2(feat_dim=72, embed_dim, pooling_func="ASTP", two_emb_layer=False)
+    (redimnet_wespeaker.py:925-948; ReDimNet :793-845, ReDimNetBone.build :654-756): the per-stage input weights, the
+    stem, six stages of (entry conv, ConvNeXt-like 2-D blocks, to1d, TimeContextBlock1d) — to1d has no parameters, so
+    the 1-D block sits at index blocks + 2 — then ASTP with the global context and seg_1.  548 keys."""
+    k: list = []
+    bb, cf = prefix + "backbone.", REDIM_CF
+
+    def conv(p: str, shape, kind: str):
+        k.append((p + ".weight", shape, kind))
+        k.append((p + ".bias", (shape[0],), "small"))
+
+    k.append((bb + "inputs_weights.0", (1, 1, 1, 1), "ones"))
+    for i in range(1, len(REDIM_STAGES) + 1):
+        k.append((bb + f"inputs_weights.{i}", (1, i + 1, cf, 1), "rd_mix"))
+    conv(bb + "stem.0", (16, 1, 3, 3), "rd_conv")
+    k.append((bb + "stem.1.weight", (16,), "rd_ln_w"))
+    k.append((bb + "stem.1.bias", (16,), "small"))
+    c = 16
+    for i, (stride, blocks, red) in enumerate(REDIM_STAGES):
+        sp = f"{bb}stage{i}."
+        conv(sp + "0", (c * stride, c, stride, 1), "rd_conv")
+        c *= stride
+        for b in range(1, blocks + 1):
+            q = f"{sp}{b}.conv_block."
+            conv(q + "dwconvs.0", (c, 4, 3, 3), "rd_conv")
+            _bn(k, q + "norm", c, kind="rd")
+            conv(q + "pwconv1", (c, c, 1, 1), "rd_out")
+        t, hc = f"{sp}{blocks + 2}.", cf // red
+        conv(t + "red_dim_conv.0", (hc, cf, 1), "rd_conv")
+        k.append((t + "red_dim_conv.1.weight", (hc,), "rd_ln_w"))
+        k.append((t + "red_dim_conv.1.bias", (hc,), "small"))
+        for j, ks in enumerate(REDIM_KERNELS):
+            q = f"{t}tcm.{j}."
+            conv(q + "dwconvs.0", (hc, 1, ks), "rd_conv")
+            _bn(k, q + "norm", hc, kind="rd")
+            conv(q + "pwconv1", (hc, hc, 1), "rd_out")
+        a = t + "tcm.4."
+        for n in ("k_proj", "v_proj", "q_proj"):
+            conv(a + "attention." + n, (hc, hc), "rd_conv")
+        conv(a + "attention.out_proj", (hc, hc), "rd_out")
+        k.append((a + "layer_norm.weight", (hc,), "rd_ln_w"))
+        k.append((a + "layer_norm.bias", (hc,), "small"))
+        conv(a + "feed_forward.intermediate_dense", (hc, hc), "rd_conv")
+        conv(a + "feed_forward.output_dense", (hc, hc), "rd_out")
+        k.append((a + "final_layer_norm.weight", (hc,), "rd_ln_w"))
+        k.append((a + "final_layer_norm.bias", (hc,), "small"))
+        conv(t + "exp_dim_conv", (cf, hc, 1), "rd_out")
+    conv(prefix + "pool.linear1", (128, 3 * cf, 1), "ec_att1")
+    conv(prefix + "pool.linear2", (cf, 128, 1), "ec_att2")
+    conv(prefix + "seg_1", (embed_dim, 2 * cf), "kaiming")
+    return k
+
+
 def _mha(k: list, p: str, e: int):
     k.append((p + "in_proj_weight", (3 * e, e), "xavier"))
     k.append((p + "in_proj_bias", (3 * e,), "small"))
@@ -318,6 +388,13 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         k.append(("speech_down_or_up.0.weight", (se, 1536, 5), "ec_down"))
         k.append(("speech_down_or_up.0.bias", (se,), "small"))
         _bn(k, "speech_down_or_up.1.bn", se)
+    elif cfg.variant == 4:
+        # ReDimNetB2 (with its pool / seg_1, which the reference builds and never runs here) + Conv1d(1152 -> D, k5,
+        # stride 4, pad 2) (egs/magicdata-ramc/ts_vad2/model.py:694-715); the back end is variant 0's
+        k = redimnet_layout("speech_encoder.")
+        k.append(("speech_down_or_up.0.weight", (se, REDIM_CF, 5), "ec_down"))
+        k.append(("speech_down_or_up.0.bias", (se,), "small"))
+        _bn(k, "speech_down_or_up.1.bn", se)
     else:
         k = campplus_layout()
         if cfg.variant == 1:
@@ -331,7 +408,7 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         # 873-874); the reference registers it for every variant, its ots_vad forward never applies it
         k.append(("proj_layer.weight", (e, 2 * se), "linear"))
         k.append(("proj_layer.bias", (e,), "small"))
-    if cfg.variant in (0, 2, 3):
+    if cfg.variant in (0, 2, 3, 4):
         k.append(("pos_encoder.pe", (cfg.rs_len * cfg.label_rate, 1, e), "pe"))
         for i in range(cfg.num_transformer_layer):
             _tfm(k, f"single_backend.layers.{i}.", e, cfg.transformer_ffn_embed_dim)
@@ -434,6 +511,14 @@ ER_GAIN = {"er_conv1": 0.8, "er_conv": 1.0, "er_conv3": 0.6, "er_sc": 0.6, "er_a
 ER_BN_BIAS = 0.3
 
 
+# Seeded ReDimNetB2 init (redimnet_layout): He-normal times a per-role gain, the convs that close a residual branch
+# (pwconv1, out_proj, output_dense, exp_dim_conv) damped so that 22 + 24 skip sums stay O(1); BatchNorm running
+# statistics spread (mean +- 0.3, variance 0.5 .. 1.5), LayerNorm gains 0.7 .. 1.3 and inputs_weights of +- 0.5, so a
+# BatchNorm on the wrong side, a unit LayerNorm gain or a swapped stage order each move the outputs by O(1).
+# tests/golden/make_golden_redimnet.py asserts the reference's frame-level maps have a standard deviation in [0.1, 10].
+RD_GAIN = {"rd_conv": 1.0, "rd_out": 0.5}
+
+
 def _init(rng: np.random.Generator, shape: Shape, kind: str) -> np.ndarray:
     if kind == "nbt":
         return np.array(0, dtype=np.int64)
@@ -457,6 +542,20 @@ def _init(rng: np.random.Generator, shape: Shape, kind: str) -> np.ndarray:
         v = rng.standard_normal(n) * (SAM_GAIN[kind] * np.sqrt(2.0 / fan_in))
     elif kind in ER_GAIN:                 # ERes2NetV2 convs: He-normal times a per-role gain
         v = rng.standard_normal(n) * (ER_GAIN[kind] * np.sqrt(2.0 / fan_in))
+    elif kind in RD_GAIN:                 # ReDimNetB2 convs / linears: He-normal times a per-role gain
+        v = rng.standard_normal(n) * (RD_GAIN[kind] * np.sqrt(2.0 / fan_in))
+    elif kind == "rd_mix":                # inputs_weights: far from the all-zero init, so the stage order matters
+        v = rng.standard_normal(n) * 0.5
+    elif kind in ("rd_w", "rd_ln_w"):
+        v = rng.uniform(0.7, 1.3, n)
+    elif kind == "rd_b":
+        v = rng.standard_normal(n) * 0.1
+    elif kind == "rd_m":
+        v = rng.standard_normal(n) * 0.3
+    elif kind == "rd_v":
+        v = rng.uniform(0.5, 1.5, n)
+    elif kind == "ones":
+        v = np.ones(n)
     elif kind in ("er_w", "er_m", "er_v"):
         return _init(rng, shape, "bn" + kind[2:])
     elif kind == "er_b":
@@ -683,6 +782,11 @@ def eres2netv2_state_dict(seed: int = 777, base_width: int = 26, scale: int = 2,
 def ecapa_embed_state_dict(seed: int = 777, embed_dim: int = 192):
     """Seeded weights for a standalone ECAPA_TDNN_GLOB_c1024 extractor (keys layer*.*, conv.*, pool.*, bn.*, linear.*)."""
     return synthetic_state_dict(ecapa_embed_layout(embed_dim), seed)
+
+
+def redimnet_embed_state_dict(seed: int = 777, embed_dim: int = 192):
+    """Seeded weights for a standalone ReDimNetB2 extractor (keys backbone.*, pool.*, seg_1.*; redimnet_layout)."""
+    return synthetic_state_dict(redimnet_layout("", embed_dim), seed)
 
 
 def to_torch(sd):
