@@ -660,6 +660,15 @@ int sd_op_cam_dense(const void* x, int B, int T, int ld, int cin, int dil, const
                     const float* wb, const float* a2, const float* b2, const float* wl, const float* bl,
                     const float* w1, const float* c1, const float* w2, const float* c2, void* out, int repeats,
                     void* stream);
+/* One BasicResBlock of the CAM++ FCM head (cam_pplus_wespeaker.py:240-268) on a bf16 NHWC map x (B, H, W, 32):
+ * out bf16 NHWC (B, (H - 1) / stride + 1, W, 32) = relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut), 3x3 convs
+ * with pad 1, conv1 with freq stride `stride` (1 or 2).  w1 / w2 fp32 (32, 32, 3, 3) (rounded to bf16), a / b the
+ * folded BatchNorms [32].  stride 1: identity shortcut, wsc / asc / bsc NULL; stride 2: wsc fp32 (32, 32, 1, 1),
+ * shortcut = conv1x1(x, stride (2, 1)) * asc + bsc.  fused 1: one launch (fcm_conv.hip fcm_block_kernel; out
+ * must not overlap x); 0: the trunk's two launches on scratch maps.  Both give the same values. */
+int sd_op_fcm_block(const void* x, int B, int H, int W, int stride, const float* w1, const float* a1, const float* b1,
+                    const float* w2, const float* a2, const float* b2, const float* wsc, const float* asc,
+                    const float* bsc, void* out, int fused, void* stream);
 /* Diagnostics: while `stamps` (device, >= 16 u64 per workgroup of a launch) is non-NULL, every cam_dense
  * launch records its workgroups' phase-boundary s_memrealtime stamps there (tools/cam_dense_probe.py). */
 int sd_debug_cam_dense_probe(void* stamps);

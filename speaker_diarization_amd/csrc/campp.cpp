@@ -113,6 +113,25 @@ float* run_res_block(const ResBlockL& rb, float* const bufs[3], float* cur, bool
 }
 
 // ------------------------------------------------------------------------------ CamTrunk
+// One FCM BasicResBlock as two launches: conv1 (+ the 1x1 shortcut on its centre tap, + with stem.fbank the FCM stem
+// computed in LDS from the fbank; fcm_conv.hip FcmFuse), then conv2 + residual.  Where the fused conv1 does not
+// apply, the stem map is written to `cur` first (fcm_conv1) and conv_gemm serves conv1 and the shortcut.
+float* fcm_block_pair(const ResBlockL& rb, float* const bufs[3], float* cur, bool bf, int B, int& H, int& W,
+                      const FcmFuse& stem, hipStream_t st) {
+  auto conv1 = [&](const ConvGemmArgs& p, float* t2) {
+    FcmFuse fu = stem;
+    if (rb.has_sc) {
+      fu.sc_w = rb.sc.w.w; fu.sc_alpha = rb.sc.alpha; fu.sc_beta = rb.sc.beta; fu.sc_out = t2;
+    }
+    const bool fused = bf && rb.has_sc && rb.sc.w.N == 32 && rb.sc.w.K == 32 && fcm_fused_supported(p, fu);
+    if (stem.fbank && !fused) fcm_conv1(stem.fbank, B, p.W, stem.fb_F, stem.stem_w, stem.stem_alpha, stem.stem_beta, cur, bf, st);
+    if (fused) conv_fcm3x3_fused(p, fu, st);
+    else conv_gemm(p, bf, st);
+    return fused;
+  };
+  return run_res_block(rb, bufs, cur, bf, B, H, W, 1, conv1, [&](ConvGemmArgs& r) { conv_gemm(r, bf, st); }, st);
+}
+
 void CamTrunk::load(ParamStore& ps, DeviceArena& arena, const std::string& pre, bool bf16) {
   bf16_ = bf16;
   auto conv_bn = [&](const std::string& w, const std::string& bn, const std::string& bias = "") {
@@ -227,22 +246,28 @@ Tens CamTrunk::forward(const float* fbank, int B, int Tf, hipStream_t st, int b0
   float* const bufs[3] = {fcmA, fcmB, fcmC};
   for (size_t i = 0; i < fcm_blocks_.size(); ++i) {
     const ResBlockL& rb = fcm_blocks_[i];
-    auto conv1 = [&](const ConvGemmArgs& p, float* t2) {
-      FcmFuse fu;
-      if (rb.has_sc) {
-        fu.sc_w = rb.sc.w.w; fu.sc_alpha = rb.sc.alpha; fu.sc_beta = rb.sc.beta; fu.sc_out = t2;
+    if (bf && i > 0 && fcm_block_enabled()) {   // the whole block in one launch (layer1.0 keeps its stem-fused pair)
+      FcmBlockArgs a;
+      a.x = cur; a.B = B; a.H = H; a.W = W; a.C = rb.c1.w.Cin; a.stride = rb.stride; a.bf16 = true;
+      a.w1 = rb.c1.w.w; a.a1 = rb.c1.alpha; a.b1 = rb.c1.beta;
+      a.w2 = rb.c2.w.w; a.a2 = rb.c2.alpha; a.b2 = rb.c2.beta;
+      if (rb.has_sc) { a.wsc = rb.sc.w.w; a.asc = rb.sc.alpha; a.bsc = rb.sc.beta; }
+      a.out = bufs[0] != cur ? bufs[0] : bufs[1];   // both 80-row buffers hold any block's output
+      const bool w32 = rb.c1.w.N == 32 && rb.c1.w.K == 288 && rb.c2.w.N == 32 && rb.c2.w.K == 288 &&
+                       (!rb.has_sc || (rb.sc.w.N == 32 && rb.sc.w.K == 32)) && rb.has_sc == (rb.stride == 2);
+      if (w32 && fcm_block_supported(a)) {
+        conv_fcm_block(a, st);
+        cur = static_cast<float*>(a.out);
+        H = (H - 1) / rb.stride + 1;
+        continue;
       }
-      if (i == 0) {
-        fu.fbank = ref; fu.fb_F = F;
-        fu.stem_w = fcm_conv1_.pre_s; fu.stem_alpha = fcm_conv1_.alpha; fu.stem_beta = fcm_conv1_.beta;
-      }
-      const bool fused = bf && rb.has_sc && rb.sc.w.N == 32 && rb.sc.w.K == 32 && fcm_fused_supported(p, fu);
-      if (i == 0 && !fused) fcm_conv1(ref, B, Tf, F, fcm_conv1_.pre_s, fcm_conv1_.alpha, fcm_conv1_.beta, fcmA, bf, st);
-      if (fused) conv_fcm3x3_fused(p, fu, st);
-      else conv_gemm(p, bf, st);
-      return fused;
-    };
-    cur = run_res_block(rb, bufs, cur, bf, B, H, W, 1, conv1, [&](ConvGemmArgs& r) { conv_gemm(r, bf, st); }, st);
+    }
+    FcmFuse stem;
+    if (i == 0) {
+      stem.fbank = ref; stem.fb_F = F;
+      stem.stem_w = fcm_conv1_.pre_s; stem.stem_alpha = fcm_conv1_.alpha; stem.stem_beta = fcm_conv1_.beta;
+    }
+    cur = fcm_block_pair(rb, bufs, cur, bf, B, H, W, stem, st);
   }
   {
     // head.conv2 (stride (2,1)) + bn2 + relu, stored as (B, T, C*F') with channel c*F'+f.

@@ -62,6 +62,11 @@ float* run_res_block(const ResBlockL& rb, float* const bufs[3], float* cur, bool
                      const std::function<void(ConvGemmArgs& r)>& conv2, hipStream_t st,
                      const ResBlockIO& io = ResBlockIO());
 
+// One BasicResBlock of the CAM++ FCM head as its two launches (the path beside conv_fcm_block, and what
+// sd_op_fcm_block's fused = 0 runs).  stem.fbank set (layer1.0): the block's input is the FCM stem of that fbank.
+float* fcm_block_pair(const ResBlockL& rb, float* const bufs[3], float* cur, bool bf, int B, int& H, int& W,
+                      const FcmFuse& stem, hipStream_t st);
+
 class CamTrunk {
  public:
   static constexpr int kChannels = 512;   // transit3 output width

@@ -1220,6 +1220,48 @@ int sd_op_cam_dense(const void* x, int B, int T, int ld, int cin, int dil, const
   });
 }
 
+int sd_op_fcm_block(const void* x, int B, int H, int W, int stride, const float* w1, const float* a1, const float* b1,
+                    const float* w2, const float* a2, const float* b2, const float* wsc, const float* asc,
+                    const float* bsc, void* out, int fused, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && out && w1 && a1 && b1 && w2 && a2 && b2 && B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2),
+             sd::kErrInvalid, "fcm_block: bad argument");
+    SD_CHECK(stride == 2 ? (wsc && asc && bsc) : !wsc, sd::kErrInvalid, "fcm_block: the shortcut goes with stride 2");
+    PackedScratch p1(w1, 32, 32, 9, true, st), p2(w2, 32, 32, 9, true, st), ps(wsc, 32, 32, 1, true, st);
+    const int Ho = (H - 1) / stride + 1;
+    if (fused) {
+      sd::FcmBlockArgs a;
+      a.x = x; a.B = B; a.H = H; a.W = W; a.stride = stride;
+      a.w1 = p1.p; a.a1 = a1; a.b1 = b1; a.w2 = p2.p; a.a2 = a2; a.b2 = b2;
+      if (wsc) { a.wsc = ps.p; a.asc = asc; a.bsc = bsc; }
+      a.out = out;
+      sd::conv_fcm_block(a, st);   // raises on arguments the kernel cannot compute
+      return;
+    }
+    // the trunk's two launches on three maps of its own (the pair overwrites its input map when it has a shortcut)
+    const size_t in_bytes = (size_t)B * H * W * 64;
+    Scratch m0(in_bytes, st), m1(in_bytes, st), m2(in_bytes, st);
+    SD_HIP(hipMemcpyAsync(m0.p, x, in_bytes, hipMemcpyDeviceToDevice, st));
+    sd::ResBlockL rb;
+    rb.stride = stride;
+    rb.has_sc = wsc != nullptr;
+    auto conv = [](const void* w, int taps, const float* al, const float* be) {
+      sd::ConvL L;
+      L.w.w = w; L.w.N = 32; L.w.Cin = 32; L.w.K = 32 * taps * taps; L.w.kh = taps; L.w.kw = taps;
+      L.alpha = al; L.beta = be;
+      return L;
+    };
+    rb.c1 = conv(p1.p, 3, a1, b1);
+    rb.c2 = conv(p2.p, 3, a2, b2);
+    if (wsc) rb.sc = conv(ps.p, 1, asc, bsc);
+    float* const bufs[3] = {static_cast<float*>(m0.p), static_cast<float*>(m1.p), static_cast<float*>(m2.p)};
+    int h = H, w = W;
+    const float* r = sd::fcm_block_pair(rb, bufs, bufs[0], true, B, h, w, sd::FcmFuse{}, st);
+    SD_HIP(hipMemcpyAsync(out, r, (size_t)B * Ho * W * 64, hipMemcpyDeviceToDevice, st));
+  });
+}
+
 int sd_op_mha_block(const void* y, const float* w, const float* bias, int nseq, int T, const int* key_len, void* out,
                     int variant, int flags, void* stream) {
   return guard([&] {

@@ -726,7 +726,313 @@ void launch_band(const ConvGemmArgs& p, hipStream_t st, const FcmFuse& f = FcmFu
                      (int)bands, nb);
 }
 
+// ---------------------------------------------------------------------------------
+// Whole BasicResBlock in one launch (FcmBlockArgs): conv1 + BN + ReLU into an LDS image, conv2 + BN from that
+// image, + residual (the staged input's centre, or for the strided block the 1x1 stride-2 shortcut as two MFMAs
+// on the staged input) + ReLU.  Neither the intermediate map nor the shortcut map reaches HBM and the identity
+// residual is not read a second time.
+//
+// A band is R output rows x 62 frames.  Its intermediate is (R + 2) rows x 64 frames (one halo row / frame each
+// side: conv2's reach), computed from (R + 1) * SH + 3 input rows x 66 frames that arrive by LDS-DMA through a
+// 2-slot ring, one band ahead (ring kernel's slot layout and out-of-range zero fill).  The 8 waves are 4 columns
+// of 16 frames x 2 row halves: a wave walks its column's input rows top to bottom, reads each (row, dw) fragment
+// ONCE and feeds it to the up to three output rows it belongs to (dh = 0, 1, 2), so a band reads 21 fragments
+// per 90 MFMAs where a per-output-tile loop reads 45 (the LDS array was the ring kernel's limit).  Every output
+// still accumulates its taps from zero in (dh, dw) order and the epilogues repeat the two launches' expressions,
+// so the result is theirs value for value.  Intermediate pixels outside the map are conv2's zero padding: they
+// are selected to zero (conv1 there is relu(beta), not 0).
+// Ordering: every wave issues exactly HR2 output stores per band (rows / frames outside the map go to an
+// out-of-range buffer offset instead of being branched around), and they are the only vector-memory
+// instructions younger than the next band's DMAs, so `vmcnt(HR2)` at the band's top retires those DMAs without
+// waiting for the stores.
+constexpr int kFbCol = 4;                // 16-frame columns per band
+constexpr int kFbIW = kFbCol * 16;       // intermediate frames per band
+constexpr int kFbTW = kFbIW - 2;         // output frames per band
+constexpr int kFbPx = kFbIW + 2;         // staged input frames per row
+template <int SH>
+struct FbGeom {
+  static constexpr int R = SH == 1 ? 8 : 4;              // output rows per band
+  static constexpr int NI = R + 2;                       // intermediate rows
+  static constexpr int NIN = (NI - 1) * SH + 3;          // staged input rows (12 / 13)
+  static constexpr int kChunks = NIN * kFbPx * 4;        // 16-B chunks of staged input
+  static constexpr int kDma = ((kChunks + 63) / 64 + 7) / 8;   // DMA instructions per wave
+  static constexpr int kSlot = kDma * 8 * 1024;          // bytes
+  static constexpr int kImg = NI * kFbIW * 64 + 128;     // + 2 pixels: the last column's dw reach (unused outputs)
+  static constexpr int kLds = 2 * kSlot + kImg + 6 * 32 * 4;
+};
+
+template <int SH>
+__global__ __launch_bounds__(kBandThreads) void fcm_block_kernel(FcmBlockArgs p, int Ho, int n_bands, int n_tt) {
+  using G = FbGeom<SH>;
+  constexpr int R = G::R, NI = G::NI, kDma = G::kDma;
+  constexpr int HR1 = NI / 2, HR2 = R / 2;   // intermediate / output rows per wave
+  static_assert(NI % 2 == 0 && R % 2 == 0 && G::NIN < 256 && kFbPx < 256, "row halves, packed DMA coordinates");
+  extern __shared__ __attribute__((aligned(1024))) uint16_t xs[];
+  uint16_t* const img = xs + G::kSlot;   // after the two slots
+  float* const prm = reinterpret_cast<float*>(img + G::kImg / 2);   // [a1 b1 a2 b2 asc bsc][32]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, q = lane >> 4;
+  const int col = wv & 3, half = wv >> 2;
+  const int H = p.H, W = p.W;
+  const int n_rb = (Ho + R - 1) / R;
+
+  bf16x8 wf1[9][2], wf2[9][2], wsc[2];
+  {
+    const uint16_t* W1 = reinterpret_cast<const uint16_t*>(p.w1);
+    const uint16_t* W2 = reinterpret_cast<const uint16_t*>(p.w2);
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        wf1[t][nt] = *reinterpret_cast<const bf16x8*>(W1 + band_channel(l15, nt) * 288 + t * 32 + q * 8);
+        wf2[t][nt] = *reinterpret_cast<const bf16x8*>(W2 + band_channel(l15, nt) * 288 + t * 32 + q * 8);
+      }
+    if constexpr (SH == 2) {
+      const uint16_t* Ws = reinterpret_cast<const uint16_t*>(p.wsc);
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+        wsc[nt] = *reinterpret_cast<const bf16x8*>(Ws + band_channel(l15, nt) * 32 + q * 8);
+    }
+  }
+  if (tid < 6 * 32) {   // the folded BNs, read back per epilogue (registers go to the two weight sets)
+    const int k = tid >> 5, c = tid & 31;
+    float v = 0.f;
+    if (k == 0) v = p.a1[c];
+    else if (k == 1) v = p.b1[c];
+    else if (k == 2) v = p.a2[c];
+    else if (k == 3) v = p.b2[c];
+    else if (SH == 2) v = k == 4 ? p.asc[c] : p.bsc[c];
+    prm[tid] = v;
+  }
+  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), (short)0,
+                                                                      (int)kFcmOOB, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(p.out, (short)0, (int)kFcmOOB, 0x00020000);
+  // this lane's chunk of each of the wave's DMAs (row | frame << 8 | channel chunk << 16; -1: unused lane):
+  // DMA k writes slot positions (k * 8 + wv) * 64 + lane
+  int d_at[kDma];
+#pragma unroll
+  for (int k = 0; k < kDma; ++k) {
+    const int pos = (k * 8 + wv) * 64 + lane;
+    const int row = pos / (kFbPx * 4), rem = pos - row * kFbPx * 4, px = rem >> 2;
+    d_at[k] = pos < G::kChunks ? (row | (px << 8) | ((((rem & 3) - (px >> 2)) & 3) << 16)) : -1;
+  }
+  // XCD-aware band order (see the ring kernel): row-neighbour bands share two to four input rows through one L2
+  const int NG = gridDim.x;
+  const int vb = (NG % 8 == 0) ? (blockIdx.x % 8) * (NG / 8) + blockIdx.x / 8 : blockIdx.x;
+  auto issue = [&](int band, int slot) {
+    const int tt = band % n_tt, bh = band / n_tt;
+    const int b = bh / n_rb, ho0 = (bh % n_rb) * R;
+    const int h0 = (ho0 - 1) * SH - 1, w0 = tt * kFbTW - 2;   // first staged input row / frame
+#pragma unroll
+    for (int k = 0; k < kDma; ++k) {
+      const auto* lds = (const __attribute__((address_space(3))) void*)(xs + (slot * G::kSlot + (k * 8 + wv) * 1024) / 2);
+      const int d = d_at[k];
+      const int h = h0 + (d & 255), w = w0 + ((d >> 8) & 255);
+      const bool ok = d >= 0 && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
+      const uint32_t off = ok ? (uint32_t)(((((int64_t)b * H + h) * W + w) * 32 + ((d >> 16) & 3) * 8) * 2) : kFcmOOB;
+      dma_lds16_buf(ra, off, lds);
+    }
+  };
+  auto barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+  // channels 8q .. 8q+7 of table k (accumulator (nt, r) is channel 8q + 4nt + r)
+  auto load_prm = [&](int k, float* v) {
+    const floatx4 lo = *reinterpret_cast<const floatx4*>(prm + k * 32 + q * 8);
+    const floatx4 hi = *reinterpret_cast<const floatx4*>(prm + k * 32 + q * 8 + 4);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = lo[u], v[4 + u] = hi[u];
+  };
+  // LDS positions (bf16 units) of this lane in the first row its wave reads or writes; the rows after it are a
+  // constant stride apart (an immediate offset), so these few registers address everything
+  const int fr = col * 16 + l15;   // this lane's intermediate frame (w0 - 1 + fr) / output frame (w0 + fr)
+  constexpr int kInRow = kFbPx * 32, kImRow = kFbIW * 32;
+  int in_dw[3], im_dw[3];
+#pragma unroll
+  for (int dw = 0; dw < 3; ++dw) {
+    in_dw[dw] = ring_pos(half * HR1 * SH, fr + dw, q, kFbPx) * 8;
+    im_dw[dw] = ring_pos(half * HR2, fr + dw, q, kFbIW) * 8;
+  }
+  const int im_wr = ring_pos(half * HR1, fr, q, kFbIW) * 8;
+  // the residual's operand: the block's input at (ho, wo) = staged row r + 2, or for the shortcut input (2 ho, wo) =
+  // staged row 2 r + 3; frame fr + 2
+  const int in_res = ring_pos(SH == 1 ? half * HR2 + 2 : 2 * half * HR2 + 3, fr + 2, q, kFbPx) * 8;
+  const int nb_mine = n_bands > vb ? (n_bands - vb + NG - 1) / NG : 0;
+  if (nb_mine > 0) issue(vb, 0);
+  for (int i = 0; i < nb_mine; ++i) {
+    // band i's DMAs are older than the HR2 stores of band i - 1, this wave's only younger vector-memory work.
+    // The count rests on two things.  (1) Vector-memory completions are reported to a wave in issue order, the
+    // stores behind the older LDS-DMA loads included (what the compiler's own gfx9 wait counts assume; the ring
+    // kernel needs it between loads only).  (2) Every wave issues EXACTLY HR2 vector-memory instructions between
+    // issue(i) and this wait.  An extra one in the loop (a global load the compiler sinks or rematerialises
+    // here, a scratch reload) only makes the wait stricter; one FEWER (a store branched around or predicated
+    // away as an instruction, not as lanes) lets band i's last DMAs be outstanding at the barrier: a race.
+    // After an edit to the loop, count the buffer_store / buffer_load in its disassembly (kDma + HR2 per band; tests/test_fcm_block_isa.py).
+    if (i > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(HR2) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    barrier();   // band i is in LDS; every wave is done with band i - 1's slot and with the image
+    if (i + 1 < nb_mine) issue(vb + (i + 1) * NG, (i + 1) & 1);
+    const int band = vb + i * NG;
+    const int tt = band % n_tt, bh = band / n_tt;
+    const int b = bh / n_rb, ho0 = (bh % n_rb) * R, w0 = tt * kFbTW;
+    const uint16_t* sx = xs + (i & 1) * (G::kSlot / 2);
+
+    {   // ---- conv1 + BN1 + ReLU: intermediate rows half * HR1 .. + HR1 of the band -> image
+      floatx4 acc[HR1][2];
+      constexpr int NJ = (HR1 - 1) * SH + 3;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+        for (int dw = 0; dw < 3; ++dw) {
+          const bf16x8 af = *reinterpret_cast<const bf16x8*>(sx + in_dw[dw] + j * kInRow);
+#pragma unroll
+          for (int dh = 0; dh < 3; ++dh) {
+            const int jm = j - dh;
+            if (jm >= 0 && jm % SH == 0 && jm / SH < HR1) {
+              const int m = jm / SH;
+#pragma unroll
+              for (int nt = 0; nt < 2; ++nt) {
+                if (dh == 0 && dw == 0) acc[m][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
+                acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf1[dh * 3 + dw][nt], af, acc[m][nt], 0, 0, 0);
+              }
+            }
+          }
+        }
+        if (j >= 2 && (j - 2) % SH == 0 && (j - 2) / SH < HR1) {   // row m has all nine taps
+          const int m = (j - 2) / SH, mi = half * HR1 + m;
+          const int hi = ho0 - 1 + mi, wi = w0 - 1 + fr;
+          const bool ok = (unsigned)hi < (unsigned)Ho && (unsigned)wi < (unsigned)W;
+          float al[8], be[8], v[8];
+          load_prm(0, al);
+          load_prm(1, be);
+#pragma unroll
+          for (int u = 0; u < 8; ++u) v[u] = fmaxf(fmaf(acc[m][u >> 2][u & 3], al[u], be[u]) + 0.f, 0.f);
+          uint4 o = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
+                               pack_bf16x2(v[6], v[7]));
+          if (!ok) o = make_uint4(0u, 0u, 0u, 0u);   // conv2's padding (a select: 0 * NaN would be NaN)
+          *reinterpret_cast<uint4*>(img + im_wr + m * kImRow) = o;
+        }
+        __builtin_amdgcn_sched_barrier(0);   // keep the next rows' fragment reads from piling up in registers
+      }
+    }
+    barrier();   // the image is complete
+
+    {   // ---- conv2 + BN2 + residual + ReLU: output rows half * HR2 .. + HR2 of the band
+      floatx4 acc[HR2][2];
+      constexpr int NJ = HR2 + 2;
+      const int row0 = half * HR2;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+        for (int dw = 0; dw < 3; ++dw) {
+          const bf16x8 af = *reinterpret_cast<const bf16x8*>(img + im_dw[dw] + j * kImRow);
+#pragma unroll
+          for (int dh = 0; dh < 3; ++dh) {
+            const int m = j - dh;
+            if (m >= 0 && m < HR2) {
+#pragma unroll
+              for (int nt = 0; nt < 2; ++nt) {
+                if (dh == 0 && dw == 0) acc[m][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
+                acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf2[dh * 3 + dw][nt], af, acc[m][nt], 0, 0, 0);
+              }
+            }
+          }
+        }
+        if (j >= 2) {
+          const int m = j - 2, r = row0 + m;
+          const int ho = ho0 + r, wo = w0 + fr;
+          float rv[8];
+          if constexpr (SH == 1) {   // the block's input at (ho, wo): staged row r + 2, frame fr + 2
+            const u32x4_t r4 = *reinterpret_cast<const u32x4_t*>(sx + in_res + m * kInRow);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              rv[2 * u] = __uint_as_float(r4[u] << 16);
+              rv[2 * u + 1] = __uint_as_float(r4[u] & 0xffff0000u);
+            }
+          } else {   // 1x1 stride-2 shortcut + BN of input (2 ho, wo): staged row 2 r + 3, rounded to bf16 as stored
+            const bf16x8 cf = *reinterpret_cast<const bf16x8*>(sx + in_res + 2 * m * kInRow);
+            floatx4 sacc[2] = {floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt)
+              sacc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wsc[nt], cf, sacc[nt], 0, 0, 0);
+            float sal[8], sbe[8];
+            load_prm(4, sal);
+            load_prm(5, sbe);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const uint32_t w2 = pack_bf16x2(fmaf(sacc[(2 * u) >> 2][(2 * u) & 3], sal[2 * u], sbe[2 * u]),
+                                              fmaf(sacc[(2 * u + 1) >> 2][(2 * u + 1) & 3], sal[2 * u + 1], sbe[2 * u + 1]));
+              rv[2 * u] = __uint_as_float(w2 << 16);
+              rv[2 * u + 1] = __uint_as_float(w2 & 0xffff0000u);
+            }
+          }
+          float al[8], be[8], v[8];
+          load_prm(2, al);
+          load_prm(3, be);
+#pragma unroll
+          for (int u = 0; u < 8; ++u) v[u] = fmaxf(fmaf(acc[m][u >> 2][u & 3], al[u], be[u]) + rv[u], 0.f);
+          const bool ok = ho < Ho && fr < kFbTW && wo < W;
+          const uint32_t off = ok ? (uint32_t)(((((int64_t)b * Ho + ho) * W + wo) * 32 + q * 8) * 2) : kFcmOOB;
+          const u32x4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
+                             pack_bf16x2(v[6], v[7])};
+          __builtin_amdgcn_raw_buffer_store_b128(o, ro, off, 0, 0);   // always issued: see "Ordering" above
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  }
+}
+
+template <int SH>
+void launch_fcm_block(const FcmBlockArgs& a, int Ho, hipStream_t st) {
+  using G = FbGeom<SH>;
+  static_assert(G::kLds <= 160 * 1024, "LDS budget");
+  const int n_tt = cdiv(a.W, kFbTW);
+  const int64_t bands = (int64_t)a.B * cdiv(Ho, G::R) * n_tt;
+  static bool attr = false;
+  if (!attr) {
+    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fcm_block_kernel<SH>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, G::kLds));
+    attr = true;
+  }
+  const int grid = (int)std::min<int64_t>(bands, (int64_t)g_fcm_cu);
+  hipLaunchKernelGGL((fcm_block_kernel<SH>), dim3(grid), dim3(kBandThreads), (size_t)G::kLds, st, a, Ho, (int)bands, n_tt);
+}
+
 }  // namespace
+
+bool fcm_block_enabled() {
+  static const bool off = getenv("SDIAR_NO_FCM_BLOCK") != nullptr;   // A/B switch: the two launches per block
+  return !off;
+}
+
+bool fcm_block_supported(const FcmBlockArgs& a) {
+  if (!a.bf16 || a.C != 32 || a.B < 1 || a.H < 1 || a.W < 1 || (a.stride != 1 && a.stride != 2)) return false;
+  if (!(a.x && a.out && a.w1 && a.w2 && a.a1 && a.b1 && a.a2 && a.b2)) return false;
+  if (a.stride == 2 ? !(a.wsc && a.asc && a.bsc) : a.wsc != nullptr) return false;
+  const int Ho = (a.H - 1) / a.stride + 1;
+  const int64_t bands = (int64_t)a.B * cdiv(Ho, a.stride == 1 ? FbGeom<1>::R : FbGeom<2>::R) * cdiv(a.W, kFbTW);
+  return (int64_t)a.B * a.H * a.W * 64 < (int64_t)kFcmOOB && bands < (1ll << 31);
+}
+
+void conv_fcm_block(const FcmBlockArgs& a, hipStream_t st) {
+  SD_CHECK(fcm_block_supported(a), kErrInvalid, "fcm block: unsupported arguments");
+  const int Ho = (a.H - 1) / a.stride + 1;
+  const int64_t in_bytes = (int64_t)a.B * a.H * a.W * 64, out_bytes = (int64_t)a.B * Ho * a.W * 64;
+  const char *xb = static_cast<const char*>(a.x), *ob = static_cast<const char*>(a.out);
+  // neighbouring bands read each other's halo rows after a band has stored its output
+  SD_CHECK(ob + out_bytes <= xb || xb + in_bytes <= ob, kErrInvalid, "fcm block: out overlaps the input");
+  if (!g_fcm_cu) {
+    int dev = 0;
+    SD_HIP(hipGetDevice(&dev));
+    SD_HIP(hipDeviceGetAttribute(&g_fcm_cu, hipDeviceAttributeMultiprocessorCount, dev));
+  }
+  const double px = (double)a.B * Ho * a.W;
+  ProfScope prof("fcm_block", 2.0 * px * 32 * 288 * 2 + (a.wsc ? 2.0 * px * 32 * 32 : 0.0),
+                 (double)in_bytes + (double)out_bytes, st);
+  if (a.stride == 1) launch_fcm_block<1>(a, Ho, st);
+  else launch_fcm_block<2>(a, Ho, st);
+  SD_LAUNCH_CHECK();
+}
 
 // FCM head.conv2 (stride 2 to Ho = 10 rows) into the TDNN's (B, T, 32 * Ho) layout: see TOUT above
 bool tout_ok(const ConvGemmArgs& p) {

@@ -119,6 +119,22 @@ struct FcmFuse {
 };
 bool fcm_fused_supported(const ConvGemmArgs& p, const FcmFuse& f);
 void conv_fcm3x3_fused(const ConvGemmArgs& p, const FcmFuse& f, hipStream_t st);
+// One whole CAM++ FCM BasicResBlock (cam_pplus_wespeaker.py:240-268) in one launch (fcm_conv.hip, fcm_block_kernel):
+// out = relu(bn2(conv2(relu(bn1(conv1(x))))) + (x | bn_sc(conv1x1_sc(x)))) on bf16 NHWC maps of C = 32 channels,
+// 3x3 pad 1, freq stride 1 (identity residual) or 2 (1x1 stride-2 shortcut; wsc set).  The intermediate map and the
+// shortcut stay in LDS; the arithmetic is that of the two launches (conv_fcm3x3[_fused]), value for value.  w1 / w2:
+// packed bf16 Wt[32][288], wsc: packed bf16 Wt[32][32]; a* / b*: folded BN per channel.  out must not overlap x.
+struct FcmBlockArgs {
+  const void* x = nullptr;
+  int B = 0, H = 0, W = 0, C = 32, stride = 1;
+  bool bf16 = true;
+  const void *w1 = nullptr, *w2 = nullptr, *wsc = nullptr;
+  const float *a1 = nullptr, *b1 = nullptr, *a2 = nullptr, *b2 = nullptr, *asc = nullptr, *bsc = nullptr;
+  void* out = nullptr;   // (B, (H - 1) / stride + 1, W, 32)
+};
+bool fcm_block_supported(const FcmBlockArgs& a);   // false: fp32 maps, C != 32, a map of 2 GiB or more
+bool fcm_block_enabled();                          // false with SDIAR_NO_FCM_BLOCK set (read once): the two launches
+void conv_fcm_block(const FcmBlockArgs& a, hipStream_t st);
 // ResNet34 trunk 3x3 convs (res_conv.hip): bf16 NHWC in, pad 1, stride 1 or 2 in BOTH axes, Cin / Cout in
 // {32, 64, 128, 256, 512}, folded BN + optional bf16 residual + ReLU (NaN kept), bf16 out (NHWC as 16-B stores, or any
 // o_s* strides per element).  ResFuse: the block's 1x1 shortcut at the same stride (+ its BN, no ReLU) from the
