@@ -87,6 +87,27 @@ typedef struct {
                                      nn.Linear(2 * speaker_embed_dim, transformer_embed_dim) (model.py:212-217,
                                      873-874), variants 0, 2 and 3 only: the reference's ots_vad forward never applies
                                      it (model.py:730-731), so variant 1 is refused at create */
+  int backend;                    /* 0: the variant's back end above (a zero-initialised config behaves as before)
+                                     1: single_backend_type "mamba2", multi_backend_type "transformer"
+                                        (egs/magicdata-ramc/run_ts_vad2_based_on_system_sad.sh:58-68, stage 4)
+                                     2: "mamba2" for both; adds multi_backend_proj = Linear(2 E, E) before fc
+                                     (egs/magicdata-ramc/ts_vad2/model.py:377-403, 488-504, 1337-1399; ts_vad2/mamba.py:
+                                     149-213).  variant 0 only, SD_ERR_INVALID otherwise.  Each back end is a
+                                     bidirectional Mamba2BlockV2(E, n_layer = num_transformer_layer, d_state, d_conv 4,
+                                     expand); backend_down.0 reads 2 * E * max_num_speaker channels.
+                                     THE AXIS QUIRK: the reference hands its seq-first (T, B, E) tensor to mamba_ssm's
+                                     batch-first modules (model.py:1366-1367, 1393), so the scan, the causal conv and
+                                     the backward flip run along the WINDOWS of a reference forward call, one sequence
+                                     per (speaker, label frame).  This runner reproduces that: the sequences are the
+                                     windows of each forward_batch group of sd_tsvad_forward_batched (the whole call
+                                     for sd_tsvad_forward), in order, and never cross groups, so logits depend on
+                                     which windows share a group; `force` (a slice of a reference batch) is refused.
+                                     mamba_ssm is CUDA-only: the arithmetic restates its published Mamba2 module and
+                                     no reference-run golden pins it (parity unpinned, like the Conformer) */
+  int d_state;                    /* backend 1 / 2: TSVADConfig.d_state (reference default 64, the recipe 128): a
+                                     multiple of 16 up to 256 */
+  int expand;                     /* backend 1 / 2: TSVADConfig.expand (4): expand * transformer_embed_dim must be a
+                                     multiple of 64 (the Mamba2 head dimension) */
 } sd_tsvad_config;
 
 int sd_tsvad_create(const sd_tsvad_config* cfg, sd_tsvad** out);
@@ -763,6 +784,16 @@ int sd_op_aff_gate(const void* x, const void* y, int dtype, int64_t P, int C, in
 int sd_op_speaker_input_proj(const float* ts, const float* mix, int B, int NS, int T, int Tmix, int SE, int E,
                              const float* w, const float* bias, const float* pe, const float* bn_a, const float* bn_b,
                              const int* grp, int group, float* out, void* out_bf16, int precision, void* stream);
+/* Bidirectional Mamba2BlockV2 (ts_vad2/mamba.py:149-213 over mamba_ssm's Mamba2: headdim 64, ngroups 1, d_conv 4,
+ * gated RMSNorm) on R independent sequences: x (R, L, E) fp32 -> out (R, L, 2 E) fp32 = [forward chain | backward
+ * chain on the reversed sequence, reversed back].  weights: one fp32 device array of n_weights floats, for direction
+ * (forward_blocks, backward_blocks), for layer 0 .. n_layer - 1, the block's tensors flattened in this order:
+ * norm.weight (E), mixer.in_proj.weight (2 d_inner + 2 d_state + H, E), mixer.conv1d.weight (d_inner + 2 d_state, 1, 4),
+ * mixer.conv1d.bias, mixer.dt_bias (H), mixer.A_log (H), mixer.D (H), mixer.norm.weight (d_inner),
+ * mixer.out_proj.weight (E, d_inner); d_inner = expand * E, H = d_inner / 64.  precision 0 fp32, 1 bf16 (bf16 GEMM
+ * operands, zxbcdt / g and the output stored as bf16; the scan itself is fp32), 2 bf16x3.  Synchronises `stream`. */
+int sd_op_mamba2_stack(const float* x, int R, int L, int E, const float* weights, int64_t n_weights, int n_layer,
+                       int d_state, int expand, int precision, float* out, void* stream);
 /* Attention core on packed qkv (S*T, 3D) -> out (S*T, D). */
 int sd_op_attention(const float* qkv, int S, int T, int D, int nh, int causal, int causal_delay,
                     const int* key_len, float* out, int precision, void* stream);

@@ -37,6 +37,9 @@ class TsvadConfig(ctypes.Structure):
         ("transformer_embed_dim", c_int),
         ("transformer_ffn_embed_dim", c_int),
         ("speaker_embed_dim", c_int),
+        ("backend", c_int),    # 0 the variant's own; 1 mamba2 + transformer; 2 mamba2 + mamba2 (variant 0 only)
+        ("d_state", c_int),
+        ("expand", c_int),
     ]
 
 
@@ -269,6 +272,8 @@ _SIGS = {
     "sd_op_speaker_input_proj": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                          c_int, c_void_p]),
+    "sd_op_mamba2_stack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                   c_void_p, c_void_p]),
     "sd_op_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                 c_void_p]),
     "sd_op_attention_grid": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,

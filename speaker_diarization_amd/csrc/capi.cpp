@@ -210,7 +210,11 @@ int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
     t.embed_dim = c->transformer_embed_dim;
     t.ffn_dim = c->transformer_ffn_embed_dim;
     t.speaker_embed_dim = c->speaker_embed_dim;
-    sd::TsvadModel::validate(t);   // proj_layer configurations (speaker_embed_dim * 2 != transformer_embed_dim)
+    t.backend = c->backend;
+    t.d_state = c->d_state;
+    t.expand = c->expand;
+    // proj_layer configurations (speaker_embed_dim * 2 != transformer_embed_dim); backend / d_state / expand
+    sd::TsvadModel::validate(t);
     create(out, c->precision == 2, t);
   });
 }
@@ -1184,6 +1188,55 @@ int sd_op_speaker_input_proj(const float* ts, const float* mix, int B, int NS, i
     a.mix_a = mixa.p; a.p_ts = static_cast<float*>(pts.p); a.p_mix = static_cast<float*>(pmix.p);
     a.out = out; a.xb = static_cast<uint16_t*>(out_bf16);
     sd::speaker_input_proj(a, bf, st);
+  });
+}
+
+int sd_op_mamba2_stack(const float* x, int R, int L, int E, const float* weights, int64_t n_weights, int n_layer,
+                       int d_state, int expand, int precision, float* out, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && weights && out && R >= 1 && L >= 1 && E >= 8 && n_layer >= 1, sd::kErrInvalid,
+             "mamba2_stack: bad argument");
+    SD_CHECK(precision >= 0 && precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
+    sd::Mamba2Stack::validate(E, d_state, expand);
+    const sd::GemmX3Scope x3(precision == 2);
+    const int64_t DI = (int64_t)expand * E, H = DI / sd::kMamba2HeadDim, CD = DI + 2 * d_state, dip = 2 * DI + 2 * d_state + H;
+    struct Key { const char* name; std::vector<int64_t> shape; };
+    const std::vector<Key> keys = {{"norm.weight", {E}}, {"mixer.in_proj.weight", {dip, E}},
+                                   {"mixer.conv1d.weight", {CD, 1, 4}}, {"mixer.conv1d.bias", {CD}},
+                                   {"mixer.dt_bias", {H}}, {"mixer.A_log", {H}}, {"mixer.D", {H}},
+                                   {"mixer.norm.weight", {DI}}, {"mixer.out_proj.weight", {E, DI}}};
+    int64_t per_block = 0;
+    for (const Key& k : keys) {
+      int64_t n = 1;
+      for (int64_t d : k.shape) n *= d;
+      per_block += n;
+    }
+    SD_CHECK(n_weights == 2 * n_layer * per_block, sd::kErrInvalid,
+             "mamba2_stack: weights must hold " + std::to_string(2 * n_layer * per_block) + " floats");
+    std::vector<float> host((size_t)n_weights);
+    SD_HIP(hipStreamSynchronize(st));
+    SD_HIP(hipMemcpy(host.data(), weights, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+    sd::ParamStore ps;
+    const float* w = host.data();
+    for (int dir = 0; dir < 2; ++dir)
+      for (int i = 0; i < n_layer; ++i)
+        for (const Key& k : keys) {
+          int64_t n = 1;
+          for (int64_t d : k.shape) n *= d;
+          ps.set(std::string(dir ? "backward_blocks." : "forward_blocks.") + std::to_string(i) + "." + k.name, w,
+                 k.shape.data(), (int)k.shape.size());
+          w += n;
+        }
+    sd::DeviceArena arena;   // freed on return, after the stream has drained
+    sd::Mamba2Stack stack;
+    stack.load(ps, arena, "", E, n_layer, d_state, expand, precision == 1);
+    stack.alloc(arena, (int64_t)R * L);
+    // R sequences of L contiguous rows: groups of G = L "windows" with one inner row each
+    Scratch o16(precision == 1 ? (size_t)R * L * 2 * E * 2 : 4, st);
+    stack.forward(x, R * L, L, 1, precision == 1 ? o16.p : out, precision == 1, 1, R * L, st);
+    if (precision == 1) sd::bf16_to_f32(o16.p, (int64_t)R * L * 2 * E, out, st);
+    SD_HIP(hipStreamSynchronize(st));
   });
 }
 

@@ -878,3 +878,75 @@ void stream_enc_finish(const float* x, const void* t, bool t_bf16, const float* 
 void stream_dec_finish(const float* x, const void* t, bool t_bf16, const float* g, const float* b, float eps, int c,
                        int C, int D, const float* emb, float* scores, int* cursor, hipStream_t st);
 }  // namespace sd
+
+namespace sd {
+// ---------------------------------------------------------------- mamba2 (mamba2.hip)
+// Kernels of the bidirectional Mamba2BlockV2 back end (mamba2.h).  Token rows are (window b, inner i) at row b * I + i,
+// `rows` = B * I of them; every per-direction buffer is [forward | backward], `rows` rows each.  A sequence is the rows
+// of one inner index over the windows of one group of G consecutive windows (the last group may be shorter), walked in
+// window order by the forward chain and in reversed order by the backward chain: reversed indexing, no flipped copies.
+constexpr int kMamba2HeadDim = 64;    // mamba_ssm's headdim default
+constexpr int kMamba2MaxState = 256;
+constexpr float kMamba2Eps = 1e-5f;   // RMSNorm(eps=1e-5) and the mixer's gated RMSNorm
+// The residual sum of a block and the RMSNorm of the next one, per row and direction:
+//   r = r_in (+ t * rsqrt(sum_h ssq / d_inner + eps): the previous mixer's out_proj output, its gated RMSNorm's per-row
+//   scale applied here because norm.weight is folded into out_proj's columns);  r_out = r (t given);
+//   y = r * rsqrt(mean(r^2) + eps) * w   (the in_proj A operand, bf16 bits when y_bf16);
+//   dt_raw = y (unrounded) . w_dt^T: in_proj's nh dt rows in fp32, whatever the GEMMs' precision (Mamba2ScanArgs).
+struct Mamba2NormArgs {
+  int64_t rows = 0;
+  int E = 0;
+  const float* r_in = nullptr;
+  int64_t r_in_dir = 0;        // elements between the directions' r_in (0: both read the stack's input)
+  const float* t = nullptr;    // (2, rows, E) or null
+  const float* ssq = nullptr;  // (2, rows, nh) per-head sums of g^2 (with t)
+  int nh = 0, d_inner = 0;     // heads; d_inner with t
+  float* r_out = nullptr;      // (2, rows, E), required with t; may alias r_in
+  const float* w = nullptr;    // (2, E)
+  void* y = nullptr;           // (2, rows, E)
+  bool y_bf16 = false;
+  const float* w_dt = nullptr; // (2, nh, E): the last nh rows of in_proj.weight
+  float* dt_raw = nullptr;     // (2, rows, nh)
+};
+void mamba2_norm(const Mamba2NormArgs& a, hipStream_t st);
+// The stack's output h_n + r_n (r_in, t, ssq as above) of token row (b, spk, tt) = (b * NS + spk) * T + tt, written to
+// out row b * T + tt at columns spk * 2 E + dir * E + e: the slot speakers_to_channels would give it (NS = 1, T = rows:
+// plain (rows, 2 E) rows).
+struct Mamba2FinishArgs {
+  int64_t rows = 0;
+  int E = 0;
+  const float* r_in = nullptr;
+  int64_t r_in_dir = 0;
+  const float* t = nullptr;
+  const float* ssq = nullptr;
+  int nh = 0, d_inner = 0;
+  int NS = 1, T = 1;
+  void* out = nullptr;
+  bool out_bf16 = false;
+};
+void mamba2_finish(const Mamba2FinishArgs& a, hipStream_t st);
+// The mixer between in_proj and out_proj, one workgroup per (sequence, head, direction): causal depthwise conv (k 4,
+// left zero pad) + bias + SiLU on x | Bm | Cm, dt = softplus(dt_raw + dt_bias), the recurrence
+//   S_l = exp(dt_l A) S_{l-1} + dt_l x_l (x) Bm_l,   y_l = S_l Cm_l + D x_l
+// with the 64 x d_state state in registers (fp32 whatever the i/o type, any sequence length), g = y * silu(z) and the
+// head's sum of g^2 per row for the gated RMSNorm.
+struct Mamba2ScanArgs {
+  const void* zx = nullptr;    // (2, rows, ldz): in_proj's [z | x | Bm | Cm | dt_raw], bf16 bits when bf16
+  int ldz = 0;
+  bool bf16 = false;
+  // (2, rows, heads) fp32 from mamba2_norm, read instead of zx's dt columns: exp(dt A) with A down to -16 turns the
+  // 2^-9 relative rounding of bf16 operands or of a bf16 dt_raw into percents of the decay
+  const float* dt_raw = nullptr;
+  int64_t rows = 0;
+  int B = 0, G = 0, I = 0;
+  int d_inner = 0, d_state = 0;
+  const float *conv_w = nullptr, *conv_b = nullptr;   // (2, conv_dim, 4), (2, conv_dim)
+  const float *dt_bias = nullptr, *A = nullptr, *D = nullptr;   // (2, heads); A = -exp(A_log)
+  void* g = nullptr;           // (2, rows, d_inner), zx's type
+  float* ssq = nullptr;        // (2, rows, heads)
+};
+void mamba2_scan(const Mamba2ScanArgs& a, hipStream_t st);
+// rows of `per_win` floats of every window of a group g with grp[g] set -> NaN: with a scan over the windows of a
+// reference forward, a non-finite input reaches every window of its group (both directions meet in backend_down).
+void poison_groups(float* x, int B, int64_t per_win, const int* grp, int group, hipStream_t st);
+}  // namespace sd

@@ -15,6 +15,9 @@
 //     -> transformer_backend, variants 0, 2, 3 and 4 (forward_common, model.py:758-897):
 //          [ts_embed | mix] + PE, 2-layer transformer per speaker (batched over speakers)
 //          -> backend_down conv(1536->384, k5)+BN+ReLU -> PE -> 2-layer transformer -> fc
+//          backend 1 / 2 (variant 0; egs/magicdata-ramc/ts_vad2/model.py:377-403, 488-504, 1337-1399): the per-speaker
+//          encoder, and with 2 the multi-speaker one (+ multi_backend_proj), is a bidirectional Mamba2BlockV2 (mamba2.h)
+//          that scans along the WINDOWS of a reference forward call; backend_down reads 2 E NS channels
 //        ots_vad_backend, variant 1 (forward_common_ots_vad, model.py:669-756):
 //          GSP + gsp_fc -> [ts_embed | mix] -> 6-layer Conformer per speaker (conformer_slice: the fused stack,
 //          which runs inside each window slice) -> BiLSTM(1536 -> 2x256) -> fc
@@ -33,6 +36,12 @@ ConvL TsvadModel::conv_bn(const std::string& wname, const std::string& bn, const
 }
 
 void TsvadModel::validate(const TsvadConfig& c) {
+  SD_CHECK(c.backend >= 0 && c.backend <= 2, kErrInvalid, "backend must be 0, 1 or 2");
+  if (c.backend != 0) {
+    SD_CHECK(c.variant == 0, kErrInvalid,
+             "backend 1 / 2 (Mamba2 back ends) is built for variant 0 (speech_encoder_type CAM++) only");
+    Mamba2Stack::validate(c.embed_dim, c.d_state, c.expand);
+  }
   if (c.speaker_embed_dim * 2 == c.embed_dim) return;
   // proj_layer = nn.Linear(2 SE, E) on cat(ts_embed, mix_embeds) (model.py:212-217, 873-874)
   SD_CHECK(c.variant != 1, kErrInvalid,
@@ -150,11 +159,33 @@ void TsvadModel::build() {
       proj_mix_ = upload_packed(arena_, wm, E, SE, 1, 1, cfg_.bf16);
       proj_b_ = arena_.upload(b.data);
     }
+    if (cfg_.backend != 0) {
+      // Mamba2BlockV2(E, n_layer=num_transformer_layer, d_state, d_conv=4, expand, bidirectional=True)
+      // (magicdata model.py:377-403)
+      single_m_ = std::make_unique<Mamba2Stack>();
+      single_m_->load(ps_, arena_, "single_backend.", cfg_.embed_dim, cfg_.num_transformer_layer, cfg_.d_state,
+                      cfg_.expand, cfg_.bf16);
+    }
+    if (cfg_.backend == 2) {
+      // the same stack over the speaker-merged rows, then multi_backend_proj = Linear(2 E, E) (:488-504, 1396-1397)
+      multi_m_ = std::make_unique<Mamba2Stack>();
+      multi_m_->load(ps_, arena_, "multi_backend.", cfg_.embed_dim, cfg_.num_transformer_layer, cfg_.d_state,
+                     cfg_.expand, cfg_.bf16);
+      multi_proj_ = loader().linear("multi_backend_proj");
+      SD_CHECK(multi_proj_.w.N == cfg_.embed_dim && multi_proj_.w.K == 2 * cfg_.embed_dim, kErrParam,
+               "multi_backend_proj.weight must be (transformer_embed_dim, 2 * transformer_embed_dim)");
+      SD_CHECK(ps_.get("multi_backend_proj.bias").numel() == cfg_.embed_dim, kErrParam, "multi_backend_proj.bias size");
+    }
     for (int i = 0; i < cfg_.num_transformer_layer; ++i) {
-      single_.push_back(loader().transformer("single_backend.layers." + std::to_string(i)));
-      multi_.push_back(loader().transformer("multi_backend.layers." + std::to_string(i)));
+      if (cfg_.backend == 0) single_.push_back(loader().transformer("single_backend.layers." + std::to_string(i)));
+      if (cfg_.backend != 2) multi_.push_back(loader().transformer("multi_backend.layers." + std::to_string(i)));
     }
     backend_down_ = conv_bn("backend_down.0.weight", "", "backend_down.0.bias");
+    if (cfg_.backend != 0)   // the two directions are concatenated: Conv1d(2 E NS -> E, k5, pad 2)
+      SD_CHECK(backend_down_.w.N == cfg_.embed_dim && backend_down_.w.kw == 5 &&
+                   backend_down_.w.Cin == 2 * cfg_.embed_dim * cfg_.max_num_speaker,
+               kErrParam, "backend_down.0.weight must be (transformer_embed_dim, 2 * transformer_embed_dim * "
+                          "max_num_speaker, 5) behind a Mamba2 single back end");
     backend_bn_ = bn_only("backend_down.1.bn");
     fc_ = loader().linear("fc");
   } else {
@@ -212,7 +243,11 @@ void TsvadModel::alloc_workspace() {
   QKV_ = ws(g.token_elems * 3);
   AO_ = ws(g.token_elems);
   H_ = ws(g.rows * std::max<int64_t>({(int64_t)cfg_.ffn_dim, 2 * E, (int64_t)cfg_.conformer_ffn}));
-  X2_ = ws(g.token_elems);
+  // behind a Mamba2 single back end X2_ holds both directions: (B, Tl, NS * 2 E)
+  X2_ = ws(g.token_elems * (single_m_ ? 2 : 1));
+  // the Mamba2 stages' own buffers (in_proj's zxbcdt is the large one), sized for max_batch windows
+  if (single_m_) single_m_->alloc(arena_, g.rows);
+  if (multi_m_) multi_m_->alloc(arena_, Bm * g.Tl);
   partial_ = ws(Bm * NS * ((E + 63) / 64) * 2);
   lstm_work_ = ws(lstm_work_floats((int)Bm, cfg_.lstm_hidden, 2));
   nonfinite_ = static_cast<int*>(arena_.alloc(4 * (size_t)Bm * sizeof(int)));
@@ -294,17 +329,33 @@ void TsvadModel::transformer_backend(const float* ts, int T3, int B, int Tl, flo
     build_speaker_input(ts, mix_, SE, T3, B, NS, Tl, SE, pe_, X_, st, sd_bn);
     // bf16(X) for the first layer's in-projection too (every later layer gets it from the LayerNorms): an
     // fp32 A operand would send that GEMM to the register-staged kernel (C4: 1.5 ms per 640 windows vs 0.3)
-    if (bf) f32_to_bf16(X_, (int64_t)S * Tl * E, enc_work().AO, st);
+    if (bf && !single_m_) f32_to_bf16(X_, (int64_t)S * Tl * E, enc_work().AO, st);
   }
-  for (size_t i = 0; i < single_.size(); ++i)
-    run_transformer(single_[i], X_, S, Tl, E, cfg_.num_attention_head, nullptr, enc_work(), st, 0, 0, bf || i > 0);
-  speakers_to_channels(X_, B, NS, Tl, E, X2_, bf, st);
-  ConvGemmArgs p = cam_conv1d(Tens{X2_, bf}, B, Tl, NS * E, backend_down_, 1, 2, 1, Tens{X_, false}, E);
+  // Mamba2 back ends: the reference hands the seq-first (T, B, E) tensor to a batch-first module (magicdata
+  // model.py:1366-1367, 1393), so each (speaker, frame) is a sequence over the windows of one reference forward call:
+  // the groups of `group` windows the BatchNorm1D bypass already names
+  const int G = bd_bn.group;
+  int ch = NS * E;   // backend_down's input channels per frame
+  if (single_m_) {
+    // both directions of every speaker straight into the speakers-to-channels layout (B, Tl, NS * 2 E)
+    single_m_->forward(X_, B, G, NS * Tl, X2_, bf, NS, Tl, st);
+    ch = NS * 2 * E;
+  } else {
+    for (size_t i = 0; i < single_.size(); ++i)
+      run_transformer(single_[i], X_, S, Tl, E, cfg_.num_attention_head, nullptr, enc_work(), st, 0, 0, bf || i > 0);
+    speakers_to_channels(X_, B, NS, Tl, E, X2_, bf, st);
+  }
+  ConvGemmArgs p = cam_conv1d(Tens{X2_, bf}, B, Tl, ch, backend_down_, 1, 2, 1, Tens{X_, false}, E);
   conv_gemm(p, bf, st);
   add_pe(X_, B * Tl, Tl, E, E, pe_, st, bd_bn);   // backend_down's BatchNorm1D + ReLU, then the PE
-  if (bf) f32_to_bf16(X_, (int64_t)B * Tl * E, enc_work().AO, st);
-  for (size_t i = 0; i < multi_.size(); ++i)
-    run_transformer(multi_[i], X_, B, Tl, E, cfg_.num_attention_head, nullptr, enc_work(), st, 0, 0, bf || i > 0);
+  if (multi_m_) {
+    multi_m_->forward(X_, B, G, Tl, X2_, bf, 1, Tl, st);
+    conv_gemm(lin(Tens{X2_, bf}, B * Tl, 2 * E, multi_proj_.w, multi_proj_.beta, Tens{X_, false}, E), bf, st);
+  } else {
+    if (bf) f32_to_bf16(X_, (int64_t)B * Tl * E, enc_work().AO, st);
+    for (size_t i = 0; i < multi_.size(); ++i)
+      run_transformer(multi_[i], X_, B, Tl, E, cfg_.num_attention_head, nullptr, enc_work(), st, 0, 0, bf || i > 0);
+  }
   conv_gemm(logits_fc(X_, B, Tl, E, fc_, NS, logits), bf, st);
 }
 
@@ -429,6 +480,9 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   SD_CHECK(forward_batch >= 0 && force >= 0 && force <= 3, kErrInvalid, "forward: bad forward_batch / force");
   require_finalized();
   SD_CHECK(B >= 1 && B <= cfg_.max_batch, kErrInvalid, "batch exceeds max_batch");
+  // a Mamba2 back end scans over the windows of a reference forward call: the call must hold each of them whole
+  SD_CHECK(!single_m_ || force == 0, kErrInvalid,
+           "force: a Mamba2 back end cannot run a slice of a reference batch (raise max_batch to forward_batch)");
   // ECAPA and ReDimNetB2 never subsample inside the trunk: any window of at least one frame runs
   SD_CHECK(Tf >= (cfg_.variant >= 3 ? 1 : 8) && Tf <= cfg_.max_fbank_frames, kErrInvalid,
            "fbank frames exceed max_fbank_frames");
@@ -485,6 +539,10 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   else transformer_backend(ts, T3, B, Tl, logits, st, sd_bn, bd_bn);
   // a window whose fbank or target-speaker embeddings hold a NaN / Inf has NaN logits in the reference
   poison_windows(logits, B, (int64_t)NS * Tl, win_fb, win_ts, st);
+  // behind a Mamba2 back end the forward and backward scans carry that NaN to every window of its reference forward
+  // call, and backend_down mixes the two directions: the whole group is NaN there (the flags are taken at the source
+  // for the same reason as poison_windows': the trunk's ReLUs drop NaN)
+  if (single_m_) poison_groups(logits, B, (int64_t)NS * Tl, grp_bd, G, st);
 }
 
 }  // namespace sd

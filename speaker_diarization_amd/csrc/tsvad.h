@@ -5,6 +5,7 @@
 #include <vector>
 #include "campp.h"
 #include "ecapa.h"
+#include "mamba2.h"
 #include "redimnet.h"
 #include "resnet.h"
 
@@ -31,6 +32,13 @@ struct TsvadConfig {
   int conformer_ffn = 512;
   int conformer_kernel = 31;
   int lstm_hidden = 256;
+  // 0: the variant's own back end; 1: single_backend "mamba2" + multi_backend "transformer"; 2: "mamba2" for both
+  // (egs/magicdata-ramc/ts_vad2/model.py:377-403, 488-504, 1337-1399; variant 0 only).  The Mamba2BlockV2 stacks scan
+  // ALONG THE WINDOWS of a reference forward call (forward's forward_batch groups), as the reference's seq-first call
+  // of a batch-first module does (model.py:1366-1367, 1393; mamba2.h)
+  int backend = 0;
+  int d_state = 64;
+  int expand = 4;
 };
 
 class TsvadModel : public ModelCore {
@@ -121,6 +129,9 @@ class TsvadModel : public ModelCore {
   const float* proj_b_ = nullptr;
   float *pts_ = nullptr, *pmix_ = nullptr;
   std::vector<TransformerL> single_, multi_;
+  // backend 1 / 2: single_backend (and, 2, multi_backend + multi_backend_proj) as Mamba2BlockV2 stacks
+  std::unique_ptr<Mamba2Stack> single_m_, multi_m_;
+  ConvL multi_proj_;
   ConvL backend_down_;
   std::vector<ConformerL> conf_;
   PackedW lstm_ih_;

@@ -44,7 +44,8 @@ class TSVADModel(_lib.Handle):
             max_fbank_frames=self.max_fbank, precision=_lib.PRECISION[precision],
             num_transformer_layer=c.num_transformer_layer, num_attention_head=c.num_attention_head,
             transformer_embed_dim=c.transformer_embed_dim,
-            transformer_ffn_embed_dim=c.transformer_ffn_embed_dim, speaker_embed_dim=c.speaker_embed_dim))
+            transformer_ffn_embed_dim=c.transformer_ffn_embed_dim, speaker_embed_dim=c.speaker_embed_dim,
+            backend=c.backend, d_state=c.d_state if c.backend else 0, expand=c.expand if c.backend else 0))
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Strict load (missing/unexpected keys raise RuntimeError like torch)."""
@@ -78,7 +79,10 @@ class TSVADModel(_lib.Handle):
         call is one batch.  A call of more than max_batch windows runs as several device forwards cut at
         reference-batch boundaries; a reference batch wider than max_batch is cut into device forwards that
         each learn (`_force`) whether a non-finite input sits anywhere in that batch, so the bypass keeps the
-        reference's scope."""
+        reference's scope.
+        With a Mamba2 back end (single_backend_type "mamba2") forward_batch is part of the model's function: the
+        reference scans along the windows of each forward call (sdiar.h, sd_tsvad_config.backend), so the logits
+        depend on which windows share a group and in which order; a group wider than max_batch is refused."""
         import torch
         B, T_fb, F = ref_speech.shape
         T_lab = labels if isinstance(labels, int) else labels.size(-1)
@@ -95,6 +99,9 @@ class TSVADModel(_lib.Handle):
                 for s in range(0, B, step):
                     e = min(B, s + step)
                     self.forward(ref[s:e], ts[s:e], T_lab, out=out[s:e], check=False, forward_batch=G)
+            elif self.cfg.backend:
+                raise ValueError(f"a Mamba2 back end scans over the {G} windows of a reference forward call: "
+                                 f"create the model with max_batch >= {G} (it is {self.max_batch})")
             else:                        # a reference batch spans device forwards: its non-finite flags up front
                 for g0 in range(0, B, G):
                     g1 = min(B, g0 + G)

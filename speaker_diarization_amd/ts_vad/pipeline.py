@@ -43,12 +43,21 @@ def _ts_block(ts, dev, NS: int, B: int):
 
 
 class TSVADPipeline:
+    """batch_size: windows per reference forward call (infer.py's DataLoader batch, 64).  For the transformer and
+    conformer back ends it is a throughput knob (and the scope of BatchNorm1D's NaN bypass).  With a Mamba2 back end
+    (single_backend_type "mamba2") it is part of the model's function: the reference scans along the windows of each
+    forward call, so posteriors match a reference run only at the batch size that run used (infer.py: 64), and the
+    model's max_batch must be at least that large."""
+
     def __init__(self, model: TSVADModel, segment_shift: int = 1, batch_size: int = 64):
         self.model = model
         self.cfg = model.cfg
         self.segment_shift = segment_shift
         # a model that fixes the reference batch (the streaming decoder: batch 1) overrides it
         batch_size = getattr(model, "reference_batch_size", batch_size)
+        if getattr(self.cfg, "backend", 0) and batch_size > model.max_batch:
+            raise ValueError(f"a Mamba2 back end scans over the {batch_size} windows of a reference batch: create the "
+                             f"model with max_batch >= {batch_size} (it is {model.max_batch})")
         self.batch_size = min(batch_size, model.max_batch)
         # a device batch fuses whole reference batches: BatchNorm1D's NaN bypass keeps the reference scope
         self._fwd_kw = {"forward_batch": self.batch_size} if isinstance(model, TSVADModel) else {}

@@ -20,6 +20,12 @@ Shape = Tuple[int, ...]
 
 
 # ----------------------------------------------------------------------------- TS-VAD
+# (speech_encoder_type, single_backend_type, multi_backend_type) -> sd_tsvad_config.backend of the Mamba2 back ends.
+# Mamba v1 ("mamba", "mamba_v2"), "mamba2_unidirectional" and mamba2 behind another speech encoder are not built.
+_MAMBA2_BACKENDS = {("CAM++", "mamba2", "transformer"): 1, ("CAM++", "mamba2", "mamba2"): 2}
+MAMBA2_HEADDIM = 64   # mamba_ssm Mamba2's headdim default
+
+
 @dataclass
 class TSVADConfig:
     """Mirror of ts_vad2/model.py:40-110 (TSVADConfig) restricted to the fields
@@ -35,6 +41,10 @@ class TSVADConfig:
     single_backend_type: str = "transformer"
     multi_backend_type: str = "transformer"
     ots_vad_style: str = ""
+    # Mamba2 back ends (egs/magicdata-ramc/ts_vad2/model.py:377-403): the reference defaults; the MagicData recipe
+    # (run_ts_vad2_based_on_system_sad.sh:58-68) sets d_state 128
+    d_state: int = 64
+    expand: int = 4
     # data config
     rs_len: int = 4
     segment_shift: int = 1
@@ -64,14 +74,24 @@ class TSVADConfig:
         if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) == (
                 "ReDimNetB2", "transformer", "transformer"):
             return 4
+        if not self.ots_vad_style and (self.speech_encoder_type, self.single_backend_type,
+                                       self.multi_backend_type) in _MAMBA2_BACKENDS:
+            return 0   # CAM++ with Mamba2 back ends: variant 0 plus `backend`
         if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) != (
                 "CAM++", "transformer", "transformer"):
             raise ValueError(
                 f"unsupported TS-VAD configuration {self.speech_encoder_type}/"
                 f"{self.single_backend_type}/{self.multi_backend_type} (MI355X backend builds CAM++ "
-                "with transformer or conformer_ots_vad/lstm_ots_vad, resnet34_wespeaker, "
-                "ecapa_channel_1024_wespeaker and ReDimNetB2 with transformer)")
+                "with transformer, mamba2 + transformer, mamba2 + mamba2 or conformer_ots_vad/lstm_ots_vad, "
+                "resnet34_wespeaker, ecapa_channel_1024_wespeaker and ReDimNetB2 with transformer)")
         return 0
+
+    @property
+    def backend(self) -> int:
+        """sd_tsvad_config.backend: 0 the variant's own back end, 1 single_backend "mamba2" + multi_backend
+        "transformer", 2 "mamba2" for both (bidirectional Mamba2BlockV2 stacks, CAM++ only).  Raises like `variant`."""
+        self.variant
+        return _MAMBA2_BACKENDS.get((self.speech_encoder_type, self.single_backend_type, self.multi_backend_type), 0)
 
     @staticmethod
     def ots_vad_v1(**kw) -> "TSVADConfig":
@@ -410,13 +430,24 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         k.append(("proj_layer.bias", (e,), "small"))
     if cfg.variant in (0, 2, 3, 4):
         k.append(("pos_encoder.pe", (cfg.rs_len * cfg.label_rate, 1, e), "pe"))
-        for i in range(cfg.num_transformer_layer):
-            _tfm(k, f"single_backend.layers.{i}.", e, cfg.transformer_ffn_embed_dim)
-        k.append(("backend_down.0.weight", (e, e * ns, 5), "conv1d"))
+        backend = cfg.backend
+        if backend:
+            # Mamba2BlockV2(e, n_layer, d_state, d_conv=4, expand, bidirectional=True): the two directions are
+            # concatenated, so backend_down reads 2 e ns channels (magicdata model.py:377-403)
+            mamba2_block_v2_layout(k, "single_backend.", e, cfg.num_transformer_layer, cfg.d_state, cfg.expand)
+        else:
+            for i in range(cfg.num_transformer_layer):
+                _tfm(k, f"single_backend.layers.{i}.", e, cfg.transformer_ffn_embed_dim)
+        k.append(("backend_down.0.weight", (e, (2 if backend else 1) * e * ns, 5), "conv1d"))
         k.append(("backend_down.0.bias", (e,), "small"))
         _bn(k, "backend_down.1.bn", e)
-        for i in range(cfg.num_transformer_layer):
-            _tfm(k, f"multi_backend.layers.{i}.", e, cfg.transformer_ffn_embed_dim)
+        if backend == 2:
+            mamba2_block_v2_layout(k, "multi_backend.", e, cfg.num_transformer_layer, cfg.d_state, cfg.expand)
+            k.append(("multi_backend_proj.weight", (e, 2 * e), "linear"))   # magicdata model.py:488-504
+            k.append(("multi_backend_proj.bias", (e,), "small"))
+        else:
+            for i in range(cfg.num_transformer_layer):
+                _tfm(k, f"multi_backend.layers.{i}.", e, cfg.transformer_ffn_embed_dim)
         k.append(("fc.weight", (ns, e), "linear"))
         k.append(("fc.bias", (ns,), "small"))
     else:
@@ -450,6 +481,34 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         k.append(("fc.weight", (ns, 2 * h), "linear"))
         k.append(("fc.bias", (ns,), "small"))
     return k
+
+
+def mamba2_sizes(e: int, d_state: int, expand: int):
+    """(d_inner, heads, conv_dim, d_in_proj) of mamba_ssm's Mamba2(d_model=e, d_state, expand) at its defaults
+    (headdim 64, ngroups 1)."""
+    d_inner = expand * e
+    if d_inner % MAMBA2_HEADDIM:
+        raise ValueError(f"expand * transformer_embed_dim = {d_inner} is not a multiple of {MAMBA2_HEADDIM}")
+    heads = d_inner // MAMBA2_HEADDIM
+    return d_inner, heads, d_inner + 2 * d_state, 2 * d_inner + 2 * d_state + heads
+
+
+def mamba2_block_v2_layout(k: list, prefix: str, e: int, n_layer: int, d_state: int, expand: int):
+    """Keys of Mamba2BlockV2(bidirectional=True) (ts_vad2/mamba.py:149-213): Block(norm = RMSNorm, mixer = Mamba2,
+    mlp = Identity) per layer and direction.  mamba_ssm is CUDA-only, so no reference run pins this key set."""
+    d_inner, heads, conv_dim, d_in_proj = mamba2_sizes(e, d_state, expand)
+    for d in ("forward_blocks", "backward_blocks"):
+        for i in range(n_layer):
+            p = f"{prefix}{d}.{i}."
+            k.append((p + "norm.weight", (e,), "m2_w"))
+            k.append((p + "mixer.in_proj.weight", (d_in_proj, e), f"m2_in{heads}"))
+            k.append((p + "mixer.conv1d.weight", (conv_dim, 1, 4), "m2_conv"))
+            k.append((p + "mixer.conv1d.bias", (conv_dim,), "m2_conv"))
+            k.append((p + "mixer.dt_bias", (heads,), "m2_dtb"))
+            k.append((p + "mixer.A_log", (heads,), "m2_alog"))
+            k.append((p + "mixer.D", (heads,), "ones"))
+            k.append((p + "mixer.norm.weight", (d_inner,), "m2_w"))
+            k.append((p + "mixer.out_proj.weight", (e, d_inner), "linear"))
 
 
 def _tfm(k: list, p: str, e: int, ffn: int):
@@ -519,6 +578,17 @@ ER_BN_BIAS = 0.3
 RD_GAIN = {"rd_conv": 1.0, "rd_out": 0.5}
 
 
+# Seeded Mamba2 init (mamba2_block_v2_layout), in the spirit of mamba_ssm's: A = U[1, 16], dt_bias the inverse softplus
+# of a log-uniform dt in [1e-3, 1e-1], D = 1.  in_proj's z / x / Bm / Cm rows give outputs of standard deviation
+# M2_IN_GAIN on the normalised rows; its dt rows are drawn wider (M2_DT_GAIN) so that dt_raw moves dt over its whole
+# range from step to step: tests/test_mamba2_host.py asserts that the per-step decay exp(dt A) falls both below 0.5 and
+# above 0.9 and that the state term carries at least a tenth of rms(y), so a test cannot pass on a scan that forgets
+# everything or never decays.  At d_state 16 with two heads, the smallest operator case, the state term's share is
+# 0.06 at gains (1.0, 3.0) and (1.5, 2.5) and 0.12 at these.
+M2_IN_GAIN = 1.25
+M2_DT_GAIN = 3.5
+
+
 def _init(rng: np.random.Generator, shape: Shape, kind: str) -> np.ndarray:
     if kind == "nbt":
         return np.array(0, dtype=np.int64)
@@ -556,6 +626,18 @@ def _init(rng: np.random.Generator, shape: Shape, kind: str) -> np.ndarray:
         v = rng.uniform(0.5, 1.5, n)
     elif kind == "ones":
         v = np.ones(n)
+    elif kind == "m2_w":                  # RMSNorm weights: far enough from 1 that a dropped weight shows
+        v = rng.uniform(0.7, 1.3, n)
+    elif kind.startswith("m2_in"):        # in_proj, kind "m2_in<heads>": its last <heads> rows are dt's (gains above)
+        v = rng.standard_normal(n).reshape(shape) * (M2_IN_GAIN / np.sqrt(fan_in))
+        v[shape[0] - int(kind[5:]):] *= M2_DT_GAIN / M2_IN_GAIN
+    elif kind == "m2_conv":               # nn.Conv1d(groups = channels, k 4): U(+-1 / sqrt(4)), weight and bias
+        v = rng.uniform(-0.5, 0.5, n)
+    elif kind == "m2_dtb":                # inverse softplus of dt ~ log-uniform [1e-3, 1e-1] (mamba_ssm's dt_min / dt_max)
+        dt = np.exp(rng.uniform(np.log(1e-3), np.log(1e-1), n))
+        v = dt + np.log(-np.expm1(-dt))
+    elif kind == "m2_alog":               # A ~ U[1, 16] (mamba_ssm's A_init_range)
+        v = np.log(rng.uniform(1.0, 16.0, n))
     elif kind in ("er_w", "er_m", "er_v"):
         return _init(rng, shape, "bn" + kind[2:])
     elif kind == "er_b":
