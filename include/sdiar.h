@@ -690,6 +690,16 @@ int sd_op_cam_dense(const void* x, int B, int T, int ld, int cin, int dil, const
 int sd_op_fcm_block(const void* x, int B, int H, int W, int stride, const float* w1, const float* a1, const float* b1,
                     const float* w2, const float* a2, const float* b2, const float* wsc, const float* asc,
                     const float* bsc, void* out, int fused, void* stream);
+/* The CAM++ FCM stem + layer1.0 (cam_pplus_wespeaker.py:240-308) from the fbank (B, W, F) fp32: stem = relu(bn(conv3x3(
+ * fbank, 1 -> 32, pad 1))) with stem_w fp32 (32, 1, 3, 3) and stem_alpha / stem_beta the folded BatchNorm [32], then
+ * the stride-2 BasicResBlock of sd_op_fcm_block (w1 .. bsc as there; the shortcut is required).  out bf16 NHWC
+ * (B, (F - 1) / 2 + 1, W, 32).  fused 1: one launch (fcm_conv.hip fcm_stem_block_kernel; raises where it does not
+ * apply, e.g. W < 113; out must not overlap the fbank); 0: the trunk's two launches (stem computed inside conv1) on
+ * scratch maps.  Both give the same values wherever fused 1 is accepted. */
+int sd_op_fcm_stem_block(const float* fbank, int B, int W, int F, const float* stem_w, const float* stem_alpha,
+                         const float* stem_beta, const float* w1, const float* a1, const float* b1, const float* w2,
+                         const float* a2, const float* b2, const float* wsc, const float* asc, const float* bsc,
+                         void* out, int fused, void* stream);
 /* Diagnostics: while `stamps` (device, >= 16 u64 per workgroup of a launch) is non-NULL, every cam_dense
  * launch records its workgroups' phase-boundary s_memrealtime stamps there (tools/cam_dense_probe.py). */
 int sd_debug_cam_dense_probe(void* stamps);

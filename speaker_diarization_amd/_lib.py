@@ -249,6 +249,7 @@ _SIGS = {
                                 c_int, c_void_p]),
     "sd_op_fcm_block": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "sd_op_fcm_stem_block": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 13 + [c_int, c_void_p]),
     "sd_op_conv1d": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                              c_int, c_int, c_void_p, c_int, c_void_p]),
     "sd_op_conv2d": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,

@@ -239,14 +239,33 @@ Tens CamTrunk::forward(const float* fbank, int B, int Tf, hipStream_t st, int b0
   // layer1.1: A -> B; conv2 B -> C + A
   // layer2.0: C(40) -> A(20); shortcut C -> B(20); conv2 A -> C(20) + B
   // layer2.1: C -> A; conv2 A -> B + C
-  // bf16: layer1.0's conv1 computes the stem (head.conv1 + bn1 + relu) from the fbank in LDS, and the two
+  // bf16: every block is one launch (fcm_block_kernel; layer1.0 with the stem computed from the fbank in LDS:
+  // fcm_stem_block_kernel, fbank -> A(40)).  With SDIAR_NO_FCM_BLOCK, or where those do not apply, the pairs above:
+  // layer1.0's conv1 computes the stem (head.conv1 + bn1 + relu) from the fbank in LDS, and the two
   // strided blocks' shortcuts ride on their conv1's centre tap (fcm_conv.hip FcmFuse).
   float* cur = fcmA;
   int H = F, W = Tf;
   float* const bufs[3] = {fcmA, fcmB, fcmC};
   for (size_t i = 0; i < fcm_blocks_.size(); ++i) {
     const ResBlockL& rb = fcm_blocks_[i];
-    if (bf && i > 0 && fcm_block_enabled()) {   // the whole block in one launch (layer1.0 keeps its stem-fused pair)
+    if (bf && i == 0 && fcm_block_enabled() && rb.has_sc && rb.stride == 2) {   // stem + layer1.0 in one launch
+      FcmStemBlockArgs a;
+      a.fbank = ref; a.B = B; a.W = W; a.F = F;
+      a.stem_w = fcm_conv1_.pre_s; a.stem_alpha = fcm_conv1_.alpha; a.stem_beta = fcm_conv1_.beta;
+      a.w1 = rb.c1.w.w; a.a1 = rb.c1.alpha; a.b1 = rb.c1.beta;
+      a.w2 = rb.c2.w.w; a.a2 = rb.c2.alpha; a.b2 = rb.c2.beta;
+      a.wsc = rb.sc.w.w; a.asc = rb.sc.alpha; a.bsc = rb.sc.beta;
+      a.out = fcmA;   // where the pair leaves layer1.0's output
+      const bool w32 = rb.c1.w.N == 32 && rb.c1.w.K == 288 && rb.c2.w.N == 32 && rb.c2.w.K == 288 &&
+                       rb.sc.w.N == 32 && rb.sc.w.K == 32;
+      if (w32 && fcm_stem_block_supported(a)) {   // false below W 113: the pair's fp32 stem serves those
+        conv_fcm_stem_block(a, st);
+        cur = fcmA;
+        H = (H - 1) / rb.stride + 1;
+        continue;
+      }
+    }
+    if (bf && i > 0 && fcm_block_enabled()) {   // the whole block in one launch
       FcmBlockArgs a;
       a.x = cur; a.B = B; a.H = H; a.W = W; a.C = rb.c1.w.Cin; a.stride = rb.stride; a.bf16 = true;
       a.w1 = rb.c1.w.w; a.a1 = rb.c1.alpha; a.b1 = rb.c1.beta;

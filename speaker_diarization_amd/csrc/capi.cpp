@@ -1315,6 +1315,53 @@ int sd_op_fcm_block(const void* x, int B, int H, int W, int stride, const float*
   });
 }
 
+int sd_op_fcm_stem_block(const float* fbank, int B, int W, int F, const float* stem_w, const float* stem_alpha,
+                         const float* stem_beta, const float* w1, const float* a1, const float* b1, const float* w2,
+                         const float* a2, const float* b2, const float* wsc, const float* asc, const float* bsc,
+                         void* out, int fused, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(fbank && out && stem_w && stem_alpha && stem_beta && w1 && a1 && b1 && w2 && a2 && b2 && B > 0 && W > 0 &&
+                 F > 0,
+             sd::kErrInvalid, "fcm_stem_block: bad argument");
+    SD_CHECK(wsc && asc && bsc, sd::kErrInvalid, "fcm_stem_block: layer1.0 has a shortcut");
+    PackedScratch p1(w1, 32, 32, 9, true, st), p2(w2, 32, 32, 9, true, st), ps(wsc, 32, 32, 1, true, st);
+    const int Ho = (F - 1) / 2 + 1;
+    if (fused) {
+      sd::FcmStemBlockArgs a;
+      a.fbank = fbank; a.B = B; a.W = W; a.F = F;
+      a.stem_w = stem_w; a.stem_alpha = stem_alpha; a.stem_beta = stem_beta;
+      a.w1 = p1.p; a.a1 = a1; a.b1 = b1; a.w2 = p2.p; a.a2 = a2; a.b2 = b2;
+      a.wsc = ps.p; a.asc = asc; a.bsc = bsc;
+      a.out = out;
+      sd::conv_fcm_stem_block(a, st);   // raises on arguments the kernel cannot compute
+      return;
+    }
+    // the trunk's two launches (below W 113: its fp32 stem and three) on three scratch maps
+    const size_t map_bytes = (size_t)B * F * W * 64;
+    Scratch m0(map_bytes, st), m1(map_bytes, st), m2(map_bytes, st);
+    sd::ResBlockL rb;
+    rb.stride = 2;
+    rb.has_sc = true;
+    auto conv = [](const void* w, int taps, const float* al, const float* be) {
+      sd::ConvL L;
+      L.w.w = w; L.w.N = 32; L.w.Cin = 32; L.w.K = 32 * taps * taps; L.w.kh = taps; L.w.kw = taps;
+      L.alpha = al; L.beta = be;
+      return L;
+    };
+    rb.c1 = conv(p1.p, 3, a1, b1);
+    rb.c2 = conv(p2.p, 3, a2, b2);
+    rb.sc = conv(ps.p, 1, asc, bsc);
+    sd::FcmFuse stem;
+    stem.fbank = fbank; stem.fb_F = F;
+    stem.stem_w = stem_w; stem.stem_alpha = stem_alpha; stem.stem_beta = stem_beta;
+    float* const bufs[3] = {static_cast<float*>(m0.p), static_cast<float*>(m1.p), static_cast<float*>(m2.p)};
+    int h = F, w = W;
+    const float* r = sd::fcm_block_pair(rb, bufs, bufs[0], true, B, h, w, stem, st);
+    SD_HIP(hipMemcpyAsync(out, r, (size_t)B * Ho * W * 64, hipMemcpyDeviceToDevice, st));
+  });
+}
+
 int sd_op_mha_block(const void* y, const float* w, const float* bias, int nseq, int T, const int* key_len, void* out,
                     int variant, int flags, void* stream) {
   return guard([&] {

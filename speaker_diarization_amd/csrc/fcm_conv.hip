@@ -178,6 +178,15 @@ __global__ __launch_bounds__(256) void fcm_conv3x3_kernel(ConvGemmArgs p, int n_
 // consecutive channels of one frame: 8-B bf16 stores / residual loads straight from
 // the accumulators, no LDS epilogue.
 constexpr int kBandThreads = 512;
+
+// 4-B-per-lane buffer -> LDS DMA (common.h dma_lds16_buf's contract: lane i's dword lands at lds + 4 i, out-of-range
+// offsets land as zeros, the caller owns the ordering).
+__device__ __forceinline__ void dma_lds4_buf(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff,
+                                             const void __attribute__((address_space(3)))* lds) {
+  const uint32_t m0v = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(lds));
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds" ::"s"(m0v), "v"(voff), "s"(rsrc)
+               : "memory", "m0");
+}
 constexpr int kBandVecPer = 15;     // 16-B vectors per thread per band (NR * (W+2) * 4 <= 7680)
 constexpr uint32_t kFcmOOB = 0x80000000u;
 
@@ -201,6 +210,59 @@ __host__ __device__ inline int band_channel(int i, int nt) { return 8 * (i >> 2)
 // next band's prefetch and this band's output stores; with STEM also the MFMA stem (see the stem block below).
 constexpr int kToutBlk = 4;
 constexpr int kToutRow = 328;   // LDS frame-row stride in bf16 (656 B: 16-B aligned, rows 36 banks apart)
+
+// MFMA stem (head.conv1 1 -> 32, 3x3, pad 1, + BN + ReLU; shared by the band kernel's STEM path and
+// fcm_stem_block_kernel): v_mfma_f32_32x32x16_bf16 with the 32 channels as rows and 32 pixels as columns; k = the 9
+// taps (dh, dw) in order, then beta's bf16 hi and lo parts against a constant 1 (BN folded: A = bf16(alpha_c * w_c),
+// so a pixel is relu(sum + beta) with no epilogue FMAs).  A row m is channel 16 ((m >> 2) & 1) + 4 (m >> 3) + (m & 3),
+// so accumulator i of lane half h is channel 16 h + i: a lane holds 16 contiguous channels of its pixel.
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+
+// This lane's part of the A operand.
+__device__ __forceinline__ bf16x8 fcm_stem_a(const float* stem_w, const float* stem_alpha, const float* stem_beta,
+                                             int lane) {
+  const int m = lane & 31, h = lane >> 5;
+  const int c = 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3);
+  const float al = stem_alpha[c], be = stem_beta[c];
+  float e[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) e[j] = al * stem_w[c * 9 + min(8 * h + j, 8)];
+  const float bh = __uint_as_float(f2bf_bits(be) << 16);
+  if (h) {
+    e[1] = bh;
+    e[2] = __uint_as_float(f2bf_bits(be - bh) << 16);
+#pragma unroll
+    for (int j = 3; j < 8; ++j) e[j] = 0.f;
+  }
+  const uint32_t w4[4] = {pack_bf16x2(e[0], e[1]), pack_bf16x2(e[2], e[3]), pack_bf16x2(e[4], e[5]),
+                          pack_bf16x2(e[6], e[7])};
+  return *reinterpret_cast<const bf16x8*>(w4);
+}
+
+// The stem sums of 32 pixels, pixel lane & 31 per lane: t0 = this lane's top-left tap in an fp32 fbank tile with bin
+// stride sh and frame stride sw (tap (dh, dw) at t0[dh * sh + dw * sw]); returns the lane's 16 channels before the ReLU.
+__device__ __forceinline__ floatx16 fcm_stem_mfma(const bf16x8& stem_a, const float* t0, int sh, int sw, int lane) {
+  const int h = lane >> 5;
+  float tp[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) tp[k] = t0[(k / 3) * sh + (k % 3) * sw];
+  float e[8];
+  e[0] = h ? tp[8] : tp[0];
+  e[1] = h ? 1.f : tp[1];
+  e[2] = h ? 1.f : tp[2];
+#pragma unroll
+  for (int j = 3; j < 8; ++j) e[j] = h ? 0.f : tp[j];
+  const uint32_t b4[4] = {pack_bf16x2(e[0], e[1]), pack_bf16x2(e[2], e[3]), pack_bf16x2(e[4], e[5]),
+                          pack_bf16x2(e[6], e[7])};
+  floatx16 acc = {};
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(stem_a, *reinterpret_cast<const bf16x8*>(b4), acc, 0, 0, 0);
+}
+
+// ReLU + bf16 of the lane's 16 channels (two 16-B chunks); a pixel outside the map is the next conv's zero padding.
+__device__ __forceinline__ void fcm_stem_pack(const floatx16& acc, bool ok, uint32_t* o) {
+#pragma unroll
+  for (int u = 0; u < 8; ++u) o[u] = ok ? pack_bf16x2(fmaxf(acc[2 * u], 0.f), fmaxf(acc[2 * u + 1], 0.f)) : 0u;
+}
 
 template <int R, int SH, bool STEM = false, bool SC = false, bool TOUT = false, bool SMF = false>
 __global__ __launch_bounds__(kBandThreads) void fcm_conv3x3_band_kernel(ConvGemmArgs p, FcmFuse f, int n_bands,
@@ -294,32 +356,10 @@ __global__ __launch_bounds__(kBandThreads) void fcm_conv3x3_band_kernel(ConvGemm
   float* fbs = reinterpret_cast<float*>(xs + NR * Wp * kPS);
   const int fb_n = (NR + 2) * (Wp + 2);
   constexpr int kFbPer = 5;   // fbank tile floats per thread (<= 2560)
-  // MFMA stem: v_mfma_f32_32x32x16_bf16 with the 32 channels as rows and 32 staged pixels as
-  // columns; k = the 9 taps (dh, dw) in order, then beta's bf16 hi and lo parts against a constant 1 (BN
-  // folded: A = bf16(alpha_c * w_c), so a pixel is relu(sum + beta) with no epilogue FMAs).  A row m is
-  // channel 16 ((m >> 2) & 1) + 4 (m >> 3) + (m & 3), so accumulator i of lane half h is channel 16 h + i
-  // and a lane stores its pixel's 16 contiguous channels as two 16-B LDS writes.
+  // MFMA stem (fcm_stem_a / fcm_stem_mfma / fcm_stem_pack above): 32 staged pixels per MFMA, a lane stores its
+  // pixel's 16 contiguous channels as two 16-B LDS writes.
   bf16x8 stem_a;
-  if constexpr (STEM) {
-    {
-      const int m = lane & 31, h = lane >> 5;
-      const int c = 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3);
-      const float al = f.stem_alpha[c], be = f.stem_beta[c];
-      float e[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) e[j] = al * f.stem_w[c * 9 + min(8 * h + j, 8)];
-      const float bh = __uint_as_float(f2bf_bits(be) << 16);
-      if (h) {
-        e[1] = bh;
-        e[2] = __uint_as_float(f2bf_bits(be - bh) << 16);
-#pragma unroll
-        for (int j = 3; j < 8; ++j) e[j] = 0.f;
-      }
-      const uint32_t w4[4] = {pack_bf16x2(e[0], e[1]), pack_bf16x2(e[2], e[3]), pack_bf16x2(e[4], e[5]),
-                              pack_bf16x2(e[6], e[7])};
-      stem_a = *reinterpret_cast<const bf16x8*>(w4);
-    }
-  }
+  if constexpr (STEM) stem_a = fcm_stem_a(f.stem_w, f.stem_alpha, f.stem_beta, lane);
   // fbank value (bin hb - 1 + j, frame w0 - 1 + x) of a band, j < NR + 2, x < Wp + 2; zero outside the map
   auto load_fb = [&](int band, float* v) {
     const int tt = band % n_tt, bh = band / n_tt;
@@ -363,27 +403,11 @@ __global__ __launch_bounds__(kBandThreads) void fcm_conv3x3_band_kernel(ConvGemm
         const int ngr = (Wp + 31) >> 5;   // 32-pixel groups per staged row (reads past Wp hit the tile's pad)
         for (int g = wv; g < NR * ngr; g += kBandThreads / 64) {
           const int rr = g / ngr, px = (g - rr * ngr) * 32 + n;
-          const float* t0 = fbs + rr * (Wp + 2) + px;
-          float tp[9];
-#pragma unroll
-          for (int k = 0; k < 9; ++k) tp[k] = t0[(k / 3) * (Wp + 2) + k % 3];
-          float e[8];
-          e[0] = h ? tp[8] : tp[0];
-          e[1] = h ? 1.f : tp[1];
-          e[2] = h ? 1.f : tp[2];
-#pragma unroll
-          for (int j = 3; j < 8; ++j) e[j] = h ? 0.f : tp[j];
-          const uint32_t b4[4] = {pack_bf16x2(e[0], e[1]), pack_bf16x2(e[2], e[3]), pack_bf16x2(e[4], e[5]),
-                                  pack_bf16x2(e[6], e[7])};
-          typedef float floatx16 __attribute__((ext_vector_type(16)));
-          floatx16 acc = {};
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(stem_a, *reinterpret_cast<const bf16x8*>(b4), acc, 0, 0, 0);
+          const floatx16 acc = fcm_stem_mfma(stem_a, fbs + rr * (Wp + 2) + px, Wp + 2, 1, lane);
           if (px < Wp) {
             const bool ok = (unsigned)(hb + rr) < (unsigned)p.H && (unsigned)(w0 + px) < (unsigned)W;
             uint32_t o[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-              o[u] = ok ? pack_bf16x2(fmaxf(acc[2 * u], 0.f), fmaxf(acc[2 * u + 1], 0.f)) : 0u;
+            fcm_stem_pack(acc, ok, o);
             uint16_t* dst = xs + (rr * Wp + px) * kPS + 16 * h;
             *reinterpret_cast<uint4*>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
             *reinterpret_cast<uint4*>(dst + 8) = make_uint4(o[4], o[5], o[6], o[7]);
@@ -761,6 +785,136 @@ struct FbGeom {
   static constexpr int kLds = 2 * kSlot + kImg + 6 * 32 * 4;
 };
 
+// The two conv phases of a band, shared by fcm_block_kernel and fcm_stem_block_kernel (R = 2 * HR2 output rows,
+// NI = 2 * HR1 = R + 2 intermediate rows).  sx: the staged input rows (ring_pos layout, kFbPx frames per row), img: the
+// intermediate image (kFbIW frames per row), prm: the folded BN tables [a1 b1 a2 b2 asc bsc][32] in LDS.
+constexpr int kFbInRow = kFbPx * 32, kFbImRow = kFbIW * 32;   // LDS row strides in bf16
+
+// channels 8q .. 8q+7 of table k (accumulator (nt, r) is channel 8q + 4nt + r)
+__device__ __forceinline__ void fcm_blk_prm(const float* prm, int k, int q, float* v) {
+  const floatx4 lo = *reinterpret_cast<const floatx4*>(prm + k * 32 + q * 8);
+  const floatx4 hi = *reinterpret_cast<const floatx4*>(prm + k * 32 + q * 8 + 4);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) v[u] = lo[u], v[4 + u] = hi[u];
+}
+
+// conv1 (freq stride SH) + BN1 + ReLU: intermediate rows half * HR1 .. + HR1 of the band -> image.  in_dw[dw]: this
+// lane's LDS position in the first staged row its wave reads, frame fr + dw; im_wr: its position in the first image
+// row it writes.  Intermediate row mi of the band is map row ho0 - 1 + mi, frame fr is map frame w0 - 1 + fr.
+template <int SH, int HR1>
+__device__ __forceinline__ void fcm_blk_conv1(const uint16_t* sx, uint16_t* img, const float* prm,
+                                              const bf16x8 (&wf1)[9][2], const int (&in_dw)[3], int im_wr, int half,
+                                              int q, int ho0, int w0, int fr, int Ho, int W) {
+  floatx4 acc[HR1][2];
+  constexpr int NJ = (HR1 - 1) * SH + 3;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+    for (int dw = 0; dw < 3; ++dw) {
+      const bf16x8 af = *reinterpret_cast<const bf16x8*>(sx + in_dw[dw] + j * kFbInRow);
+#pragma unroll
+      for (int dh = 0; dh < 3; ++dh) {
+        const int jm = j - dh;
+        if (jm >= 0 && jm % SH == 0 && jm / SH < HR1) {
+          const int m = jm / SH;
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt) {
+            if (dh == 0 && dw == 0) acc[m][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
+            acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf1[dh * 3 + dw][nt], af, acc[m][nt], 0, 0, 0);
+          }
+        }
+      }
+    }
+    if (j >= 2 && (j - 2) % SH == 0 && (j - 2) / SH < HR1) {   // row m has all nine taps
+      const int m = (j - 2) / SH, mi = half * HR1 + m;
+      const int hi = ho0 - 1 + mi, wi = w0 - 1 + fr;
+      const bool ok = (unsigned)hi < (unsigned)Ho && (unsigned)wi < (unsigned)W;
+      float al[8], be[8], v[8];
+      fcm_blk_prm(prm, 0, q, al);
+      fcm_blk_prm(prm, 1, q, be);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = fmaxf(fmaf(acc[m][u >> 2][u & 3], al[u], be[u]) + 0.f, 0.f);
+      uint4 o = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
+                           pack_bf16x2(v[6], v[7]));
+      if (!ok) o = make_uint4(0u, 0u, 0u, 0u);   // conv2's padding (a select: 0 * NaN would be NaN)
+      *reinterpret_cast<uint4*>(img + im_wr + m * kFbImRow) = o;
+    }
+    __builtin_amdgcn_sched_barrier(0);   // keep the next rows' fragment reads from piling up in registers
+  }
+}
+
+// conv2 + BN2 + residual + ReLU: output rows half * HR2 .. + HR2 of the band, one 16-B buffer store per row and lane
+// (ALWAYS issued: rows / frames outside the map go to an out-of-range offset; fcm_block_kernel counts them).
+// im_dw[dw]: this lane's position in the first image row its wave reads; in_res: its position in the staged row of
+// the residual's operand for its first output row.
+template <int SH, int HR2>
+__device__ __forceinline__ void fcm_blk_conv2(const uint16_t* sx, const uint16_t* img, const float* prm,
+                                              const bf16x8 (&wf2)[9][2], const bf16x8 (&wsc)[2],
+                                              const int (&im_dw)[3], int in_res, __amdgpu_buffer_rsrc_t ro, int half,
+                                              int q, int b, int ho0, int w0, int fr, int Ho, int W) {
+  floatx4 acc[HR2][2];
+  constexpr int NJ = HR2 + 2;
+  const int row0 = half * HR2;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+#pragma unroll
+    for (int dw = 0; dw < 3; ++dw) {
+      const bf16x8 af = *reinterpret_cast<const bf16x8*>(img + im_dw[dw] + j * kFbImRow);
+#pragma unroll
+      for (int dh = 0; dh < 3; ++dh) {
+        const int m = j - dh;
+        if (m >= 0 && m < HR2) {
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt) {
+            if (dh == 0 && dw == 0) acc[m][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
+            acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf2[dh * 3 + dw][nt], af, acc[m][nt], 0, 0, 0);
+          }
+        }
+      }
+    }
+    if (j >= 2) {
+      const int m = j - 2, r = row0 + m;
+      const int ho = ho0 + r, wo = w0 + fr;
+      float rv[8];
+      if constexpr (SH == 1) {   // the block's input at (ho, wo): staged row r + 2, frame fr + 2
+        const u32x4_t r4 = *reinterpret_cast<const u32x4_t*>(sx + in_res + m * kFbInRow);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          rv[2 * u] = __uint_as_float(r4[u] << 16);
+          rv[2 * u + 1] = __uint_as_float(r4[u] & 0xffff0000u);
+        }
+      } else {   // 1x1 stride-2 shortcut + BN of input (2 ho, wo): staged row 2 r + 3, rounded to bf16 as stored
+        const bf16x8 cf = *reinterpret_cast<const bf16x8*>(sx + in_res + 2 * m * kFbInRow);
+        floatx4 sacc[2] = {floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+          sacc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wsc[nt], cf, sacc[nt], 0, 0, 0);
+        float sal[8], sbe[8];
+        fcm_blk_prm(prm, 4, q, sal);
+        fcm_blk_prm(prm, 5, q, sbe);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const uint32_t w2 = pack_bf16x2(fmaf(sacc[(2 * u) >> 2][(2 * u) & 3], sal[2 * u], sbe[2 * u]),
+                                          fmaf(sacc[(2 * u + 1) >> 2][(2 * u + 1) & 3], sal[2 * u + 1], sbe[2 * u + 1]));
+          rv[2 * u] = __uint_as_float(w2 << 16);
+          rv[2 * u + 1] = __uint_as_float(w2 & 0xffff0000u);
+        }
+      }
+      float al[8], be[8], v[8];
+      fcm_blk_prm(prm, 2, q, al);
+      fcm_blk_prm(prm, 3, q, be);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = fmaxf(fmaf(acc[m][u >> 2][u & 3], al[u], be[u]) + rv[u], 0.f);
+      const bool ok = ho < Ho && fr < kFbTW && wo < W;
+      const uint32_t off = ok ? (uint32_t)(((((int64_t)b * Ho + ho) * W + wo) * 32 + q * 8) * 2) : kFcmOOB;
+      const u32x4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
+                         pack_bf16x2(v[6], v[7])};
+      __builtin_amdgcn_raw_buffer_store_b128(o, ro, off, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 template <int SH>
 __global__ __launch_bounds__(kBandThreads) void fcm_block_kernel(FcmBlockArgs p, int Ho, int n_bands, int n_tt) {
   using G = FbGeom<SH>;
@@ -835,17 +989,9 @@ __global__ __launch_bounds__(kBandThreads) void fcm_block_kernel(FcmBlockArgs p,
     }
   };
   auto barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-  // channels 8q .. 8q+7 of table k (accumulator (nt, r) is channel 8q + 4nt + r)
-  auto load_prm = [&](int k, float* v) {
-    const floatx4 lo = *reinterpret_cast<const floatx4*>(prm + k * 32 + q * 8);
-    const floatx4 hi = *reinterpret_cast<const floatx4*>(prm + k * 32 + q * 8 + 4);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = lo[u], v[4 + u] = hi[u];
-  };
   // LDS positions (bf16 units) of this lane in the first row its wave reads or writes; the rows after it are a
   // constant stride apart (an immediate offset), so these few registers address everything
   const int fr = col * 16 + l15;   // this lane's intermediate frame (w0 - 1 + fr) / output frame (w0 + fr)
-  constexpr int kInRow = kFbPx * 32, kImRow = kFbIW * 32;
   int in_dw[3], im_dw[3];
 #pragma unroll
   for (int dw = 0; dw < 3; ++dw) {
@@ -876,109 +1022,13 @@ __global__ __launch_bounds__(kBandThreads) void fcm_block_kernel(FcmBlockArgs p,
     const int b = bh / n_rb, ho0 = (bh % n_rb) * R, w0 = tt * kFbTW;
     const uint16_t* sx = xs + (i & 1) * (G::kSlot / 2);
 
-    {   // ---- conv1 + BN1 + ReLU: intermediate rows half * HR1 .. + HR1 of the band -> image
-      floatx4 acc[HR1][2];
-      constexpr int NJ = (HR1 - 1) * SH + 3;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-#pragma unroll
-        for (int dw = 0; dw < 3; ++dw) {
-          const bf16x8 af = *reinterpret_cast<const bf16x8*>(sx + in_dw[dw] + j * kInRow);
-#pragma unroll
-          for (int dh = 0; dh < 3; ++dh) {
-            const int jm = j - dh;
-            if (jm >= 0 && jm % SH == 0 && jm / SH < HR1) {
-              const int m = jm / SH;
-#pragma unroll
-              for (int nt = 0; nt < 2; ++nt) {
-                if (dh == 0 && dw == 0) acc[m][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
-                acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf1[dh * 3 + dw][nt], af, acc[m][nt], 0, 0, 0);
-              }
-            }
-          }
-        }
-        if (j >= 2 && (j - 2) % SH == 0 && (j - 2) / SH < HR1) {   // row m has all nine taps
-          const int m = (j - 2) / SH, mi = half * HR1 + m;
-          const int hi = ho0 - 1 + mi, wi = w0 - 1 + fr;
-          const bool ok = (unsigned)hi < (unsigned)Ho && (unsigned)wi < (unsigned)W;
-          float al[8], be[8], v[8];
-          load_prm(0, al);
-          load_prm(1, be);
-#pragma unroll
-          for (int u = 0; u < 8; ++u) v[u] = fmaxf(fmaf(acc[m][u >> 2][u & 3], al[u], be[u]) + 0.f, 0.f);
-          uint4 o = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
-                               pack_bf16x2(v[6], v[7]));
-          if (!ok) o = make_uint4(0u, 0u, 0u, 0u);   // conv2's padding (a select: 0 * NaN would be NaN)
-          *reinterpret_cast<uint4*>(img + im_wr + m * kImRow) = o;
-        }
-        __builtin_amdgcn_sched_barrier(0);   // keep the next rows' fragment reads from piling up in registers
-      }
-    }
+    // ---- conv1 + BN1 + ReLU: intermediate rows half * HR1 .. + HR1 of the band -> image
+    fcm_blk_conv1<SH, HR1>(sx, img, prm, wf1, in_dw, im_wr, half, q, ho0, w0, fr, Ho, W);
     barrier();   // the image is complete
 
-    {   // ---- conv2 + BN2 + residual + ReLU: output rows half * HR2 .. + HR2 of the band
-      floatx4 acc[HR2][2];
-      constexpr int NJ = HR2 + 2;
-      const int row0 = half * HR2;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-#pragma unroll
-        for (int dw = 0; dw < 3; ++dw) {
-          const bf16x8 af = *reinterpret_cast<const bf16x8*>(img + im_dw[dw] + j * kImRow);
-#pragma unroll
-          for (int dh = 0; dh < 3; ++dh) {
-            const int m = j - dh;
-            if (m >= 0 && m < HR2) {
-#pragma unroll
-              for (int nt = 0; nt < 2; ++nt) {
-                if (dh == 0 && dw == 0) acc[m][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
-                acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf2[dh * 3 + dw][nt], af, acc[m][nt], 0, 0, 0);
-              }
-            }
-          }
-        }
-        if (j >= 2) {
-          const int m = j - 2, r = row0 + m;
-          const int ho = ho0 + r, wo = w0 + fr;
-          float rv[8];
-          if constexpr (SH == 1) {   // the block's input at (ho, wo): staged row r + 2, frame fr + 2
-            const u32x4_t r4 = *reinterpret_cast<const u32x4_t*>(sx + in_res + m * kInRow);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              rv[2 * u] = __uint_as_float(r4[u] << 16);
-              rv[2 * u + 1] = __uint_as_float(r4[u] & 0xffff0000u);
-            }
-          } else {   // 1x1 stride-2 shortcut + BN of input (2 ho, wo): staged row 2 r + 3, rounded to bf16 as stored
-            const bf16x8 cf = *reinterpret_cast<const bf16x8*>(sx + in_res + 2 * m * kInRow);
-            floatx4 sacc[2] = {floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-              sacc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wsc[nt], cf, sacc[nt], 0, 0, 0);
-            float sal[8], sbe[8];
-            load_prm(4, sal);
-            load_prm(5, sbe);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const uint32_t w2 = pack_bf16x2(fmaf(sacc[(2 * u) >> 2][(2 * u) & 3], sal[2 * u], sbe[2 * u]),
-                                              fmaf(sacc[(2 * u + 1) >> 2][(2 * u + 1) & 3], sal[2 * u + 1], sbe[2 * u + 1]));
-              rv[2 * u] = __uint_as_float(w2 << 16);
-              rv[2 * u + 1] = __uint_as_float(w2 & 0xffff0000u);
-            }
-          }
-          float al[8], be[8], v[8];
-          load_prm(2, al);
-          load_prm(3, be);
-#pragma unroll
-          for (int u = 0; u < 8; ++u) v[u] = fmaxf(fmaf(acc[m][u >> 2][u & 3], al[u], be[u]) + rv[u], 0.f);
-          const bool ok = ho < Ho && fr < kFbTW && wo < W;
-          const uint32_t off = ok ? (uint32_t)(((((int64_t)b * Ho + ho) * W + wo) * 32 + q * 8) * 2) : kFcmOOB;
-          const u32x4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
-                             pack_bf16x2(v[6], v[7])};
-          __builtin_amdgcn_raw_buffer_store_b128(o, ro, off, 0, 0);   // always issued: see "Ordering" above
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
+    // ---- conv2 + BN2 + residual + ReLU: output rows half * HR2 .. + HR2 of the band; its HR2 stores are
+    // always issued: see "Ordering" above
+    fcm_blk_conv2<SH, HR2>(sx, img, prm, wf2, wsc, im_dw, in_res, ro, half, q, b, ho0, w0, fr, Ho, W);
   }
 }
 
@@ -996,6 +1046,187 @@ void launch_fcm_block(const FcmBlockArgs& a, int Ho, hipStream_t st) {
   }
   const int grid = (int)std::min<int64_t>(bands, (int64_t)g_fcm_cu);
   hipLaunchKernelGGL((fcm_block_kernel<SH>), dim3(grid), dim3(kBandThreads), (size_t)G::kLds, st, a, Ho, (int)bands, n_tt);
+}
+
+// ---------------------------------------------------------------------------------
+// FCM layer1.0 in one launch (FcmStemBlockArgs): the stem (head.conv1 + BN + ReLU) of the fbank into an LDS image,
+// then the strided BasicResBlock from that image exactly as fcm_block_kernel<2> runs it from its staged input
+// (fcm_blk_conv1 / fcm_blk_conv2: same fragments, accumulation order and epilogues).  Neither the stem map, the
+// intermediate map nor the shortcut map reaches HBM: fbank in, output map out.
+//
+// A band is R = 8 output rows x 62 frames: 10 intermediate rows x 64 frames, from 21 stem rows x 66 frames (the
+// ring_pos layout of fcm_block_kernel's slots, single-buffered: it is computed, not DMA'd), from an fbank tile of
+// 23 bins x 68 frames (fp32, zero outside the map: the stem conv's padding).  The stem is the band kernel's MFMA
+// stem (fcm_stem_a / _mfma / _pack), 32 pixels per MFMA over the band's 21 x 66 pixels taken as one run (44 groups
+// over the 8 waves); stem pixels outside the map are stored as 0 (conv1's padding).  The next band's fbank tile arrives
+// by 4-B LDS-DMA (no registers: both weight sets stay resident as in fcm_block_kernel) in the other of two tiles,
+// issued after the band's first barrier and retired by a plain `vmcnt(0)` before its third, a stem and a conv1 phase
+// later and before any of the band's output stores is issued: no counted wait, nothing to prove about instruction
+// counts.  The barriers are LDS-only.  Three per band: previous band done with the stem image | stem image complete |
+// intermediate image complete (and the next tile landed).  The stem's A operand and the shortcut's weight fragments
+// are re-read from LDS per band (12 VGPRs that would otherwise be live through both conv phases).
+struct SbGeom {
+  static constexpr int R = 8, NI = R + 2, NIN = (NI - 1) * 2 + 3;   // output / intermediate / stem rows (8 / 10 / 21)
+  static constexpr int kTileH = NIN + 2, kTileW = kFbPx + 2;        // fbank tile (23 bins x 68 frames)
+  static constexpr int kTileN = kTileH * kTileW;
+  static constexpr int kTileDma = (kTileN + 63) / 64;               // 4-B DMA instructions per tile (25)
+  static constexpr int kTileDmaPer = (kTileDma + 7) / 8;            // per wave (4; the last ones of waves 1 .. 7 skipped)
+  static constexpr int kTileBytes = kTileDma * 256;
+  static constexpr int kStemPx = NIN * kFbPx;                       // stem pixels per band (1386)
+  static constexpr int kStemGroups = (kStemPx + 31) / 32;
+  static constexpr int kStem = kStemPx * 64;                        // bytes
+  static constexpr int kImg = NI * kFbIW * 64 + 128;                // + 2 pixels: the last column's dw reach
+  static constexpr int kLds = kStem + kImg + 6 * 32 * 4 + 2 * kTileBytes + 3 * 1024;   // + stem A, shortcut fragments
+};
+
+__global__ __launch_bounds__(kBandThreads) void fcm_stem_block_kernel(FcmStemBlockArgs p, int Ho, int n_bands,
+                                                                      int n_tt) {
+  using G = SbGeom;
+  constexpr int R = G::R, HR1 = G::NI / 2, HR2 = R / 2;
+  extern __shared__ __attribute__((aligned(1024))) uint16_t xs[];   // the stem image
+  uint16_t* const img = xs + G::kStem / 2;
+  float* const prm = reinterpret_cast<float*>(img + G::kImg / 2);   // [a1 b1 a2 b2 asc bsc][32]
+  float* const fbt = prm + 6 * 32;                                  // two fbank tiles [frame][bin]
+  bf16x8* const frg = reinterpret_cast<bf16x8*>(fbt + 2 * G::kTileBytes / 4);   // [stem A | wsc 0 | wsc 1][lane]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, q = lane >> 4;
+  const int col = wv & 3, half = wv >> 2;
+  const int F = p.F, W = p.W;
+  const int n_rb = (Ho + R - 1) / R;
+
+  bf16x8 wf1[9][2], wf2[9][2];
+  {
+    const uint16_t* W1 = reinterpret_cast<const uint16_t*>(p.w1);
+    const uint16_t* W2 = reinterpret_cast<const uint16_t*>(p.w2);
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        wf1[t][nt] = *reinterpret_cast<const bf16x8*>(W1 + band_channel(l15, nt) * 288 + t * 32 + q * 8);
+        wf2[t][nt] = *reinterpret_cast<const bf16x8*>(W2 + band_channel(l15, nt) * 288 + t * 32 + q * 8);
+      }
+  }
+  if (wv == 0) {
+    const uint16_t* Ws = reinterpret_cast<const uint16_t*>(p.wsc);
+    frg[lane] = fcm_stem_a(p.stem_w, p.stem_alpha, p.stem_beta, lane);
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+      frg[(1 + nt) * 64 + lane] = *reinterpret_cast<const bf16x8*>(Ws + band_channel(l15, nt) * 32 + q * 8);
+  }
+  if (tid < 6 * 32) {
+    const int k = tid >> 5, c = tid & 31;
+    const float* const tab[6] = {p.a1, p.b1, p.a2, p.b2, p.asc, p.bsc};
+    float v = 0.f;
+#pragma unroll
+    for (int u = 0; u < 6; ++u)
+      if (k == u) v = tab[u][c];
+    prm[tid] = v;
+  }
+  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(p.out, (short)0, (int)kFcmOOB, 0x00020000);
+  // XCD-aware band order (see the ring kernel): row-neighbour bands share fbank rows through one L2
+  const int NG = gridDim.x;
+  const int vb = (NG % 8 == 0) ? (blockIdx.x % 8) * (NG / 8) + blockIdx.x / 8 : blockIdx.x;
+  // fbank tile element e = (k * 8 + wv) * 64 + lane of this wave's DMA k, frame-major as in the fbank (a frame's 23 bins
+  // are contiguous): frame x = e / 23 of the tile is map frame w0 - 3 + x, bin j = e % 23 is map bin 2 ho0 - 4 + j.
+  // Elements outside the map (the stem conv's zero padding) and past the tile are out-of-range offsets: zeros.
+  const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.fbank), (short)0,
+                                                                      (int)kFcmOOB, 0x00020000);
+  auto issue = [&](int band, int tile) {
+    const int tt = band % n_tt, bh = band / n_tt;
+    const int b = bh / n_rb, ho0 = (bh % n_rb) * R;
+    const int bin0 = 2 * ho0 - 4, fr0 = tt * kFbTW - 3;
+    int ln = lane;
+    asm volatile("" : "+v"(ln));   // keeps the per-DMA coordinates from being hoisted out of the band loop into registers
+#pragma unroll
+    for (int k = 0; k < G::kTileDmaPer; ++k) {
+      const int gi = k * 8 + wv;
+      if (gi < G::kTileDma) {   // wave-uniform
+        const int e = gi * 64 + ln;
+        const int x = e / G::kTileH, j = e - x * G::kTileH;
+        const int bin = bin0 + j, frm = fr0 + x;
+        const bool ok = e < G::kTileN && (unsigned)bin < (unsigned)F && (unsigned)frm < (unsigned)W;
+        const uint32_t off = ok ? (uint32_t)((((int64_t)b * W + frm) * F + bin) * 4) : kFcmOOB;
+        dma_lds4_buf(rf, off, (const __attribute__((address_space(3))) void*)(fbt + tile * (G::kTileBytes / 4) + gi * 64));
+      }
+    }
+  };
+  auto barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+  const int fr = col * 16 + l15;   // this lane's intermediate frame (w0 - 1 + fr) / output frame (w0 + fr)
+  int in_dw[3], im_dw[3];
+#pragma unroll
+  for (int dw = 0; dw < 3; ++dw) {
+    in_dw[dw] = ring_pos(half * HR1 * 2, fr + dw, q, kFbPx) * 8;
+    im_dw[dw] = ring_pos(half * HR2, fr + dw, q, kFbIW) * 8;
+  }
+  const int im_wr = ring_pos(half * HR1, fr, q, kFbIW) * 8;
+  // the shortcut's operand: stem pixel (2 ho, wo) = stem image row 2 r + 3, frame fr + 2
+  const int in_res = ring_pos(2 * half * HR2 + 3, fr + 2, q, kFbPx) * 8;
+  const int nb_mine = n_bands > vb ? (n_bands - vb + NG - 1) / NG : 0;
+  if (nb_mine > 0) issue(vb, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the first tile (and the weights)
+  for (int i = 0; i < nb_mine; ++i) {
+    barrier();   // tile i is in LDS (all waves' parts); every wave is done with band i - 1's stem image (the shortcut)
+    if (i + 1 < nb_mine) issue(vb + (i + 1) * NG, (i + 1) & 1);   // lands while this band computes
+    const float* fbs = fbt + (i & 1) * (G::kTileBytes / 4);
+    const int band = vb + i * NG;
+    const int tt = band % n_tt, bh = band / n_tt;
+    const int b = bh / n_rb, ho0 = (bh % n_rb) * R, w0 = tt * kFbTW;
+
+    {   // ---- stem: image pixel (rr, px) = stem map row 2 ho0 - 3 + rr, frame w0 - 2 + px
+      const int n = lane & 31, h = lane >> 5;
+      const bf16x8 stem_a = frg[lane];
+      // two 32-pixel groups per turn: the second group's tap reads and MFMA are in flight while the first is packed
+      // and stored (one group per turn left every step of the chain read -> MFMA -> pack -> store exposed)
+      auto sums = [&](int g, int& rr, int& px) {
+        const int idc = min(g * 32 + n, G::kStemPx - 1);   // the last group's spare lanes re-read a pixel
+        rr = idc / kFbPx, px = idc - rr * kFbPx;
+        return fcm_stem_mfma(stem_a, fbs + px * G::kTileH + rr, 1, G::kTileH, lane);
+      };
+      auto store = [&](int g, int rr, int px, const floatx16& acc) {
+        if (g * 32 + n < G::kStemPx) {
+          const bool ok = (unsigned)(2 * ho0 - 3 + rr) < (unsigned)F && (unsigned)(w0 - 2 + px) < (unsigned)W;
+          uint32_t o[8];
+          fcm_stem_pack(acc, ok, o);
+          *reinterpret_cast<uint4*>(xs + ring_pos(rr, px, 2 * h, kFbPx) * 8) = make_uint4(o[0], o[1], o[2], o[3]);
+          *reinterpret_cast<uint4*>(xs + ring_pos(rr, px, 2 * h + 1, kFbPx) * 8) = make_uint4(o[4], o[5], o[6], o[7]);
+        }
+      };
+      constexpr int NW = kBandThreads / 64;
+      for (int g = wv; g < G::kStemGroups; g += 2 * NW) {
+        int rr0, px0, rr1 = 0, px1 = 0;
+        const floatx16 acc0 = sums(g, rr0, px0);
+        floatx16 acc1 = {};
+        const bool two = g + NW < G::kStemGroups;   // wave-uniform
+        if (two) acc1 = sums(g + NW, rr1, px1);
+        store(g, rr0, px0, acc0);
+        if (two) store(g + NW, rr1, px1, acc1);
+      }
+    }
+    barrier();   // the stem image is complete; every wave is done with band i - 1's intermediate image
+
+    fcm_blk_conv1<2, HR1>(xs, img, prm, wf1, in_dw, im_wr, half, q, ho0, w0, fr, Ho, W);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's part of the next tile (issued two phases ago)
+    barrier();   // the intermediate image is complete
+
+    const bf16x8 wsc[2] = {frg[64 + lane], frg[128 + lane]};
+    fcm_blk_conv2<2, HR2>(xs, img, prm, wf2, wsc, im_dw, in_res, ro, half, q, b, ho0, w0, fr, Ho, W);
+  }
+}
+
+void launch_fcm_stem_block(const FcmStemBlockArgs& a, int Ho, hipStream_t st) {
+  using G = SbGeom;
+  static_assert(G::kLds <= 160 * 1024 && G::kStem % 16 == 0 && G::kImg % 16 == 0, "LDS budget / alignment");
+  const int n_tt = cdiv(a.W, kFbTW);
+  const int64_t bands = (int64_t)a.B * cdiv(Ho, G::R) * n_tt;
+  static bool attr = false;
+  if (!attr) {
+    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fcm_stem_block_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, G::kLds));
+    attr = true;
+  }
+  const int grid = (int)std::min<int64_t>(bands, (int64_t)g_fcm_cu);
+  hipLaunchKernelGGL(fcm_stem_block_kernel, dim3(grid), dim3(kBandThreads), (size_t)G::kLds, st, a, Ho, (int)bands, n_tt);
 }
 
 }  // namespace
@@ -1031,6 +1262,47 @@ void conv_fcm_block(const FcmBlockArgs& a, hipStream_t st) {
                  (double)in_bytes + (double)out_bytes, st);
   if (a.stride == 1) launch_fcm_block<1>(a, Ho, st);
   else launch_fcm_block<2>(a, Ho, st);
+  SD_LAUNCH_CHECK();
+}
+
+bool fcm_stem_block_supported(const FcmStemBlockArgs& a) {
+  if (!(a.fbank && a.out && a.stem_w && a.stem_alpha && a.stem_beta && a.w1 && a.w2 && a.wsc && a.a1 && a.b1 && a.a2 &&
+        a.b2 && a.asc && a.bsc) || a.B < 1 || a.W < 1 || a.F < 1)
+    return false;
+  // Only where layer1.0's two launches run their stem-fused conv1 (fcm_block_pair): below that width the pair's stem is
+  // the fp32 fcm_conv1, whose values differ from the MFMA stem's.  The same predicate on the same arguments.
+  ConvGemmArgs q;
+  q.a_bf16 = true;
+  q.B = a.B; q.H = a.F; q.W = a.W; q.Cin = 32; q.lda = 32;
+  q.Ho = (a.F - 1) / 2 + 1; q.Wo = a.W;
+  q.kh = q.kw = 3; q.sh = 2; q.ph = q.pw = 1;
+  q.N = 32; q.K = 288;
+  q.out_bf16 = true; q.o_sn = 1; q.o_sw = 32;
+  FcmFuse f;
+  f.sc_w = a.wsc; f.sc_alpha = a.asc; f.sc_beta = a.bsc; f.sc_out = a.out;
+  f.fbank = a.fbank; f.fb_F = a.F;
+  f.stem_w = a.stem_w; f.stem_alpha = a.stem_alpha; f.stem_beta = a.stem_beta;
+  const int64_t bands = (int64_t)a.B * cdiv(q.Ho, SbGeom::R) * cdiv(a.W, kFbTW);
+  return fcm_fused_supported(q, f) && bands < (1ll << 31);   // (B * F * W * 64 < 2 GiB: the output offsets fit)
+}
+
+void conv_fcm_stem_block(const FcmStemBlockArgs& a, hipStream_t st) {
+  SD_CHECK(fcm_stem_block_supported(a), kErrInvalid, "fcm stem block: unsupported arguments");
+  const int Ho = (a.F - 1) / 2 + 1;
+  const int64_t in_bytes = (int64_t)a.B * a.W * a.F * 4, out_bytes = (int64_t)a.B * Ho * a.W * 64;
+  const char *xb = reinterpret_cast<const char*>(a.fbank), *ob = static_cast<const char*>(a.out);
+  // neighbouring bands read each other's halo bins after a band has stored its output
+  SD_CHECK(ob + out_bytes <= xb || xb + in_bytes <= ob, kErrInvalid, "fcm stem block: out overlaps the fbank");
+  if (!g_fcm_cu) {
+    int dev = 0;
+    SD_HIP(hipGetDevice(&dev));
+    SD_HIP(hipDeviceGetAttribute(&g_fcm_cu, hipDeviceAttributeMultiprocessorCount, dev));
+  }
+  const double px = (double)a.B * Ho * a.W;
+  ProfScope prof("fcm_stem_block",
+                 2.0 * (double)a.B * a.F * a.W * 32 * 9 + 2.0 * px * 32 * 288 * 2 + 2.0 * px * 32 * 32,
+                 (double)in_bytes + (double)out_bytes, st);
+  launch_fcm_stem_block(a, Ho, st);
   SD_LAUNCH_CHECK();
 }
 

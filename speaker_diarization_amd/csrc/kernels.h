@@ -135,6 +135,21 @@ struct FcmBlockArgs {
 bool fcm_block_supported(const FcmBlockArgs& a);   // false: fp32 maps, C != 32, a map of 2 GiB or more
 bool fcm_block_enabled();                          // false with SDIAR_NO_FCM_BLOCK set (read once): the two launches
 void conv_fcm_block(const FcmBlockArgs& a, hipStream_t st);
+// CAM++ FCM layer1.0 in one launch (fcm_conv.hip, fcm_stem_block_kernel): the stem (head.conv1 1 -> 32, 3x3, pad 1,
+// + BN + ReLU) of the fbank (B, W, F) fp32, computed in LDS, then the strided BasicResBlock with its 1x1 shortcut as
+// in FcmBlockArgs (stride 2); out is bf16 NHWC (B, (F - 1) / 2 + 1, W, 32).  The arithmetic is that of the block's two
+// launches with the stem-fused conv1 (conv_fcm3x3_fused + conv_fcm3x3), value for value, and it is supported exactly
+// where that conv1 is (fcm_fused_supported with the fbank and the shortcut: W >= 113, a stem map under 2 GiB).
+struct FcmStemBlockArgs {
+  const float* fbank = nullptr;
+  int B = 0, W = 0, F = 0;
+  const float *stem_w = nullptr, *stem_alpha = nullptr, *stem_beta = nullptr;   // 32x9 raw, folded BN
+  const void *w1 = nullptr, *w2 = nullptr, *wsc = nullptr;
+  const float *a1 = nullptr, *b1 = nullptr, *a2 = nullptr, *b2 = nullptr, *asc = nullptr, *bsc = nullptr;
+  void* out = nullptr;
+};
+bool fcm_stem_block_supported(const FcmStemBlockArgs& a);
+void conv_fcm_stem_block(const FcmStemBlockArgs& a, hipStream_t st);   // CamTrunk::forward: under fcm_block_enabled()
 // ResNet34 trunk 3x3 convs (res_conv.hip): bf16 NHWC in, pad 1, stride 1 or 2 in BOTH axes, Cin / Cout in
 // {32, 64, 128, 256, 512}, folded BN + optional bf16 residual + ReLU (NaN kept), bf16 out (NHWC as 16-B stores, or any
 // o_s* strides per element).  ResFuse: the block's 1x1 shortcut at the same stride (+ its BN, no ReLU) from the

@@ -1,6 +1,7 @@
-"""Per-launch time of one CAM++ FCM residual block: the fused kernel (sd_op_fcm_block fused = 1) against the
-trunk's two launches (fused = 0) at the C2 / C4 block shapes (GPU box), from the library's per-family event
-timers (so the weight packing and the scratch maps of the test entry point are not in the figures).
+"""Per-launch time of one CAM++ FCM residual block: the fused kernel (sd_op_fcm_block / sd_op_fcm_stem_block fused = 1)
+against the trunk's two launches (fused = 0) at the C2 / C4 block shapes (GPU box), from the library's per-family
+event timers (so the weight packing and the scratch maps of the test entry point are not in the figures).  layer1.0
+is the stem + strided block from the fbank (F 80); its two launches are the stem-fused conv1 and conv2.
     python3 tools/fcm_block_bench.py [B]"""
 import math
 import sys
@@ -31,6 +32,20 @@ def timed(fn, keys, reps=5):
 
 
 for W in (598, 398):
+    g = torch.Generator().manual_seed(W)
+    r = lambda *s: torch.randn(*s, generator=g).to(dev)
+    fb = 2.0 * r(B, W, 80)
+    out = torch.empty(B, 40, W, 32, dtype=torch.bfloat16, device=dev)
+    p = [r(32, 1, 3, 3) / 3, 1 + 0.1 * r(32), 0.1 * r(32), r(32, 32, 3, 3) / math.sqrt(288), 1 + 0.1 * r(32),
+         0.1 * r(32), r(32, 32, 3, 3) / math.sqrt(288), 1 + 0.1 * r(32), 0.1 * r(32), r(32, 32, 1, 1) / math.sqrt(32),
+         1 + 0.1 * r(32), 0.1 * r(32)]
+    args = [_lib.ptr(t) for t in p]
+    run = lambda fused: _lib.call("sd_op_fcm_stem_block", _lib.ptr(fb), B, W, 80, *args, _lib.ptr(out), fused, st)
+    t1 = timed(lambda: run(1), ("fcm_stem_block",))
+    ta, tb = timed(lambda: run(0), ("fcm_stem",)), timed(lambda: run(0), ("fcm_conv3x3_band",))
+    gb = (fb.numel() * 4 + out.numel() * 2) / 1e9
+    print(f"layer1.0 B {B} F 80 W {W} stem + stride 2: fused {t1:7.1f} us ({gb / t1 * 1e3:5.2f} TB/s of in + out)  "
+          f"two launches {ta + tb:7.1f} us ({ta:.1f} + {tb:.1f})  ratio {(ta + tb) / t1:4.2f}", flush=True)
     for name, H, stride in (("layer1.1", 40, 1), ("layer2.0", 40, 2), ("layer2.1", 20, 1)):
         g = torch.Generator().manual_seed(H + stride)
         r = lambda *s: torch.randn(*s, generator=g).to(dev)
