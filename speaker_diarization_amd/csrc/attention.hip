@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -868,16 +869,10 @@ bool launch_long(const AttnArgs& a, bool bf16, hipStream_t st) {
   if (off || !bf16 || !a.io_bf16 || a.chunk || a.mask_dump || HD % 32 || a.T <= 256 ||
       (a.ld_qkv % 8) || (a.D % 8) || (a.ldo % 4) || (a.tok_stride * a.ld_qkv) % 8)
     return false;
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
   dim3 grid(cdiv(a.T, kQB), a.S * a.nh);
   // fewer than 2 workgroups per CU: latency-bound, hoist the fragment reads (measured: T 6000 with 4
   // heads 67 -> 57 us; with 24 sequence-heads the occupancy loss made it 215 -> 244 us)
-  if ((int64_t)grid.x * grid.y < 2LL * n_cu) {
+  if ((int64_t)grid.x * grid.y < 2LL * device_cus()) {
     // (a split of each query block's key pairs over two workgroups measured 60 -> 54 us here, but the split
     // depends on the grid, so sharded runs — EDA chunk shards, bit-identical for any world size — would
     // differ by world size; not kept)
@@ -902,19 +897,8 @@ bool launch_short(const AttnArgs& a, bool bf16, hipStream_t st) {
   const size_t smem = sizeof(uint16_t) * (size_t)TP * (KS + VS);
   // One head per workgroup (measured best at S = 2400, T = 150: more, smaller workgroups
   // overlap their staging); XCD-aware order keeps the heads of a sequence on one L2.
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
   const int hpw = 1;
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_short_kernel<HD, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
+  allow_dynamic_lds<&attn_short_kernel<HD, true>>(160 * 1024);
   const dim3 grid(a.S * ((a.nh + hpw - 1) / hpw));
   hipLaunchKernelGGL((attn_short_kernel<HD, true>), grid, dim3(256), smem, st, a, TP, hpw);
   return true;

@@ -37,6 +37,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -711,14 +712,7 @@ void cam_dense(const void* x, int B, int T, int ld, int cin, int dil, const floa
   const bool split = cdiv(T, 16) > kPartTT;
   SD_CHECK(!split || (records && counters && (reinterpret_cast<uintptr_t>(records) & 15) == 0), kErrInvalid,
            "cam_dense: items of more than 160 frames need the exchange records and counters");
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cam_dense_kernel<false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmemBytes));
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(cam_dense_kernel<true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmemBytes));
-    attr = true;
-  }
+  allow_dynamic_lds<&cam_dense_kernel<false>, &cam_dense_kernel<true>>((int)kSmemBytes);
   const int nseg = cdiv(T, kSeg);
   ProfScope prof("cam_dense",
                  2.0 * B * T * kC * (double)cin + 2.0 * B * T * kC2 * 3 * kC + 2.0 * B * nseg * (kC * kC1 + kC1 * kC2),

@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -198,13 +199,7 @@ __global__ __launch_bounds__(256) void cam_local_fused_kernel(
 // Persistent grid: tasks (item, segment) are dealt to at most kCamWgPerCu workgroups per CU.
 constexpr int kCamWgPerCu = 4;
 dim3 cam_grid(int B, int nseg) {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
-  return dim3((unsigned)std::min(B * nseg, kCamWgPerCu * n_cu));
+  return dim3((unsigned)std::min(B * nseg, kCamWgPerCu * device_cus()));
 }
 
 }  // namespace

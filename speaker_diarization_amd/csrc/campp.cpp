@@ -246,19 +246,25 @@ Tens CamTrunk::forward(const float* fbank, int B, int Tf, hipStream_t st, int b0
   float* cur = fcmA;
   int H = F, W = Tf;
   float* const bufs[3] = {fcmA, fcmB, fcmC};
+  // the one-launch kernels' blocks: 32-wide weights, a shortcut exactly on the strided ones
+  auto w32 = [](const ResBlockL& rb) {
+    return rb.c1.w.N == 32 && rb.c1.w.K == 288 && rb.c2.w.N == 32 && rb.c2.w.K == 288 &&
+           (!rb.has_sc || (rb.sc.w.N == 32 && rb.sc.w.K == 32)) && rb.has_sc == (rb.stride == 2);
+  };
+  auto set_weights = [](auto& a, const ResBlockL& rb) {   // FcmBlockArgs / FcmStemBlockArgs
+    a.w1 = rb.c1.w.w; a.a1 = rb.c1.alpha; a.b1 = rb.c1.beta;
+    a.w2 = rb.c2.w.w; a.a2 = rb.c2.alpha; a.b2 = rb.c2.beta;
+    if (rb.has_sc) { a.wsc = rb.sc.w.w; a.asc = rb.sc.alpha; a.bsc = rb.sc.beta; }
+  };
   for (size_t i = 0; i < fcm_blocks_.size(); ++i) {
     const ResBlockL& rb = fcm_blocks_[i];
     if (bf && i == 0 && fcm_block_enabled() && rb.has_sc && rb.stride == 2) {   // stem + layer1.0 in one launch
       FcmStemBlockArgs a;
       a.fbank = ref; a.B = B; a.W = W; a.F = F;
       a.stem_w = fcm_conv1_.pre_s; a.stem_alpha = fcm_conv1_.alpha; a.stem_beta = fcm_conv1_.beta;
-      a.w1 = rb.c1.w.w; a.a1 = rb.c1.alpha; a.b1 = rb.c1.beta;
-      a.w2 = rb.c2.w.w; a.a2 = rb.c2.alpha; a.b2 = rb.c2.beta;
-      a.wsc = rb.sc.w.w; a.asc = rb.sc.alpha; a.bsc = rb.sc.beta;
+      set_weights(a, rb);
       a.out = fcmA;   // where the pair leaves layer1.0's output
-      const bool w32 = rb.c1.w.N == 32 && rb.c1.w.K == 288 && rb.c2.w.N == 32 && rb.c2.w.K == 288 &&
-                       rb.sc.w.N == 32 && rb.sc.w.K == 32;
-      if (w32 && fcm_stem_block_supported(a)) {   // false below W 113: the pair's fp32 stem serves those
+      if (w32(rb) && fcm_stem_block_supported(a)) {   // false below W 113: the pair's fp32 stem serves those
         conv_fcm_stem_block(a, st);
         cur = fcmA;
         H = (H - 1) / rb.stride + 1;
@@ -268,13 +274,9 @@ Tens CamTrunk::forward(const float* fbank, int B, int Tf, hipStream_t st, int b0
     if (bf && i > 0 && fcm_block_enabled()) {   // the whole block in one launch
       FcmBlockArgs a;
       a.x = cur; a.B = B; a.H = H; a.W = W; a.C = rb.c1.w.Cin; a.stride = rb.stride; a.bf16 = true;
-      a.w1 = rb.c1.w.w; a.a1 = rb.c1.alpha; a.b1 = rb.c1.beta;
-      a.w2 = rb.c2.w.w; a.a2 = rb.c2.alpha; a.b2 = rb.c2.beta;
-      if (rb.has_sc) { a.wsc = rb.sc.w.w; a.asc = rb.sc.alpha; a.bsc = rb.sc.beta; }
+      set_weights(a, rb);
       a.out = bufs[0] != cur ? bufs[0] : bufs[1];   // both 80-row buffers hold any block's output
-      const bool w32 = rb.c1.w.N == 32 && rb.c1.w.K == 288 && rb.c2.w.N == 32 && rb.c2.w.K == 288 &&
-                       (!rb.has_sc || (rb.sc.w.N == 32 && rb.sc.w.K == 32)) && rb.has_sc == (rb.stride == 2);
-      if (w32 && fcm_block_supported(a)) {
+      if (w32(rb) && fcm_block_supported(a)) {
         conv_fcm_block(a, st);
         cur = static_cast<float*>(a.out);
         H = (H - 1) / rb.stride + 1;

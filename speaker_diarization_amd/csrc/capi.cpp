@@ -1273,6 +1273,26 @@ int sd_op_cam_dense(const void* x, int B, int T, int ld, int cin, int dil, const
   });
 }
 
+namespace {
+// an FCM BasicResBlock over packed 32-channel weights for the trunk's unfused launches (a shortcut where wsc is set)
+sd::ResBlockL fcm_res_block(int stride, const void* w1, const float* a1, const float* b1, const void* w2,
+                            const float* a2, const float* b2, const void* wsc, const float* asc, const float* bsc) {
+  auto conv = [](const void* w, int taps, const float* al, const float* be) {
+    sd::ConvL L;
+    L.w.w = w; L.w.N = 32; L.w.Cin = 32; L.w.K = 32 * taps * taps; L.w.kh = taps; L.w.kw = taps;
+    L.alpha = al; L.beta = be;
+    return L;
+  };
+  sd::ResBlockL rb;
+  rb.stride = stride;
+  rb.has_sc = wsc != nullptr;
+  rb.c1 = conv(w1, 3, a1, b1);
+  rb.c2 = conv(w2, 3, a2, b2);
+  if (wsc) rb.sc = conv(wsc, 1, asc, bsc);
+  return rb;
+}
+}  // namespace
+
 int sd_op_fcm_block(const void* x, int B, int H, int W, int stride, const float* w1, const float* a1, const float* b1,
                     const float* w2, const float* a2, const float* b2, const float* wsc, const float* asc,
                     const float* bsc, void* out, int fused, void* stream) {
@@ -1296,18 +1316,7 @@ int sd_op_fcm_block(const void* x, int B, int H, int W, int stride, const float*
     const size_t in_bytes = (size_t)B * H * W * 64;
     Scratch m0(in_bytes, st), m1(in_bytes, st), m2(in_bytes, st);
     SD_HIP(hipMemcpyAsync(m0.p, x, in_bytes, hipMemcpyDeviceToDevice, st));
-    sd::ResBlockL rb;
-    rb.stride = stride;
-    rb.has_sc = wsc != nullptr;
-    auto conv = [](const void* w, int taps, const float* al, const float* be) {
-      sd::ConvL L;
-      L.w.w = w; L.w.N = 32; L.w.Cin = 32; L.w.K = 32 * taps * taps; L.w.kh = taps; L.w.kw = taps;
-      L.alpha = al; L.beta = be;
-      return L;
-    };
-    rb.c1 = conv(p1.p, 3, a1, b1);
-    rb.c2 = conv(p2.p, 3, a2, b2);
-    if (wsc) rb.sc = conv(ps.p, 1, asc, bsc);
+    const sd::ResBlockL rb = fcm_res_block(stride, p1.p, a1, b1, p2.p, a2, b2, wsc ? ps.p : nullptr, asc, bsc);
     float* const bufs[3] = {static_cast<float*>(m0.p), static_cast<float*>(m1.p), static_cast<float*>(m2.p)};
     int h = H, w = W;
     const float* r = sd::fcm_block_pair(rb, bufs, bufs[0], true, B, h, w, sd::FcmFuse{}, st);
@@ -1340,18 +1349,7 @@ int sd_op_fcm_stem_block(const float* fbank, int B, int W, int F, const float* s
     // the trunk's two launches (below W 113: its fp32 stem and three) on three scratch maps
     const size_t map_bytes = (size_t)B * F * W * 64;
     Scratch m0(map_bytes, st), m1(map_bytes, st), m2(map_bytes, st);
-    sd::ResBlockL rb;
-    rb.stride = 2;
-    rb.has_sc = true;
-    auto conv = [](const void* w, int taps, const float* al, const float* be) {
-      sd::ConvL L;
-      L.w.w = w; L.w.N = 32; L.w.Cin = 32; L.w.K = 32 * taps * taps; L.w.kh = taps; L.w.kw = taps;
-      L.alpha = al; L.beta = be;
-      return L;
-    };
-    rb.c1 = conv(p1.p, 3, a1, b1);
-    rb.c2 = conv(p2.p, 3, a2, b2);
-    rb.sc = conv(ps.p, 1, asc, bsc);
+    const sd::ResBlockL rb = fcm_res_block(2, p1.p, a1, b1, p2.p, a2, b2, ps.p, asc, bsc);
     sd::FcmFuse stem;
     stem.fbank = fbank; stem.fb_F = F;
     stem.stem_w = stem_w; stem.stem_alpha = stem_alpha; stem.stem_beta = stem_beta;

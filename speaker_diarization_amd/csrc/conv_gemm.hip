@@ -19,10 +19,10 @@
 //                  out[b*o_sb + h*o_sh + w*o_sw + n*o_sn] = v
 //
 // Tiles: BM x BN per 256-thread workgroup (2x2 waves), BK = 32, register-staged
-// global->LDS double buffer (one barrier per k-step).  bf16 mode converts the
-// fp32 activations to bf16 while staging and runs v_mfma_f32_16x16x32_bf16;
+// global->LDS double buffer (one barrier per k-step).  The kernels of this file
+// take fp32 tensors (bf16 requests leave conv_gemm() through conv_gemm_bf16):
 // fp32 mode runs the exact-f32 v_mfma_f32_16x16x4_f32; bf16x3 mode (round 6, the
-// fp32-equivalent fast path: conv_gemm_x3_kernel) keeps fp32 tensors and splits every
+// fp32-equivalent fast path: conv_gemm_x3_kernel) splits every
 // staged element into bf16 hi + lo: acc += lo·hi + hi·lo + hi·hi on
 // v_mfma_f32_16x16x32_bf16 (the lo·lo term and the lo part's own rounding leave
 // ~2^-16 relative error per product; 3 MFMAs of 16 cycles per 32-k step against
@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -38,7 +39,6 @@ namespace sd {
 namespace {
 
 constexpr int kBK = 32;
-constexpr int kLdsBf = kBK + 8;   // bf16 row stride (80 B: 16-B aligned, conflict-light)
 constexpr int kLdsF = kBK + 2;    // fp32 row stride (34 words: conflict-free 16x16x4 reads)
 
 thread_local bool t_gemm_x3 = false;
@@ -140,19 +140,20 @@ __device__ __forceinline__ void staged_epilogue_f32(const ConvGemmArgs& p, const
   }
 }
 
-// MODE 0: exact f32 MFMA, 1: bf16 (fp32 activations converted on staging); bf16x3: conv_gemm_x3_kernel
+// Exact f32 MFMA (bf16x3: conv_gemm_x3_kernel).  MODE is 0, the only mode left: it stays a template argument so
+// that the kernels keep the symbol names the recorded profiles and tools/device_code_diff.py match on.
 template <int BM, int BN, int MODE>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p) {
-  constexpr bool BF16 = MODE == 1;
+  static_assert(MODE == 0, "conv_gemm_kernel: exact-f32 mode only");
   constexpr int TM = BM / 2, TN = BN / 2;
   constexpr int MT = TM / 16, NT = TN / 16;
   constexpr int APASS = BM / 32;
-  using LdsT = typename std::conditional<BF16, uint16_t, float>::type;
-  constexpr int LDS_STRIDE = BF16 ? kLdsBf : kLdsF;
-  // one array (As then Bs) so the exact-f32 epilogue can stage its tile over both
-  __shared__ __attribute__((aligned(16))) LdsT smem[2 * (BM + BN) * LDS_STRIDE];
-  LdsT (*const As)[BM * LDS_STRIDE] = reinterpret_cast<LdsT (*)[BM * LDS_STRIDE]>(smem);
-  LdsT (*const Bs)[BN * LDS_STRIDE] = reinterpret_cast<LdsT (*)[BN * LDS_STRIDE]>(smem + 2 * BM * LDS_STRIDE);
+  constexpr int LDS_STRIDE = kLdsF;
+  // one array (As then Bs) so the epilogue can stage its tile over both
+  __shared__ __attribute__((aligned(16))) float smem[2 * (BM + BN) * LDS_STRIDE];
+  static_assert((int)sizeof(smem) >= BM * (BN + 4) * 4, "the staged epilogue's tile fits the operand buffers");
+  float (*const As)[BM * LDS_STRIDE] = reinterpret_cast<float (*)[BM * LDS_STRIDE]>(smem);
+  float (*const Bs)[BN * LDS_STRIDE] = reinterpret_cast<float (*)[BN * LDS_STRIDE]>(smem + 2 * BM * LDS_STRIDE);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p) {
   float4 areg[APASS], s4, h4;
   uint32_t avalid = 0;
   // B staging registers.
-  constexpr int BCHUNK = BF16 ? (BN * 4) : (BN * 8);   // 16-B chunks per tile
+  constexpr int BCHUNK = BN * 8;   // 16-B chunks per tile
   constexpr int BPASS = (BCHUNK + 255) / 256;
   uint4 breg[BPASS];
 
@@ -226,17 +227,10 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p) {
       int ch = tid + i * 256;
       uint4 v = make_uint4(0, 0, 0, 0);
       if (ch < BCHUNK) {
-        if (BF16) {
-          int n = ch >> 2, kc = (ch & 3) * 8;
-          if (n0 + n < p.N && k0 + kc < p.K)
-            v = *reinterpret_cast<const uint4*>(
-                reinterpret_cast<const uint16_t*>(p.Wt) + (int64_t)(n0 + n) * p.K + k0 + kc);
-        } else {
-          int n = ch >> 3, kc = (ch & 7) * 4;
-          if (n0 + n < p.N && k0 + kc < p.K)
-            v = *reinterpret_cast<const uint4*>(
-                reinterpret_cast<const float*>(p.Wt) + (int64_t)(n0 + n) * p.K + k0 + kc);
-        }
+        int n = ch >> 3, kc = (ch & 7) * 4;
+        if (n0 + n < p.N && k0 + kc < p.K)
+          v = *reinterpret_cast<const uint4*>(
+              reinterpret_cast<const float*>(p.Wt) + (int64_t)(n0 + n) * p.K + k0 + kc);
       }
       breg[i] = v;
     }
@@ -252,30 +246,18 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p) {
         areg[i].z = fmaxf(areg[i].z * s4.z + h4.z, 0.f);
         areg[i].w = fmaxf(areg[i].w * s4.w + h4.w, 0.f);
       }
-      if (BF16) {
-        uint2 pk;
-        pk.x = (uint32_t)f2bf_bits(areg[i].x) | ((uint32_t)f2bf_bits(areg[i].y) << 16);
-        pk.y = (uint32_t)f2bf_bits(areg[i].z) | ((uint32_t)f2bf_bits(areg[i].w) << 16);
-        *reinterpret_cast<uint2*>(&As[buf][row * LDS_STRIDE + kq]) = pk;
-      } else {
-        float* d = reinterpret_cast<float*>(&As[buf][row * LDS_STRIDE + kq]);
-        *reinterpret_cast<float2*>(d) = make_float2(areg[i].x, areg[i].y);
-        *reinterpret_cast<float2*>(d + 2) = make_float2(areg[i].z, areg[i].w);
-      }
+      float* d = &As[buf][row * LDS_STRIDE + kq];
+      *reinterpret_cast<float2*>(d) = make_float2(areg[i].x, areg[i].y);
+      *reinterpret_cast<float2*>(d + 2) = make_float2(areg[i].z, areg[i].w);
     }
 #pragma unroll
     for (int i = 0; i < BPASS; ++i) {
       int ch = tid + i * 256;
       if (ch < BCHUNK) {
-        if (BF16) {
-          int n = ch >> 2, kc = (ch & 3) * 8;
-          *reinterpret_cast<uint4*>(&Bs[buf][n * LDS_STRIDE + kc]) = breg[i];
-        } else {
-          int n = ch >> 3, kc = (ch & 7) * 4;
-          float* d = reinterpret_cast<float*>(&Bs[buf][n * LDS_STRIDE + kc]);
-          *reinterpret_cast<uint2*>(d) = make_uint2(breg[i].x, breg[i].y);
-          *reinterpret_cast<uint2*>(d + 2) = make_uint2(breg[i].z, breg[i].w);
-        }
+        int n = ch >> 3, kc = (ch & 7) * 4;
+        float* d = &Bs[buf][n * LDS_STRIDE + kc];
+        *reinterpret_cast<uint2*>(d) = make_uint2(breg[i].x, breg[i].y);
+        *reinterpret_cast<uint2*>(d + 2) = make_uint2(breg[i].z, breg[i].w);
       }
     }
   };
@@ -295,75 +277,28 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmArgs p) {
   for (int kt = 0; kt < KT; ++kt) {
     const int buf = kt & 1;
     if (kt + 1 < KT) load_tile(kt + 1);
-    if (BF16) {
-      bf16x8 af[MT], bfr[NT];
+    const float* Af = As[buf];
+    const float* Bf = Bs[buf];
+#pragma unroll
+    for (int kk = 0; kk < kBK / 4; ++kk) {
+      float af[MT], bfr[NT];
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
-        af[mt] = *reinterpret_cast<const bf16x8*>(
-            &As[buf][(wm * TM + mt * 16 + lrow) * LDS_STRIDE + lk * 8]);
+        af[mt] = Af[(wm * TM + mt * 16 + lrow) * LDS_STRIDE + kk * 4 + lk];
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt)
-        bfr[nt] = *reinterpret_cast<const bf16x8*>(
-            &Bs[buf][(wn * TN + nt * 16 + lrow) * LDS_STRIDE + lk * 8]);
+        bfr[nt] = Bf[(wn * TN + nt * 16 + lrow) * LDS_STRIDE + kk * 4 + lk];
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt], bfr[nt], acc[mt][nt], 0, 0, 0);
-    } else {
-      const float* Af = reinterpret_cast<const float*>(As[buf]);
-      const float* Bf = reinterpret_cast<const float*>(Bs[buf]);
-#pragma unroll
-      for (int kk = 0; kk < kBK / 4; ++kk) {
-        float af[MT], bfr[NT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-          af[mt] = Af[(wm * TM + mt * 16 + lrow) * LDS_STRIDE + kk * 4 + lk];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-          bfr[nt] = Bf[(wn * TN + nt * 16 + lrow) * LDS_STRIDE + kk * 4 + lk];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt)
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[mt], bfr[nt], acc[mt][nt], 0, 0, 0);
-      }
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[mt], bfr[nt], acc[mt][nt], 0, 0, 0);
     }
     if (kt + 1 < KT) store_tile(buf ^ 1);
     __syncthreads();
   }
 
-  // Epilogue: staged through LDS in exact-f32 mode (the tile fits the fp32 operand buffers)
-  if constexpr (!BF16 && (int)sizeof(smem) >= BM * (BN + 4) * 4) {
-    staged_epilogue_f32<BM, BN, MT, NT>(p, acc, reinterpret_cast<float*>(smem), m0, n0, M);
-    return;
-  }
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = m0 + wm * TM + mt * 16 + lk * 4 + r;
-      if (m >= M) continue;
-      const int wo = m % p.Wo;
-      const int t = m / p.Wo;
-      const int ho = t % p.Ho;
-      const int b = t / p.Ho;
-      const int64_t obase = (int64_t)b * p.o_sb + (int64_t)ho * p.o_sh + (int64_t)wo * p.o_sw;
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const int n = n0 + wn * TN + nt * 16 + lrow;
-        if (n >= p.N) continue;
-        float v = acc[mt][nt][r];
-        if (p.alpha) v *= p.alpha[n];
-        if (p.beta) v += p.beta[n];
-        if (p.res) v += reinterpret_cast<const float*>(p.res)[(int64_t)m * p.res_ld + n];
-        v = apply_act(v, p.act);
-        if (p.post_scale) v = v * p.post_scale[n] + p.post_shift[n];
-        if (p.gate) v *= p.gate[((int64_t)b * p.gate_nseg + wo / p.gate_seg) * p.N + n];
-        reinterpret_cast<float*>(p.out)[obase + (int64_t)n * p.o_sn] = v;
-      }
-    }
-  }
+  staged_epilogue_f32<BM, BN, MT, NT>(p, acc, smem, m0, n0, M);   // staged over the operand buffers
 }
 
 // 4 fp32 -> bf16 hi (round to nearest even) and lo = bf16(v - hi) (v - hi is exact in fp32), 2 words each
@@ -600,23 +535,16 @@ void launch_x3(const ConvGemmArgs& p, dim3 grid, hipStream_t st) {
   constexpr int kRing = 2 * (2 * BM + 2 * BN) * kBK * (int)sizeof(uint16_t);   // 2 buffers x (hi+lo of A, B)
   constexpr int kEpi = BM * (BN + 4) * (int)sizeof(float);                      // the staged epilogue tile
   constexpr int kBytes = kRing > kEpi ? kRing : kEpi;
-  static bool attr = [] {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_x3_kernel<BM, BN>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kBytes));
-    return true;
-  }();
-  (void)attr;
+  allow_dynamic_lds<&conv_gemm_x3_kernel<BM, BN>>(kBytes);
   hipLaunchKernelGGL((conv_gemm_x3_kernel<BM, BN>), grid, dim3(256), kBytes, st, p);
 }
 
 template <int BM, int BN>
-void launch_tile(const ConvGemmArgs& p, bool bf16, hipStream_t st) {
+void launch_tile(const ConvGemmArgs& p, hipStream_t st) {
   SD_CHECK(!p.a_bf16 && !p.out_bf16 && !p.res_bf16, kErrInvalid, "fp32 conv_gemm takes fp32 tensors");
   const int M = p.B * p.Ho * p.Wo;
   dim3 grid(cdiv(p.N, BN) * cdiv(M, BM));
-  if (bf16)
-    hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, 1>), grid, dim3(256), 0, st, p);
-  else if (t_gemm_x3)
+  if (t_gemm_x3)
     launch_x3<BM, BN>(p, grid, st);
   else
     hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, 0>), grid, dim3(256), 0, st, p);
@@ -656,10 +584,9 @@ void conv_gemm(const ConvGemmArgs& p, bool bf16, hipStream_t st) {
   const int M = p.B * p.Ho * p.Wo;
   // Algorithmic work: 2*M*N*K flops; bytes = input activation once + weights + output (+res).
   const double flops = 2.0 * M * p.N * (double)p.K;
-  const double bytes = 4.0 * p.B * p.H * p.W * p.Cin + (bf16 ? 2.0 : 4.0) * p.N * p.K +
-                       4.0 * M * p.N * (p.res ? 2.0 : 1.0);
+  const double bytes = 4.0 * p.B * p.H * p.W * p.Cin + 4.0 * p.N * p.K + 4.0 * M * p.N * (p.res ? 2.0 : 1.0);
   static const bool detail = getenv("SDIAR_PROF_DETAIL") != nullptr;
-  std::string key = bf16 ? "conv_gemm_bf16" : t_gemm_x3 ? "conv_gemm_bf16x3" : "conv_gemm_f32";
+  std::string key = t_gemm_x3 ? "conv_gemm_bf16x3" : "conv_gemm_f32";
   if (detail && prof_enabled())
     key += " M=" + std::to_string(M) + " N=" + std::to_string(p.N) + " K=" + std::to_string(p.K) +
            " taps=" + std::to_string(p.kh * p.kw) + (p.pre_scale ? " pre" : "");
@@ -668,11 +595,11 @@ void conv_gemm(const ConvGemmArgs& p, bool bf16, hipStream_t st) {
   const int tiles128 = cdiv(M, 128) * cdiv(p.N, bn);
   const bool big = tiles128 >= 512;
   if (bn == 128) {
-    if (big) launch_tile<128, 128>(p, bf16, st); else launch_tile<64, 128>(p, bf16, st);
+    if (big) launch_tile<128, 128>(p, st); else launch_tile<64, 128>(p, st);
   } else if (bn == 64) {
-    if (big) launch_tile<128, 64>(p, bf16, st); else launch_tile<64, 64>(p, bf16, st);
+    if (big) launch_tile<128, 64>(p, st); else launch_tile<64, 64>(p, st);
   } else {
-    if (big) launch_tile<128, 32>(p, bf16, st); else launch_tile<64, 32>(p, bf16, st);
+    if (big) launch_tile<128, 32>(p, st); else launch_tile<64, 32>(p, st);
   }
   SD_LAUNCH_CHECK();
 }

@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -341,13 +342,7 @@ void res2_chain_fused(const void* x, int B, int T, int d, const Res2ChainW& W, v
   SD_CHECK(x && out && B >= 1 && B <= 65535 && T >= 1 && res2_chain_fused_supported(d), kErrInvalid,
            "res2_chain_fused: 1 <= B <= 65535, T >= 1, dilation 1..4");
   const int bytes = 2 * (chain_rows(d) + 2 * kChainPad) * kChainLd * (int)sizeof(uint16_t);
-  static bool attr = [] {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&res2_chain_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               2 * (chain_rows(kChainPad) + 2 * kChainPad) * kChainLd * (int)sizeof(uint16_t)));
-    return true;
-  }();
-  (void)attr;
+  allow_dynamic_lds<&res2_chain_kernel>(2 * (chain_rows(kChainPad) + 2 * kChainPad) * kChainLd * (int)sizeof(uint16_t));
   const double flops = 2.0 * B * T * 128.0 * 384.0 * Res2ChainW::kStages;
   ProfScope prof("res2_chain_fused", flops, 2.0 * B * T * 1024 * 2.0 + 7.0 * 128 * 384 * 2, st);
   hipLaunchKernelGGL(res2_chain_kernel, dim3(cdiv(T, kChainTT), B), dim3(256), bytes, st,

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -435,12 +436,7 @@ void attractor_scores(const float* emb, int S, int T, int E, const float* att, i
                       const float* lb, float* probs, float* act, hipStream_t st) {
   const size_t smem = sizeof(float) * (size_t)(n_att + kScoreRows) * (E + 1);
   SD_CHECK(smem <= 160 * 1024, kErrInvalid, "attractor_scores: too many attractors for LDS");
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attractor_scores_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
+  allow_dynamic_lds<&attractor_scores_kernel>(160 * 1024);
   ProfScope prof("attractor_scores", 2.0 * S * T * E * (n_att - 1), 4.0 * S * T * (E + n_att), st);
   hipLaunchKernelGGL(attractor_scores_kernel, dim3(cdiv(T, kScoreRows), S), dim3(256), smem, st, emb, T, E,
                      att, n_att, lw, lb, probs, act);

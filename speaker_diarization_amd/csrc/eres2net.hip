@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -262,12 +263,7 @@ void launch_aff(const AffGateArgs& a, hipStream_t st) {
   const int SW = (2 * RW) | 1;
   const size_t smem = ((size_t)kAffPix * SW + (size_t)kAffPix * (4 * IPT + 1)) * 4;
   SD_CHECK(smem <= 160 * 1024, kErrInvalid, "aff_gate: LDS budget");
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(aff_gate_kernel<BF, IPT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
+  allow_dynamic_lds<&aff_gate_kernel<BF, IPT>>(160 * 1024);
   const int64_t blocks = (a.P + kAffPix - 1) / kAffPix;
   SD_CHECK(blocks < (1ll << 31), kErrInvalid, "aff_gate: too many pixels");
   hipLaunchKernelGGL((aff_gate_kernel<BF, IPT>), dim3((unsigned)blocks), dim3(kThreads), smem, st, a, SW);

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -234,11 +235,9 @@ void fbank_kaldi(const float* wav, int64_t n_samples, float in_scale, int n_fram
   // as many workgroups as are resident at once (each builds its tables once and walks frame groups)
   static int slots = 0;
   if (!slots) {
-    int dev = 0, cus = 0, per_cu = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    int per_cu = 0;
     SD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fbank_kernel, 512, 0));
-    slots = std::max(1, cus * std::max(1, per_cu));
+    slots = std::max(1, device_cus() * std::max(1, per_cu));
   }
   const int groups = cdiv(n_frames, kFramesPerBlock);
   const dim3 grid(std::min(groups, slots));

@@ -13,6 +13,7 @@
 // per-element for the transposed FCM output layout).
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -525,8 +526,6 @@ __global__ __launch_bounds__(kBandThreads) void fcm_conv3x3_band_kernel(ConvGemm
   }
 }
 
-int g_fcm_cu = 0;
-
 // ---------------------------------------------------------------------------------
 // Ring variant of the stride-1 band conv (the production path for FCM's stride-1 3x3 convs, bf16 NHWC
 // in and out).  The band kernel above keeps ONE band's rows in flight (register prefetch, drained by the
@@ -694,13 +693,8 @@ void launch_ring(const ConvGemmArgs& p, hipStream_t st) {
   SD_CHECK(bands < (1ll << 31), kErrInvalid, "fcm conv: too many bands");
   constexpr size_t smem = (size_t)kRNSlot * ring_slot_bytes<RES>();
   static_assert(smem <= 160 * 1024, "LDS budget");
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fcm_conv3x3_ring_kernel<RES, RELU>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    attr = true;
-  }
-  const int grid = (int)std::min<int64_t>(bands, (int64_t)g_fcm_cu);
+  allow_dynamic_lds<&fcm_conv3x3_ring_kernel<RES, RELU>>((int)smem);
+  const int grid = (int)std::min<int64_t>(bands, (int64_t)device_cus());
   hipLaunchKernelGGL((fcm_conv3x3_ring_kernel<RES, RELU>), dim3(grid), dim3(kBandThreads), smem, st, p, (int)bands, n_tt);
 }
 
@@ -738,13 +732,8 @@ void launch_band(const ConvGemmArgs& p, hipStream_t st, const FcmFuse& f = FcmFu
   const int nb = band_blocks(p.W);
   const int64_t bands = (int64_t)p.B * cdiv(p.Ho, R) * cdiv(p.W, nb * 16);
   SD_CHECK(bands < (1ll << 31), kErrInvalid, "fcm conv: too many bands");
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fcm_conv3x3_band_kernel<R, SH, STEM, SC, false, SMF>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
-  const int grid = (int)std::min<int64_t>(bands, (int64_t)g_fcm_cu);
+  allow_dynamic_lds<&fcm_conv3x3_band_kernel<R, SH, STEM, SC, false, SMF>>(160 * 1024);
+  const int grid = (int)std::min<int64_t>(bands, (int64_t)device_cus());
   const size_t smem = band_lds<R, SH, STEM>(nb);
   hipLaunchKernelGGL((fcm_conv3x3_band_kernel<R, SH, STEM, SC, false, SMF>), dim3(grid), dim3(kBandThreads), smem, st, p, f,
                      (int)bands, nb);
@@ -1038,13 +1027,8 @@ void launch_fcm_block(const FcmBlockArgs& a, int Ho, hipStream_t st) {
   static_assert(G::kLds <= 160 * 1024, "LDS budget");
   const int n_tt = cdiv(a.W, kFbTW);
   const int64_t bands = (int64_t)a.B * cdiv(Ho, G::R) * n_tt;
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fcm_block_kernel<SH>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G::kLds));
-    attr = true;
-  }
-  const int grid = (int)std::min<int64_t>(bands, (int64_t)g_fcm_cu);
+  allow_dynamic_lds<&fcm_block_kernel<SH>>(G::kLds);
+  const int grid = (int)std::min<int64_t>(bands, (int64_t)device_cus());
   hipLaunchKernelGGL((fcm_block_kernel<SH>), dim3(grid), dim3(kBandThreads), (size_t)G::kLds, st, a, Ho, (int)bands, n_tt);
 }
 
@@ -1219,13 +1203,8 @@ void launch_fcm_stem_block(const FcmStemBlockArgs& a, int Ho, hipStream_t st) {
   static_assert(G::kLds <= 160 * 1024 && G::kStem % 16 == 0 && G::kImg % 16 == 0, "LDS budget / alignment");
   const int n_tt = cdiv(a.W, kFbTW);
   const int64_t bands = (int64_t)a.B * cdiv(Ho, G::R) * n_tt;
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fcm_stem_block_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, G::kLds));
-    attr = true;
-  }
-  const int grid = (int)std::min<int64_t>(bands, (int64_t)g_fcm_cu);
+  allow_dynamic_lds<&fcm_stem_block_kernel>(G::kLds);
+  const int grid = (int)std::min<int64_t>(bands, (int64_t)device_cus());
   hipLaunchKernelGGL(fcm_stem_block_kernel, dim3(grid), dim3(kBandThreads), (size_t)G::kLds, st, a, Ho, (int)bands, n_tt);
 }
 
@@ -1252,11 +1231,6 @@ void conv_fcm_block(const FcmBlockArgs& a, hipStream_t st) {
   const char *xb = static_cast<const char*>(a.x), *ob = static_cast<const char*>(a.out);
   // neighbouring bands read each other's halo rows after a band has stored its output
   SD_CHECK(ob + out_bytes <= xb || xb + in_bytes <= ob, kErrInvalid, "fcm block: out overlaps the input");
-  if (!g_fcm_cu) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&g_fcm_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
   const double px = (double)a.B * Ho * a.W;
   ProfScope prof("fcm_block", 2.0 * px * 32 * 288 * 2 + (a.wsc ? 2.0 * px * 32 * 32 : 0.0),
                  (double)in_bytes + (double)out_bytes, st);
@@ -1293,11 +1267,6 @@ void conv_fcm_stem_block(const FcmStemBlockArgs& a, hipStream_t st) {
   const char *xb = reinterpret_cast<const char*>(a.fbank), *ob = static_cast<const char*>(a.out);
   // neighbouring bands read each other's halo bins after a band has stored its output
   SD_CHECK(ob + out_bytes <= xb || xb + in_bytes <= ob, kErrInvalid, "fcm stem block: out overlaps the fbank");
-  if (!g_fcm_cu) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&g_fcm_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
   const double px = (double)a.B * Ho * a.W;
   ProfScope prof("fcm_stem_block",
                  2.0 * (double)a.B * a.F * a.W * 32 * 9 + 2.0 * px * 32 * 288 * 2 + 2.0 * px * 32 * 32,
@@ -1321,13 +1290,8 @@ void launch_tout(const ConvGemmArgs& p, hipStream_t st) {
   const size_t smem = (size_t)NR * (kToutBlk * 16 + 2) * kPS * 2 + (size_t)kToutBlk * 16 * kToutRow * 2;
   static_assert((size_t)NR * (kToutBlk * 16 + 2) * kPS * 2 + (size_t)kToutBlk * 16 * kToutRow * 2 <= 160 * 1024,
                 "LDS budget");
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fcm_conv3x3_band_kernel<R, 2, false, false, true, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    attr = true;
-  }
-  const int grid = (int)std::min<int64_t>(bands, (int64_t)g_fcm_cu);
+  allow_dynamic_lds<&fcm_conv3x3_band_kernel<R, 2, false, false, true, true>>((int)smem);
+  const int grid = (int)std::min<int64_t>(bands, (int64_t)device_cus());
   hipLaunchKernelGGL((fcm_conv3x3_band_kernel<R, 2, false, false, true, true>), dim3(grid), dim3(kBandThreads), smem, st,
                      p, FcmFuse{}, (int)bands, kToutBlk);
 }
@@ -1340,11 +1304,6 @@ bool fcm_conv_supported(const ConvGemmArgs& p) {
 }
 
 void conv_fcm3x3(const ConvGemmArgs& p, hipStream_t st) {
-  if (!g_fcm_cu) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&g_fcm_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
   if (ring_ok(p)) {
     const bool relu = p.act == kActRelu;
     if (p.res) relu ? launch_ring<true, true>(p, st) : launch_ring<true, false>(p, st);
@@ -1370,7 +1329,7 @@ void conv_fcm3x3(const ConvGemmArgs& p, hipStream_t st) {
   const int n_wt = cdiv(p.Wo, kPx);
   const int64_t tiles = (int64_t)p.B * p.Ho * n_wt;
   SD_CHECK(tiles < (1ll << 31), kErrInvalid, "fcm conv: too many tiles");
-  const int grid = (int)std::min<int64_t>(tiles, (int64_t)g_fcm_cu * 4);
+  const int grid = (int)std::min<int64_t>(tiles, (int64_t)device_cus() * 4);
   hipLaunchKernelGGL(fcm_conv3x3_kernel, dim3(grid), dim3(256), 0, st, p, (int)tiles);
   SD_LAUNCH_CHECK();
 }
@@ -1390,11 +1349,6 @@ bool fcm_fused_supported(const ConvGemmArgs& p, const FcmFuse& f) {
 
 void conv_fcm3x3_fused(const ConvGemmArgs& p, const FcmFuse& f, hipStream_t st) {
   SD_CHECK(fcm_fused_supported(p, f), kErrInvalid, "fcm fused conv: unsupported arguments");
-  if (!g_fcm_cu) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&g_fcm_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
   const double px = (double)p.B * p.Ho * p.Wo;
   const double in_px = f.fbank ? 0.0 : (double)p.B * p.H * p.W;
   double flops = 2.0 * px * 32 * 288 + (f.sc_w ? 2.0 * px * 32 * 32 : 0.0);

@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -272,20 +273,13 @@ __global__ __launch_bounds__(512) void gemm_areg_kernel(ConvGemmArgs p) {
   }
 }
 
-int g_cu = 0;
-
 template <int KT32, int ACT>
 void launch_areg(const ConvGemmArgs& p, hipStream_t st) {
   const int M = p.B * p.Ho * p.Wo;
   const int tiles = cdiv(M, RB);
-  const int grid = std::min(tiles, g_cu);
+  const int grid = std::min(tiles, device_cus());
   const size_t smem = sizeof(uint16_t) * (size_t)NSLOT * NB * KT32 * 32 + 2 * kMaxN * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_areg_kernel<KT32, ACT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
+  allow_dynamic_lds<&gemm_areg_kernel<KT32, ACT>>(160 * 1024);
   hipLaunchKernelGGL((gemm_areg_kernel<KT32, ACT>), dim3(grid), dim3(512), smem, st, p);
 }
 
@@ -316,11 +310,6 @@ bool gemm_areg_supported(const ConvGemmArgs& p) {
 }
 
 void conv_gemm_areg(const ConvGemmArgs& p, hipStream_t st) {
-  if (!g_cu) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&g_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
   if (p.glu) {
     launch_act<kGlu>(p, st);
   } else {

@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -449,13 +450,7 @@ int gemm_splitk_count(const ConvGemmArgs& p) {
     return 1;
   // enough 256x128 tiles for one per CU: the ring GEMM (3-stage DMA ring) beats the split (FS-EEND decoder
   // FFN-down, M 36000: 163 vs 243 us for 2 launches; at M 6000 the split wins, 96 vs 141 us for 4)
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
-  if (gemm_ring_supported(p) && (int64_t)cdiv(M, 256) * cdiv(p.N, 128) >= n_cu) return 1;
+  if (gemm_ring_supported(p) && (int64_t)cdiv(M, 256) * cdiv(p.N, 128) >= device_cus()) return 1;
   const int bn = p.N >= 128 ? 128 : (p.N >= 64 ? 64 : 32);
   const int64_t tiles = (int64_t)cdiv(M, 128) * cdiv(p.N, bn);
   const int64_t tiles_launched = tiles >= 512 ? tiles : (int64_t)cdiv(M, 64) * cdiv(p.N, bn);

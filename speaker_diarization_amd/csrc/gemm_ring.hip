@@ -18,6 +18,7 @@
 //   s/h    [2][K] f32                      8 KiB at K = 1024
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -466,20 +467,10 @@ __global__ __launch_bounds__(kRingThreads) void gemm_ring_persist_kernel(ConvGem
 
 template <bool PRE, int ACT>
 void launch_ring_persist(const ConvGemmArgs& p, hipStream_t st) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  }
+  const int cus = device_cus();
   const int M = p.B * p.Ho * p.Wo;
   const size_t smem = sizeof(uint16_t) * RST * STAGE_ELEMS + (PRE ? 2 * kRingMaxK * sizeof(float) : 0);
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring_persist_kernel<PRE, ACT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
+  allow_dynamic_lds<&gemm_ring_persist_kernel<PRE, ACT>>(160 * 1024);
   const int tiles = cdiv(M, RBM);
   hipLaunchKernelGGL((gemm_ring_persist_kernel<PRE, ACT>), dim3(tiles < cus ? tiles : cus), dim3(kRingThreads),
                      smem, st, p);
@@ -493,12 +484,7 @@ void launch_ring(const ConvGemmArgs& p, hipStream_t st) {
   }
   const int M = p.B * p.Ho * p.Wo;
   const size_t smem = sizeof(uint16_t) * RST * STAGE_ELEMS + (PRE ? 2 * kRingMaxK * sizeof(float) : 0);
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ring_kernel<PRE, ACT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
+  allow_dynamic_lds<&gemm_ring_kernel<PRE, ACT>>(160 * 1024);
   hipLaunchKernelGGL((gemm_ring_kernel<PRE, ACT>), dim3(cdiv(M, RBM) * cdiv(p.N, RBN)), dim3(kRingThreads), smem,
                      st, p);
 }

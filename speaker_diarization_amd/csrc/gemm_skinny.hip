@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -285,14 +286,8 @@ void launch_skinny(const ConvGemmArgs& p, int M, int rs, bool wbf, hipStream_t s
   const int span = (M - 1) * rs + p.K;
   const size_t lds = (size_t)span * sizeof(float);
   const dim3 grid(cdiv(p.N, 4 * NC));
-  static bool attr_set[2] = {false, false};   // once per instantiation, before any graph capture
-  if (!attr_set[wbf]) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_skinny_kernel<MMAX, NC, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kSkinnyLdsFloats * 4));
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_skinny_kernel<MMAX, NC, false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kSkinnyLdsFloats * 4));
-    attr_set[wbf] = true;
-  }
+  // both weight forms on the first launch of either, before any graph capture
+  allow_dynamic_lds<&gemm_skinny_kernel<MMAX, NC, true>, &gemm_skinny_kernel<MMAX, NC, false>>(kSkinnyLdsFloats * 4);
   if (wbf) {
     hipLaunchKernelGGL((gemm_skinny_kernel<MMAX, NC, true>), grid, dim3(256), lds, st, p, M, rs);
   } else {

@@ -17,6 +17,7 @@
 //   A ring   [NST][128][64]         16 KiB per stage
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -255,22 +256,15 @@ __global__ __launch_bounds__(kStreamThreads) void gemm_stream_kernel(ConvGemmArg
   }
 }
 
-int g_num_cu = 0;
-
 template <int BN, int ACT>
 void launch_stream(const ConvGemmArgs& p, hipStream_t st) {
   const int M = p.B * p.Ho * p.Wo;
   const int n_nt = cdiv(p.N, BN);
   const int m_tiles = cdiv(M, SBM);
-  int groups = std::max(1, g_num_cu / n_nt);
+  int groups = std::max(1, device_cus() / n_nt);
   groups = std::min(groups, m_tiles);
   const size_t smem = sizeof(uint16_t) * ((size_t)(p.K / SBK) * BN * SBK + (size_t)NST * SBM * SBK);
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_stream_kernel<BN, ACT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
+  allow_dynamic_lds<&gemm_stream_kernel<BN, ACT>>(160 * 1024);
   hipLaunchKernelGGL((gemm_stream_kernel<BN, ACT>), dim3(n_nt * groups), dim3(kStreamThreads), smem, st, p, groups);
 }
 
@@ -297,11 +291,6 @@ bool gemm_stream_supported(const ConvGemmArgs& p) {
 }
 
 void conv_gemm_stream(const ConvGemmArgs& p, hipStream_t st) {
-  if (!g_num_cu) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&g_num_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
   const bool wide = stream_bn(p) == 128;
   if (p.glu) {
     SD_CHECK(p.act == kActNone && p.out_bf16 && p.N % 32 == 0, kErrInvalid,

@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -645,12 +646,7 @@ void launch_lstm_group_t(const float* gx, int B, int T, int ndir, const void* wh
                          uint16_t* hx, int Bp, unsigned* counters, int* err, int* host_err, hipStream_t st,
                          const void* whh_lo = nullptr) {
   const size_t smem = sizeof(uint16_t) * 256 * LS_WS;
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_group_bf16_kernel<MT, WV, X3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
+  allow_dynamic_lds<&lstm_group_bf16_kernel<MT, WV, X3>>(160 * 1024);
   const int groups = ndir * cdiv(B, 16 * MT);
   hipLaunchKernelGGL((lstm_group_bf16_kernel<MT, WV, X3>), dim3(4 * groups), dim3(64 * WV), smem, st, gx, B, T,
                      ndir, reinterpret_cast<const uint16_t*>(whh_bf16), reinterpret_cast<const uint16_t*>(whh_lo),
@@ -667,8 +663,7 @@ int lstm_group_blocks_per_cu() {
   static int nb = -1;
   if (nb < 0) {
     const size_t smem = sizeof(uint16_t) * 256 * LS_WS;
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_group_bf16_kernel<MT, WV, X3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    allow_dynamic_lds<&lstm_group_bf16_kernel<MT, WV, X3>>(160 * 1024);
     int v = 0;
     SD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, lstm_group_bf16_kernel<MT, WV, X3>, 64 * WV, smem));
     nb = v;
@@ -714,12 +709,7 @@ int lstm_group_capacity(int mt) {
 }
 
 int lstm_group_mt(int B, int ndir) {
-  static int n_cu = 0;
-  if (!n_cu) {
-    int dev = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
+  const int n_cu = device_cus();
   // Smallest row block (16 * MT) whose 4 x groups fit one workgroup per CU, provided the occupancy
   // query admits the kernel at all (co-residency of every workgroup of the grid); else 0 and the
   // caller takes the per-step launches.
@@ -862,23 +852,13 @@ void lstm_recurrence(const float* gx, int B, int T, int H, int ndir, const float
   if (c0) SD_HIP(hipMemcpyAsync(c, c0, n * 4, hipMemcpyDeviceToDevice, st));
   else zero_fill(c, n * 4, st);
   const size_t smem = sizeof(float) * ((kBB + kRows) * (H + 4) + kBB * (kRows + 1));
-  static bool attr_set = false;
-  if (!attr_set) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_step_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  allow_dynamic_lds<&lstm_step_kernel>(160 * 1024);
   ProfScope prof("lstm_recurrence", 2.0 * ndir * B * T * 4.0 * H * H,
                  4.0 * ((double)B * T * ndir * 4 * H + (double)T * ndir * 4 * H * H), st);
   if (whh_bf16 && H % kUB2 == 0) {
     const size_t smem2 = sizeof(uint16_t) * (size_t)(kBB + kRows2) * (H + 8) + sizeof(float) * kBB * (kRows2 + 1);
     SD_CHECK(smem2 <= 160 * 1024, kErrInvalid, "lstm: hidden size too large for the bf16 step kernel");
-    static bool attr2 = false;
-    if (!attr2) {
-      SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_step_bf16_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr2 = true;
-    }
+    allow_dynamic_lds<&lstm_step_bf16_kernel>(160 * 1024);
     dim3 grid2(H / kUB2, ndir, cdiv(B, kBB));
     for (int s = 0; s < T; ++s) {
       const float* hin = (s & 1) ? hB : hA;

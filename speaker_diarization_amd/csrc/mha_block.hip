@@ -24,6 +24,7 @@
 // HBM sees the normalised rows and the attention output only.
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -315,12 +316,7 @@ __global__ __launch_bounds__(W * 64) void mha_block_kernel(MhaBlockArgs a) {
 template <int SEQ, int W, int NSLOT, int QS, int PROBE = 0>
 void launch_mha(const MhaBlockArgs& a, hipStream_t st) {
   using L = MhaL<SEQ, W, NSLOT, QS>;
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mha_block_kernel<SEQ, W, NSLOT, QS, PROBE>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::kSmem));
-    attr = true;
-  }
+  allow_dynamic_lds<&mha_block_kernel<SEQ, W, NSLOT, QS, PROBE>>((int)L::kSmem);
   hipLaunchKernelGGL((mha_block_kernel<SEQ, W, NSLOT, QS, PROBE>), dim3((a.S + SEQ - 1) / SEQ), dim3(L::kThreads),
                      L::kSmem, st, a);
 }

@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -1193,11 +1194,9 @@ static void launch_dwconv_pp_r(int S, int T, int C, hipStream_t st, const uint16
                                uint16_t* y, float* partial, int fused_silu) {
   static int resident = 0;
   if (!resident) {
-    int dev = 0, cus = 0, per = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    int per = 0;
     SD_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, dwconv_pp_kernel<K, R>, 256, 0));
-    resident = std::max(1, cus * std::max(1, per));
+    resident = std::max(1, device_cus() * std::max(1, per));
   }
   const int ncb = C / kDwCB;
   const int per_cb = std::max(1, std::min(S, resident / ncb));

@@ -19,6 +19,7 @@
 // element against a Python float (NEP 50).
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 
 namespace sd {
 
@@ -206,12 +207,7 @@ void run_segments(const float* med, int rows, int T, const ThresholdSet& thr, in
   if (rows == 0 || T == 0) return;
   const int W = (T + 31) / 32;
   const size_t lds = 2 * (size_t)W * sizeof(uint32_t);
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute((const void*)run_segments_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               160 * 1024 - 4096));
-    attr = true;
-  }
+  allow_dynamic_lds<&run_segments_kernel>(160 * 1024 - 4096);
   hipLaunchKernelGGL(run_segments_kernel, dim3(rows * thr.n), dim3(kSegThreads), lds, st, med, T, thr, lim_sil,
                      lim_sp, cap, seg_begin, seg_end, n_seg);
   SD_LAUNCH_CHECK();

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -283,12 +284,7 @@ void launch_res(const ConvGemmArgs& p, const ResFuse& f, hipStream_t st) {
   const int64_t blocks = (int64_t)p.B * g.n_th * g.n_tw * g.n_ct;
   SD_CHECK(blocks < (1ll << 31), kErrInvalid, "res_conv: too many tiles");
   const size_t smem = (size_t)4 * g.plane + (size_t)9 * 4 * NT * 16;
-  static bool attr = false;
-  if (!attr) {
-    SD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(res_conv_kernel<WM, WN, PB, S, SC>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-    attr = true;
-  }
+  allow_dynamic_lds<&res_conv_kernel<WM, WN, PB, S, SC>>(96 * 1024);
   SD_CHECK(smem <= 96 * 1024, kErrInvalid, "res_conv: LDS budget");
   hipLaunchKernelGGL((res_conv_kernel<WM, WN, PB, S, SC>), dim3((unsigned)blocks), dim3(kThreads), smem, st, p, f, g);
 }

@@ -39,6 +39,7 @@
 #include <vector>
 #include "common.h"
 #include "kernels.h"
+#include "launch.h"
 #include "prof.h"
 
 namespace sd {
@@ -612,18 +613,10 @@ void rowprog(const RowProgArgs& a, const char* name, hipStream_t st) {
   SD_CHECK(!(a.x_tiled || a.xo_tiled || a.a_tiled || a.y_tiled) || a.M % 16 == 0, kErrInvalid,
            "rowprog: the tiled X / A layouts need M % 16 == 0");
   if (a.M <= 0) return;
-  static int grid_max = 0;
-  if (!grid_max) {
-    int dev = 0, cus = 0;
-    SD_HIP(hipGetDevice(&dev));
-    SD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const void* ks[] = {reinterpret_cast<const void*>(rowprog_kernel<1, 0, 1>), reinterpret_cast<const void*>(rowprog_kernel<1, 0, 2>),
-                        reinterpret_cast<const void*>(rowprog_kernel<1, 0, 3>), reinterpret_cast<const void*>(rowprog_kernel<1, 0, 5>),
-                        reinterpret_cast<const void*>(rowprog_kernel<1, 0>), reinterpret_cast<const void*>(rowprog_kernel<1, 8, 5>)};
-    for (const void* k : ks)
-      SD_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSmemBytes));
-    grid_max = cus > 0 ? cus : 256;
-  }
+  allow_dynamic_lds<&rowprog_kernel<1, 0, 1>, &rowprog_kernel<1, 0, 2>, &rowprog_kernel<1, 0, 3>, &rowprog_kernel<1, 0, 5>,
+                    &rowprog_kernel<1, 0>, &rowprog_kernel<1, 8, 5>>((int)kSmemBytes);
+  const int cus = device_cus();
+  const int grid_max = cus > 0 ? cus : 256;
   const int ntiles = (a.M + kRows - 1) / kRows;
   const int grid = ntiles < grid_max ? ntiles : grid_max;
   const double rows = (double)a.M;
