@@ -720,6 +720,69 @@ int sd_probe_graph_memset(int n, int replays, int fork, int* bad_per_replay, voi
  * programs' MFMA-fragment layout (RowProgArgs::a_tiled), bit 1 = out written in it (S * T % 16 == 0). */
 int sd_op_mha_block(const void* y, const float* w, const float* bias, int S, int T, const int* key_len, void* out,
                     int variant, int flags, void* stream);
+/* The conformer conv module's depthwise conv over time (ops.hip glu_dwconv; kernel k odd <= 31, pad (k - 1) / 2, zeros
+ * outside each sequence) on S sequences, optionally followed by GroupNorm(1 group) + SiLU (groupnorm_silu).  x (S, T, C)
+ * or, with glu_in, the pointwise_conv1 output (S, T, 2 C) whose columns are 32-wide groups [16 values | their 16
+ * gates] (the GLU is applied on load); fp32, or bf16 bits with io_bf16 (y too).  w (C, k), bias (C) fp32; C % 16 == 0.
+ * mode 0: y = silu(conv) (the BatchNorm-folded form), partial unused; 1: y = conv and partial (S, cdiv(C, 64), 2) fp32 =
+ * each 64-channel block's (sum, sum of squares) of y over the sequence; 2: mode 1, then y = silu(GroupNorm(y) * gn_g +
+ * gn_b) in place, eps 1e-5.  Which kernel runs follows from the shape alone, as in the product. */
+int sd_op_glu_dwconv(const void* x, int S, int T, int C, const float* w, const float* bias, int k, int glu_in,
+                     int io_bf16, int mode, const float* gn_g, const float* gn_b, void* y, float* partial,
+                     void* stream);
+/* One conformer row program (rowprog.hip) over M rows of D = 384, every optional part selectable:
+ *   acc = X (fp32 rows), or row (s, t) = [ts[s] | mix[s / NS][t]] (192 + 192; zeros for t >= Tmix) of T_seq rows per
+ *         sequence when ts is set (ts (M / T_seq, 192), mix (., Tmix, ldmix) fp32);
+ *   acc += A w0^T + b0 when w0 is set (A (M, 384) bf16 bits, w0 (384, 384) fp32 torch layout, rounded to bf16); with
+ *         gn_partial, A is first replaced by silu(GroupNorm(A) * gn_g + gn_b), one group per gn_T rows, statistics
+ *         from gn_partial (M / gn_T, gn_nblk, 2) = (sum, sum of squares) partial sums;
+ *   per FFN i < n_ffn: acc += w2 silu(w1 LN(acc; ln_g, ln_b) + b1) + b2, then acc = LN(acc; post_g, post_b) when post_g
+ *         is set; w1 (hidden, 384), w2 (384, hidden) fp32, hidden % 32 == 0, <= 1024.  Nothing is scaled here: a caller
+ *         that wants the module's 1/2 passes w2 / b2 halved;
+ *   Xo = acc (fp32, nullable, may equal X); y = LN(acc; y_g, y_b) as bf16 bits (nullable); yt (nullable) = bf16(acc) in
+ *         the speakers-to-channels layout (M / (yt_NS T_seq), T_seq, yt_NS * 384).
+ * All LayerNorms use eps 1e-5.  Every pointer is a device pointer.  flags: bit 0 X, bit 1 Xo, bit 2 A, bit 3 y in the
+ * MFMA-tiled layouts (kernels.h RowProgArgs::x_tiled / a_tiled; M % 16 == 0, else SD_ERR_INVALID).  Synchronises
+ * `stream` (the weights are packed on the host). */
+typedef struct sd_rowprog_ffn {
+  const float *ln_g, *ln_b, *w1, *b1, *w2, *b2, *post_g, *post_b;
+  int hidden;
+} sd_rowprog_ffn;
+typedef struct sd_rowprog_op {
+  int M, flags;
+  const float* X;
+  float* Xo;
+  const float *ts, *mix;
+  int ldmix, Tmix, NS, T_seq;
+  const void* A;
+  const float *w0, *b0;
+  const float *gn_partial, *gn_g, *gn_b;
+  int gn_T, gn_nblk;
+  int n_ffn;
+  sd_rowprog_ffn ffn[2];
+  const float *y_g, *y_b;
+  void* y;
+  void* yt;
+  int yt_NS;
+} sd_rowprog_op;
+int sd_op_rowprog(const sd_rowprog_op* op, void* stream);
+/* torchaudio.models.Conformer (input_dim 384, convolution after attention) of n_layers layers on x (S, T, 384) fp32 ->
+ * out (S, T, 384) fp32, key_len device int32 (S) or NULL.  weights: one fp32 device array of n_weights floats, for
+ * layer 0 .. n_layers - 1 the layer's tensors flattened in its state_dict order: ffn1.sequential.{0.weight, 0.bias,
+ * 1.weight (ffn_dim, 384), 1.bias, 4.weight (384, ffn_dim), 4.bias}, self_attn_layer_norm.{weight, bias},
+ * self_attn.{in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias}, conv_module.layer_norm.{weight, bias},
+ * conv_module.sequential.{0.weight (768, 384, 1), 0.bias, 2.weight (384, 1, kernel), 2.bias, 3.weight, 3.bias,
+ * [group_norm 0 only: 3.running_mean, 3.running_var,] 5.weight (384, 384, 1), 5.bias}, ffn2.sequential.* as ffn1,
+ * final_layer_norm.{weight, bias}.  They go through the product's loader (the 1/2 fold, the GLU row interleave, the
+ * BatchNorm fold, the row-program packing).  precision 0 fp32, 1 bf16, 2 bf16x3.  use_generic 1: one run_conformer per
+ * layer; 0: run_conformer_stack's row programs (precision 1 only, SD_ERR_INVALID otherwise).  Speaker-stream mode (ts
+ * non-NULL, x NULL, precision 1, use_generic 0): the input rows of sequence s = b * NS + spk are [ts[s] | mix[b][t]]
+ * (ts (S, 192), mix (S / NS, Tmix, ldmix) fp32, zeros for t >= Tmix) and out is bf16 (S / NS, T, NS * 384).
+ * Synchronises `stream`. */
+int sd_op_conformer_stack(const float* x, int S, int T, const float* weights, int64_t n_weights, int n_layers,
+                          int ffn_dim, int nh, int kernel, int group_norm, const int* key_len, int precision,
+                          int use_generic, const float* ts, const float* mix, int ldmix, int Tmix, int NS, void* out,
+                          void* stream);
 /* nn.Conv1d on channel-last input x (B, T, Cin) with weight (Cout, Cin, k) -> out (B, To, Cout). */
 int sd_op_conv1d(const float* x, int B, int T, int Cin, const float* w, const float* b, int Cout,
                  int k, int stride, int pad, int dil, int act, float* out, int precision, void* stream);

@@ -165,6 +165,27 @@ class TsvadStreamConfig(ctypes.Structure):
     ]
 
 
+class RowprogFfn(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("ln_g", "ln_b", "w1", "b1", "w2", "b2", "post_g", "post_b")] + [("hidden", c_int)]
+
+
+class RowprogOp(ctypes.Structure):
+    """sd_rowprog_op (include/sdiar.h): one conformer row program, every pointer a device pointer or None."""
+    _fields_ = [
+        ("M", c_int), ("flags", c_int),
+        ("X", c_void_p), ("Xo", c_void_p),
+        ("ts", c_void_p), ("mix", c_void_p),
+        ("ldmix", c_int), ("Tmix", c_int), ("NS", c_int), ("T_seq", c_int),
+        ("A", c_void_p), ("w0", c_void_p), ("b0", c_void_p),
+        ("gn_partial", c_void_p), ("gn_g", c_void_p), ("gn_b", c_void_p),
+        ("gn_T", c_int), ("gn_nblk", c_int),
+        ("n_ffn", c_int),
+        ("ffn", RowprogFfn * 2),
+        ("y_g", c_void_p), ("y_b", c_void_p), ("y", c_void_p),
+        ("yt", c_void_p), ("yt_NS", c_int),
+    ]
+
+
 _SIGS = {
     "sd_last_error": (c_char_p, []),
     "sd_version": (c_int, []),
@@ -244,6 +265,12 @@ _SIGS = {
     "sd_debug_rowprog_probe": (c_int, [c_void_p]),
     "sd_probe_graph_memset": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
     "sd_op_mha_block": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "sd_op_glu_dwconv": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sd_op_rowprog": (c_int, [POINTER(RowprogOp), c_void_p]),
+    "sd_op_conformer_stack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
+                                      c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                      c_void_p]),
     "sd_op_cam_dense": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_int, c_void_p]),

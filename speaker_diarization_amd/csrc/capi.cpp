@@ -6,9 +6,11 @@
 #include <memory>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include <algorithm>
 
+#include "encoder.h"
 #include "kernels.h"
 #include "prof.h"
 #include "eda.h"
@@ -1373,6 +1375,205 @@ int sd_op_mha_block(const void* y, const float* w, const float* bias, int nseq, 
     m.y_tiled = flags & 1;     // y in RowProgArgs::a_tiled's fragment layout (what the FFN programs hand over)
     m.out_tiled = (flags >> 1) & 1;   // the output in that layout (what the out-projection program reads)
     sd::mha_block(m, st, variant);
+  });
+}
+
+int sd_op_glu_dwconv(const void* x, int nseq, int T, int C, const float* w, const float* bias, int k, int glu_in,
+                     int io_bf16, int mode, const float* gn_g, const float* gn_b, void* y, float* partial,
+                     void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && w && y && nseq >= 1 && T >= 1 && C >= 16, sd::kErrInvalid, "glu_dwconv: bad argument");
+    SD_CHECK(mode >= 0 && mode <= 2, sd::kErrInvalid, "glu_dwconv: mode must be 0, 1 or 2");
+    SD_CHECK(mode == 0 || partial, sd::kErrInvalid, "glu_dwconv: modes 1 and 2 need the partial sums buffer");
+    SD_CHECK(mode != 2 || (gn_g && gn_b), sd::kErrInvalid, "glu_dwconv: mode 2 needs gn_g / gn_b");
+    // which kernel runs is glu_dwconv's own decision from the shape, as in the product
+    sd::glu_dwconv(x, nseq, T, C, w, bias, k, y, mode == 0 ? nullptr : partial, mode == 0, glu_in != 0, io_bf16 != 0,
+                   st);
+    if (mode == 2) sd::groupnorm_silu(y, nseq, T, C, partial, gn_g, gn_b, 1e-5f, io_bf16 != 0, st);
+  });
+}
+
+int sd_op_rowprog(const sd_rowprog_op* op, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    constexpr int D = 384;
+    SD_CHECK(op && op->M >= 1 && op->flags >= 0 && op->flags <= 15, sd::kErrInvalid, "rowprog: bad argument");
+    SD_CHECK(op->Xo || op->yt, sd::kErrInvalid, "rowprog: no output");
+    SD_CHECK((op->X != nullptr) != (op->ts != nullptr), sd::kErrInvalid, "rowprog: exactly one of X and ts");
+    SD_CHECK(!op->ts || (op->mix && op->NS > 0 && op->T_seq > 0 && op->Tmix > 0 && op->ldmix >= D / 2 &&
+                         op->M % (op->NS * op->T_seq) == 0),
+             sd::kErrInvalid, "rowprog: speaker source arguments");
+    SD_CHECK(!op->yt || (op->yt_NS > 0 && op->T_seq > 0 && op->M % (op->yt_NS * op->T_seq) == 0), sd::kErrInvalid,
+             "rowprog: speaker sink arguments");
+    SD_CHECK((op->w0 != nullptr) == (op->A != nullptr) && (op->w0 != nullptr) == (op->b0 != nullptr), sd::kErrInvalid,
+             "rowprog: A, w0 and b0 go together");
+    SD_CHECK(!op->gn_partial || (op->w0 && op->gn_g && op->gn_b && op->gn_T > 0 && op->gn_nblk >= 1 &&
+                                 op->M % op->gn_T == 0),
+             sd::kErrInvalid, "rowprog: GroupNorm-on-load arguments");
+    SD_CHECK(op->n_ffn >= 0 && op->n_ffn <= 2, sd::kErrInvalid, "rowprog: n_ffn");
+    SD_CHECK((op->y != nullptr) == (op->y_g != nullptr) && (op->y != nullptr) == (op->y_b != nullptr), sd::kErrInvalid,
+             "rowprog: y, y_g and y_b go together");
+    for (int i = 0; i < op->n_ffn; ++i) {
+      const sd_rowprog_ffn& f = op->ffn[i];
+      SD_CHECK(f.ln_g && f.ln_b && f.w1 && f.b1 && f.w2 && f.b2 && sd::rowprog_supported(D, f.hidden, true) &&
+                   (f.post_g != nullptr) == (f.post_b != nullptr),
+               sd::kErrInvalid, "rowprog: ffn arguments");
+    }
+    SD_HIP(hipStreamSynchronize(st));
+    auto host = [](const float* d, size_t n) {
+      std::vector<float> h(n);
+      SD_HIP(hipMemcpy(h.data(), d, n * sizeof(float), hipMemcpyDeviceToHost));
+      return h;
+    };
+    std::vector<std::unique_ptr<Scratch>> keep;   // the packed pieces, freed once the stream has drained
+    auto put = [&](const void* h, size_t bytes) -> const void* {
+      keep.emplace_back(new Scratch(bytes, st));
+      SD_HIP(hipMemcpy(keep.back()->p, h, bytes, hipMemcpyHostToDevice));
+      return keep.back()->p;
+    };
+    sd::RowProgArgs r;
+    r.M = op->M;
+    r.X = op->X; r.Xo = op->Xo;
+    r.x_ts = op->ts; r.x_mix = op->mix; r.x_ldmix = op->ldmix; r.x_Tmix = op->Tmix; r.x_NS = op->NS;
+    r.T_seq = op->T_seq;
+    r.yt = op->yt; r.yt_NS = op->yt_NS;
+    if (op->w0) {
+      const std::vector<uint16_t> p = sd::rowprog_pack_pre(host(op->w0, (size_t)D * D), D, D);
+      r.w0 = put(p.data(), p.size() * 2);
+      r.A = op->A; r.b0 = op->b0;
+    }
+    if (op->gn_partial) {
+      r.gn_partial = op->gn_partial; r.gn_nblk = op->gn_nblk; r.gn_T = op->gn_T; r.gn_g = op->gn_g; r.gn_b = op->gn_b;
+    }
+    r.n_ffn = op->n_ffn;
+    for (int i = 0; i < op->n_ffn; ++i) {
+      const sd_rowprog_ffn& f = op->ffn[i];
+      const size_t hd = (size_t)f.hidden;
+      std::vector<float> b1;
+      // W2 / b2 as the kernel consumes them: the caller has folded the module's 1/2, nothing is scaled here
+      const std::vector<uint16_t> p = sd::rowprog_pack_ffn(host(f.w1, hd * D), host(f.w2, D * hd), f.hidden,
+                                                           host(f.ln_g, D), host(f.ln_b, D), host(f.b1, hd), b1);
+      r.ffn[i].w = put(p.data(), p.size() * 2);
+      r.ffn[i].hidden = f.hidden;
+      r.ffn[i].b1 = static_cast<const float*>(put(b1.data(), b1.size() * sizeof(float)));
+      r.ffn[i].b2 = f.b2;
+      r.ffn[i].post_g = f.post_g; r.ffn[i].post_b = f.post_b;
+    }
+    r.y = op->y; r.y_g = op->y_g; r.y_b = op->y_b;
+    r.x_tiled = op->flags & 1; r.xo_tiled = (op->flags >> 1) & 1;
+    r.a_tiled = (op->flags >> 2) & 1; r.y_tiled = (op->flags >> 3) & 1;
+    // the profiler name the conformer stack gives a program of this structure (encoder.cpp run_conformer_stack)
+    const char* name = op->w0 ? (op->n_ffn ? "rowprog_pw2_ffn" : "rowprog_out")
+                              : (op->n_ffn == 1 ? "rowprog_ffn" : "rowprog");
+    sd::rowprog(r, name, st);
+  });
+}
+
+int sd_op_conformer_stack(const float* x, int nseq, int T, const float* weights, int64_t n_weights, int n_layers,
+                          int ffn_dim, int nh, int kernel, int group_norm, const int* key_len, int precision,
+                          int use_generic, const float* ts, const float* mix, int ldmix, int Tmix, int NS, void* out,
+                          void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    constexpr int E = 384;
+    SD_CHECK(weights && out && nseq >= 1 && T >= 1 && n_layers >= 1 && ffn_dim >= 8 && ffn_dim % 8 == 0 && nh >= 1 &&
+                 E % nh == 0 && kernel >= 1 && kernel % 2 == 1,
+             sd::kErrInvalid, "conformer_stack: bad argument");
+    SD_CHECK(precision >= 0 && precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
+    const bool spk = ts != nullptr;
+    SD_CHECK(spk ? (mix && !x && NS >= 1 && nseq % NS == 0 && Tmix >= 1 && ldmix >= E / 2 && ldmix % 4 == 0) : x != nullptr,
+             sd::kErrInvalid, "conformer_stack: x, or the speaker streams ts / mix / NS / Tmix / ldmix");
+    const sd::GemmX3Scope x3(precision == 2);
+    const bool bf = precision == 1;
+    const int64_t F = ffn_dim;
+    // the flat blob's key order, per layer (torchaudio ConformerLayer's state_dict order)
+    std::vector<std::pair<std::string, std::vector<int64_t>>> order;
+    auto add_ffn = [&](const std::string& f) {
+      order.push_back({f + ".sequential.0.weight", {E}});
+      order.push_back({f + ".sequential.0.bias", {E}});
+      order.push_back({f + ".sequential.1.weight", {F, E}});
+      order.push_back({f + ".sequential.1.bias", {F}});
+      order.push_back({f + ".sequential.4.weight", {E, F}});
+      order.push_back({f + ".sequential.4.bias", {E}});
+    };
+    add_ffn("ffn1");
+    order.push_back({"self_attn_layer_norm.weight", {E}});
+    order.push_back({"self_attn_layer_norm.bias", {E}});
+    order.push_back({"self_attn.in_proj_weight", {3 * E, E}});
+    order.push_back({"self_attn.in_proj_bias", {3 * E}});
+    order.push_back({"self_attn.out_proj.weight", {E, E}});
+    order.push_back({"self_attn.out_proj.bias", {E}});
+    order.push_back({"conv_module.layer_norm.weight", {E}});
+    order.push_back({"conv_module.layer_norm.bias", {E}});
+    order.push_back({"conv_module.sequential.0.weight", {2 * E, E, 1}});
+    order.push_back({"conv_module.sequential.0.bias", {2 * E}});
+    order.push_back({"conv_module.sequential.2.weight", {E, 1, kernel}});
+    order.push_back({"conv_module.sequential.2.bias", {E}});
+    order.push_back({"conv_module.sequential.3.weight", {E}});
+    order.push_back({"conv_module.sequential.3.bias", {E}});
+    if (!group_norm) {
+      order.push_back({"conv_module.sequential.3.running_mean", {E}});
+      order.push_back({"conv_module.sequential.3.running_var", {E}});
+    }
+    order.push_back({"conv_module.sequential.5.weight", {E, E, 1}});
+    order.push_back({"conv_module.sequential.5.bias", {E}});
+    add_ffn("ffn2");
+    order.push_back({"final_layer_norm.weight", {E}});
+    order.push_back({"final_layer_norm.bias", {E}});
+    auto numel = [](const std::vector<int64_t>& s) {
+      int64_t n = 1;
+      for (int64_t d : s) n *= d;
+      return n;
+    };
+    int64_t per_layer = 0;
+    for (const auto& k : order) per_layer += numel(k.second);
+    SD_CHECK(n_weights == n_layers * per_layer, sd::kErrInvalid,
+             "conformer_stack: weights must hold " + std::to_string(n_layers * per_layer) + " floats");
+    std::vector<float> host((size_t)n_weights);
+    SD_HIP(hipStreamSynchronize(st));
+    SD_HIP(hipMemcpy(host.data(), weights, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+    sd::ParamStore ps;
+    const float* wp = host.data();
+    for (int i = 0; i < n_layers; ++i)
+      for (const auto& k : order) {
+        ps.set("conformer_layers." + std::to_string(i) + "." + k.first, wp, k.second.data(), (int)k.second.size());
+        wp += numel(k.second);
+      }
+    sd::DeviceArena arena;   // freed on return, after the stream has drained
+    sd::LayerLoader loader{ps, arena, bf};
+    std::vector<sd::ConformerL> Ls;
+    for (int i = 0; i < n_layers; ++i) Ls.push_back(loader.conformer("conformer_layers." + std::to_string(i), group_norm != 0));
+    ps.require_all_used();
+    const int64_t rows = (int64_t)nseq * T;
+    SD_CHECK(rows * std::max<int64_t>(ffn_dim, 3 * E) < (int64_t)1 << 31, sd::kErrInvalid, "conformer_stack: too many rows");
+    auto ws = [&](int64_t n) { return static_cast<float*>(arena.alloc((size_t)n * sizeof(float))); };
+    sd::EncoderWork w;
+    w.Y = ws(rows * E);
+    w.QKV = ws(rows * 3 * E);
+    w.AO = ws(rows * E);
+    w.H = ws(rows * std::max(ffn_dim, 2 * E));
+    w.partial = ws((int64_t)nseq * ((E + 63) / 64) * 2);
+    w.bf16 = bf;
+    w.split_k = false;
+    if (spk) {
+      SD_CHECK(!use_generic && sd::conformer_stack_fused(Ls, E, bf), sd::kErrInvalid,
+               "conformer_stack: the speaker streams need the fused stack (precision 1, use_generic 0)");
+      sd::SpeakerStreams io;
+      io.ts = ts; io.mix = mix; io.ldmix = ldmix; io.Tmix = Tmix; io.NS = NS; io.out = out;
+      sd::run_conformer_stack(Ls, ws(rows * E), nseq, T, E, nh, kernel, key_len, w, st, &io);
+    } else {
+      float* X = static_cast<float*>(out);
+      SD_HIP(hipMemcpyAsync(X, x, (size_t)rows * E * sizeof(float), hipMemcpyDeviceToDevice, st));
+      if (use_generic) {
+        for (const sd::ConformerL& L : Ls) sd::run_conformer(L, X, nseq, T, E, nh, kernel, key_len, w, st);
+      } else {
+        SD_CHECK(sd::conformer_stack_fused(Ls, E, bf), sd::kErrInvalid,
+                 "conformer_stack: use_generic 0 needs the row programs (precision 1, ffn_dim % 32 == 0, <= 1024)");
+        sd::run_conformer_stack(Ls, X, nseq, T, E, nh, kernel, key_len, w, st);
+      }
+    }
+    SD_HIP(hipStreamSynchronize(st));
   });
 }
 

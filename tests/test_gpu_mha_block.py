@@ -4,11 +4,17 @@ torch.nn.MultiheadAttention: q/k/v = y W^T + b, softmax(q k^T / sqrt(48)) v per 
 the lengths), on bf16 inputs.  Every kernel layout sd_op_mha_block can launch (0: the shipped <SEQ 2, 8 waves,
 3-slot ring, 48-wide Q / K rows>; 1-7: the round-5 sweep's other layouts, mha_block.hip) must agree with the
 reference within bf16 rounding and with each other bit for bit."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
-from speaker_diarization_amd import _lib
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from conformer_ref import tile_a as _tile, untile_a as _untile  # noqa: E402  (the row programs' fragment layout)
+from speaker_diarization_amd import _lib  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -35,20 +41,6 @@ def _run(y, w, b, key_len, variant, flags=0):
               _lib.stream_ptr(y.device))
     torch.cuda.synchronize()
     return out
-
-
-def _tile(x):
-    """(S, T, 384) rows -> the row programs' MFMA-fragment layout (kernels.h RowProgArgs::a_tiled): 16-row group g,
-    fragment kk (features 32 kk ..), lane l = row % 16 + 16 q holds features 32 kk + 8 q .. + 7 of row 16 g + l % 16."""
-    S, T, D = x.shape
-    r = x.reshape(S * T // 16, 16, D // 32, 4, 8)          # (group, row, kk, q, 8)
-    return r.permute(0, 2, 3, 1, 4).contiguous().reshape(S, T, D)
-
-
-def _untile(x):
-    S, T, D = x.shape
-    r = x.reshape(S * T // 16, D // 32, 4, 16, 8)           # (group, kk, q, row, 8)
-    return r.permute(0, 3, 1, 2, 4).contiguous().reshape(S, T, D)
 
 
 @pytest.mark.parametrize("S,T,lens", [(4, 150, False), (7, 150, True), (3, 100, False), (5, 37, True), (1, 160, False)])
