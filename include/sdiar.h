@@ -422,6 +422,85 @@ int sd_op_astp_pool_c(const void* x, int x_bf16, int B, int T, int C, const floa
 int sd_op_attention_scaled(const float* qkv, int S, int T, int D, int nh, float scale, float* out, int precision,
                            void* stream);
 
+/* ------------------------------------------------------------------ WavLM feature extractor
+ * Replaces WavLM.extract_features (egs/magicdata-ramc/ts_vad2/wavlm.py:359-414) of the WavLM class (:256-305) at the
+ * two published geometries, Base+ and Large:
+ *   feature_extractor     wavlm.py:434-556 (seven unbiased, unpadded Conv1d; "default": GroupNorm(512, 512) on layer 0;
+ *                         "layer_norm": LayerNorm(512) on every layer; GELU)
+ *   layer_norm + post_extract_proj   :377-384
+ *   encoder               :559-675 (x += GELU(pos_conv(x)), weight_norm(dim 2) folded at load; post-LN or pre-LN)
+ *   encoder layer         :678-805
+ *   attention             modules.py:463-579 (relative_attention_bias of layer 0 through _relative_positions_bucket
+ *                         :417-447 and compute_bias :449-461, gated per query by grep_linear / grep_a :533-548)
+ * State-dict keys are the module's (mask_emb, feature_extractor.conv_layers.*, layer_norm.*, post_extract_proj.*,
+ * encoder.pos_conv.0.{bias, parametrizations.weight.original0 / original1 | weight_g / weight_v}, encoder.layers.*,
+ * encoder.layer_norm.*).  Fixed here: conv_feature_layers [(512,10,5)] + [(512,3,2)]*4 + [(512,2,2)]*2, conv_bias
+ * False, conv_pos 128, conv_pos_groups 16, relative_position_embedding and gru_rel_pos True, num_buckets 320,
+ * max_distance 800, activation_fn "gelu"; no padding_mask, no masking, no waveform normalisation. */
+typedef struct sd_wavlm sd_wavlm;
+
+typedef struct {
+  int embed_dim;         /* (embed_dim, ffn_dim, heads) = (768, 3072, 12) or (1024, 4096, 16) */
+  int ffn_dim;
+  int heads;
+  int encoder_layers;    /* 1..24 (the TS-VAD recipes cut the stack to 6) */
+  int extractor_mode;    /* 0: "default", 1: "layer_norm" */
+  int layer_norm_first;  /* 0 with extractor_mode 0 (Base+), 1 with extractor_mode 1 (Large) */
+  int max_batch;         /* workspace: windows per forward */
+  int max_samples;       /* workspace: samples per window, >= 400 (64000 = 4 s) */
+  int precision;         /* 0: fp32 (exact-f32 MFMA), 1: bf16 GEMM / attention operands (layer 0, LayerNorms, softmax,
+                            gates and the residual stream stay fp32) */
+} sd_wavlm_config;
+
+/* Output frames of the conv front end (wavlm.py:434-556): 400..719 samples -> 1, 16000 -> 49, 64000 -> 199,
+ * 96000 -> 299; 0 below 400 samples.  Host only, no handle (exported rather than static so that bindings can call it). */
+int sd_wavlm_frames(int n_samples);
+
+/* WavLM.__init__ (wavlm.py:256-305); anything outside the configurations above gives SD_ERR_INVALID with a message
+ * naming the field */
+int sd_wavlm_create(const sd_wavlm_config* cfg, sd_wavlm** out);
+/* load_state_dict (strict here) */
+int sd_wavlm_set_param(sd_wavlm* h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+int sd_wavlm_finalize(sd_wavlm* h);
+/* wavlm.py:359-414.  source: device (B, n_samples) fp32 waveforms, n_samples >= 400; T = sd_wavlm_frames(n_samples).
+ * output_layer: 0 = None (every layer, and in pre-LN mode the final encoder.layer_norm, wavlm.py:623-624), k >= 1 =
+ * stop after layer k (no final norm).  x_out: device (B, T, D) or NULL; features_out: device (B, T, D) or NULL, the
+ * projected conv features (ret_conv); layers_out: device (output_layer + 1, B, T, D) or NULL, the input to layer 0
+ * then each layer's output (ret_layer_results; needs output_layer >= 1).  At least one output is required. */
+int sd_wavlm_forward(sd_wavlm* h, const float* source, int B, int n_samples, int output_layer, float* x_out,
+                     float* features_out, float* layers_out, void* stream);
+int64_t sd_wavlm_device_bytes(const sd_wavlm* h);
+int sd_wavlm_destroy(sd_wavlm* h);
+
+/* Host-only probes (no device): out[r + n - 1] = _relative_positions_bucket(r) (modules.py:417-447) for every
+ * relative position r = key - query in [-(n - 1), n - 1]; and the folded positional-conv weight g v / |v| (wavlm.py:
+ * 578-580, weight_norm dim 2) of g (128) and v (D, D / 16, 128), D 768 or 1024, into out (D, D / 16, 128). */
+int sd_probe_wavlm_buckets(int n, int32_t* out);
+int sd_probe_wavlm_pos_weight(const float* g, const float* v, int D, float* out);
+
+/* Test-only single ops of the WavLM trunk (csrc/wavlm.hip); every pointer is a device pointer, precision 0 or 1 as
+ * above.
+ * sd_op_wavlm_layer0: conv layer 0 + norm + GELU of wav (B, n): w (512, 10), norm affine g / b (512), layer_norm 0 =
+ *   GroupNorm per (window, channel), 1 = LayerNorm over channels; out (B, (n - 10) / 5 + 1, 512), bf16 when out_bf16.
+ * sd_op_wavlm_conv: one of conv layers 1-6 on x (B, T, 512) fp32: w (512, 512, k), k 2 or 3, stride 2, then GELU, or
+ *   LayerNorm(ln_g, ln_b) + GELU when ln_g is given; out (B, (T - k) / 2 + 1, 512) fp32.  Here precision 2 is
+ *   precision 1 with a bf16 map out, as the model's bf16 mode runs layers 1-5: with ln_g the raw conv result is
+ *   stored in bf16 and the LayerNorm (fp32 statistics) reads that map.
+ * sd_op_wavlm_pos_conv: out = x + GELU(conv(x) + bias) on x (B, T, D) with the folded weight w (D, D / 16, 128).
+ * sd_op_wavlm_bias_table: table (H, 2 T - 1) from relative_attention_bias.weight emb (320, H).
+ * sd_op_wavlm_attention: the gated attention on qkv (B T, 3 H 64) = (q | k | v) and the layer input xin (B T, H 64):
+ *   grep_w (8, 64), grep_b (8), grep_a (H), table (H, 2 T - 1); out (B T, H 64) fp32. */
+int sd_op_wavlm_layer0(const float* wav, int B, int n, const float* w, const float* g, const float* b, int layer_norm,
+                       void* out, int out_bf16, void* stream);
+int sd_op_wavlm_conv(const float* x, int B, int T, const float* w, int k, const float* ln_g, const float* ln_b,
+                     void* out, int precision, void* stream);
+int sd_op_wavlm_pos_conv(const float* x, int B, int T, int D, const float* w, const float* bias, float* out,
+                         int precision, void* stream);
+int sd_op_wavlm_bias_table(const float* emb, int T, int H, float* table, void* stream);
+int sd_op_wavlm_attention(const float* qkv, const float* xin, int B, int T, int H, const float* grep_w,
+                          const float* grep_b, const float* grep_a, const float* table, float* out, int precision,
+                          void* stream);
+
 /* ------------------------------------------------------------------ SSND
  * Replaces SSNDModel.infer (egs/alimeeting/ssnd/ssnd_model.py:752-776) with extractor
  * 'CAM++_wo_gsp' (:107-124), SSNDConformerEncoder (:172-195), DetectionDecoder (:274-296: the

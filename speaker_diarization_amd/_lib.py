@@ -144,6 +144,12 @@ class RedimnetConfig(ctypes.Structure):
     ]
 
 
+class WavlmConfig(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in (
+        "embed_dim", "ffn_dim", "heads", "encoder_layers", "extractor_mode", "layer_norm_first", "max_batch",
+        "max_samples", "precision")]
+
+
 class SsndConfig(ctypes.Structure):
     _fields_ = [(n, c_int) for n in (
         "max_batch", "max_fbank_frames", "max_speakers", "feat_dim", "emb_dim", "q_det_aux_dim", "q_rep_aux_dim",
@@ -218,6 +224,18 @@ _SIGS = {
     "sd_ecapa_debug_stats": (c_int, [c_void_p, POINTER(c_void_p)]),
     "sd_redimnet_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_redimnet_debug_generic": (c_int, [c_void_p, c_int]),
+    "sd_wavlm_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sd_wavlm_frames": (c_int, [c_int]),
+    "sd_probe_wavlm_buckets": (c_int, [c_int, c_void_p]),
+    "sd_probe_wavlm_pos_weight": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "sd_op_wavlm_layer0": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                   c_void_p]),
+    "sd_op_wavlm_conv": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                 c_void_p]),
+    "sd_op_wavlm_pos_conv": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "sd_op_wavlm_bias_table": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sd_op_wavlm_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int, c_void_p]),
     "sd_op_attention_scaled": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
     "sd_op_redim_block2d": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -319,7 +337,8 @@ _SIGS = {
 # -> <the kind's forward calls>* -> destroy, device_bytes at any time.
 KINDS = {"tsvad": TsvadConfig, "tsvad_stream": TsvadStreamConfig, "eda": EdaConfig, "fseend": FseendConfig,
          "campp": CamppConfig, "resnet34": Resnet34Config, "simam_resnet34": SimamResnet34Config,
-         "eres2netv2": Eres2netv2Config, "ecapa": EcapaConfig, "redimnet": RedimnetConfig, "ssnd": SsndConfig}
+         "eres2netv2": Eres2netv2Config, "ecapa": EcapaConfig, "redimnet": RedimnetConfig, "wavlm": WavlmConfig,
+         "ssnd": SsndConfig}
 for _kind, _conf in KINDS.items():
     _SIGS[f"sd_{_kind}_create"] = (c_int, [POINTER(_conf), POINTER(c_void_p)])
     _SIGS[f"sd_{_kind}_set_param"] = (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int])

@@ -23,6 +23,7 @@
 #include "eres2net.h"
 #include "ecapa.h"
 #include "redimnet.h"
+#include "wavlm.h"
 #include "tsvad_stream.h"
 #include "ssnd.h"
 
@@ -50,6 +51,7 @@ struct sd_simam_resnet34 : Handle<sd::SimamEmbModel> {};
 struct sd_eres2netv2 : Handle<sd::ERes2NetV2Model> {};
 struct sd_ecapa : Handle<sd::EcapaModel> {};
 struct sd_redimnet : Handle<sd::RedimNetModel> {};
+struct sd_wavlm : Handle<sd::WavlmModel> {};
 struct sd_ssnd : Handle<sd::SsndModel> {};
 
 namespace {
@@ -776,6 +778,147 @@ int sd_redimnet_debug_generic(sd_redimnet* h, int on) {
 int64_t sd_redimnet_device_bytes(const sd_redimnet* h) { return device_bytes(h); }
 
 int sd_redimnet_destroy(sd_redimnet* h) { return destroy(h); }
+
+int sd_wavlm_create(const sd_wavlm_config* c, sd_wavlm** out) {
+  return guard([&] {
+    SD_CHECK(c && out, sd::kErrInvalid, "null argument");
+    SD_CHECK(c->precision == 0 || c->precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    SD_CHECK((c->embed_dim == 768 && c->ffn_dim == 3072 && c->heads == 12) ||
+                 (c->embed_dim == 1024 && c->ffn_dim == 4096 && c->heads == 16),
+             sd::kErrInvalid,
+             "WavLM (MI355X backend) builds (embed_dim, ffn_dim, heads) = (768, 3072, 12) or (1024, 4096, 16) only");
+    SD_CHECK(c->encoder_layers >= 1 && c->encoder_layers <= 24, sd::kErrInvalid, "encoder_layers must be 1..24");
+    SD_CHECK((c->extractor_mode == 0 && c->layer_norm_first == 0) || (c->extractor_mode == 1 && c->layer_norm_first == 1),
+             sd::kErrInvalid,
+             "WavLM (MI355X backend) builds (extractor_mode, layer_norm_first) = (0 default, 0) or (1 layer_norm, 1) only");
+    SD_CHECK(c->max_batch > 0, sd::kErrInvalid, "max_batch must be positive");
+    SD_CHECK(c->max_samples >= sd::WavlmModel::kMinSamples, sd::kErrInvalid, "max_samples must be at least 400");
+    // rows (B T) and map values per launch are counted in int
+    SD_CHECK((int64_t)c->max_batch * sd::WavlmModel::frames(c->max_samples) * c->ffn_dim < (1ll << 31) &&
+                 (int64_t)std::min(c->max_batch, sd::WavlmModel::kSlice) * (c->max_samples / 5) * 512 < (1ll << 31),
+             sd::kErrInvalid, "max_batch * frames(max_samples) * ffn_dim must be below 2^31");
+    sd::WavlmConfig t;
+    t.embed_dim = c->embed_dim; t.ffn_dim = c->ffn_dim; t.heads = c->heads; t.layers = c->encoder_layers;
+    t.layer_norm_mode = c->extractor_mode == 1;
+    t.pre_ln = c->layer_norm_first == 1;
+    t.max_batch = c->max_batch; t.max_samples = c->max_samples;
+    t.bf16 = c->precision == 1;
+    create(out, false, t);
+  });
+}
+
+int sd_wavlm_set_param(sd_wavlm* h, const char* name, const float* data, const int64_t* shape, int ndim) {
+  return set_param(h, name, data, shape, ndim);
+}
+
+int sd_wavlm_finalize(sd_wavlm* h) { return finalize(h); }
+
+int sd_wavlm_forward(sd_wavlm* h, const float* source, int B, int n_samples, int output_layer, float* x_out,
+                     float* features_out, float* layers_out, void* stream) {
+  return guard([&] {
+    SD_CHECK(h && source && (x_out || features_out || layers_out), sd::kErrInvalid, "null argument");
+    h->model->forward(source, B, n_samples, output_layer, x_out, features_out, layers_out, S(stream));
+  });
+}
+
+int64_t sd_wavlm_device_bytes(const sd_wavlm* h) { return device_bytes(h); }
+
+int sd_wavlm_destroy(sd_wavlm* h) { return destroy(h); }
+
+int sd_wavlm_frames(int n_samples) { return sd::WavlmModel::frames(n_samples); }
+
+int sd_probe_wavlm_buckets(int n, int32_t* out) {
+  return guard([&] {
+    SD_CHECK(out, sd::kErrInvalid, "null argument");
+    SD_CHECK(n >= 1, sd::kErrInvalid, "probe_wavlm_buckets: n must be at least 1");
+    for (int r = -(n - 1); r <= n - 1; ++r) out[r + n - 1] = sd::wavlm_bucket(r);
+  });
+}
+
+int sd_probe_wavlm_pos_weight(const float* g, const float* v, int D, float* out) {
+  return guard([&] {
+    SD_CHECK(g && v && out, sd::kErrInvalid, "null argument");
+    SD_CHECK(D == 768 || D == 1024, sd::kErrInvalid, "probe_wavlm_pos_weight: D must be 768 or 1024");
+    sd::wavlm_fold_pos_weight(g, v, D, out);
+  });
+}
+
+int sd_op_wavlm_layer0(const float* wav, int B, int n, const float* w, const float* g, const float* b, int layer_norm,
+                       void* out, int out_bf16, void* stream) {
+  return guard([&] {
+    SD_CHECK(wav && w && g && b && out, sd::kErrInvalid, "wavlm_layer0: null argument");
+    SD_CHECK(B >= 1 && n >= 10, sd::kErrInvalid, "wavlm_layer0: B >= 1 and n >= 10");
+    hipStream_t st = S(stream);
+    const int T0 = (n - 10) / 5 + 1;
+    Scratch partial((size_t)B * sd::wavlm_l0_parts(T0) * 3 * 512 * 4, st), ss((size_t)B * 2 * 512 * 4, st);
+    sd::wavlm_layer0(wav, B, n, w, g, b, layer_norm != 0, static_cast<float*>(partial.p), static_cast<float*>(ss.p),
+                     out, out_bf16 != 0, st);
+  });
+}
+
+int sd_op_wavlm_conv(const float* x, int B, int T, const float* w, int k, const float* ln_g, const float* ln_b,
+                     void* out, int precision, void* stream) {
+  return guard([&] {
+    SD_CHECK(x && w && out && (ln_g == nullptr) == (ln_b == nullptr), sd::kErrInvalid, "wavlm_conv: bad argument");
+    SD_CHECK(B >= 1 && (k == 2 || k == 3) && T >= k, sd::kErrInvalid, "wavlm_conv: k must be 2 or 3 and T >= k");
+    SD_CHECK(precision >= 0 && precision <= 2, sd::kErrInvalid, "wavlm_conv: precision must be 0, 1 or 2");
+    hipStream_t st = S(stream);
+    const bool bf = precision >= 1, obf = precision == 2;
+    PackedScratch wt(w, 512, 512, k, bf, st);
+    Activations xa(x, (int64_t)B * T * 512, bf ? 2 : 0, st);
+    sd::ConvGemmArgs p;
+    p.A = xa.a; p.a_bf16 = bf; p.B = B; p.H = 1; p.W = T; p.Cin = 512; p.lda = 512;
+    p.kh = 1; p.kw = k; p.sw = 2; p.Ho = 1; p.Wo = (T - k) / 2 + 1;
+    p.Wt = wt.p; p.N = 512; p.K = 512 * k;
+    p.act = ln_g ? sd::kActNone : sd::kActGelu;
+    p.out = out; p.out_bf16 = obf; p.o_sb = (int64_t)p.Wo * 512; p.o_sw = 512; p.o_sn = 1;
+    sd::conv_gemm(p, bf, st);
+    if (ln_g) sd::wavlm_ln_gelu(out, obf, (int64_t)B * p.Wo, ln_g, ln_b, st);
+  });
+}
+
+int sd_op_wavlm_pos_conv(const float* x, int B, int T, int D, const float* w, const float* bias, float* out,
+                         int precision, void* stream) {
+  return guard([&] {
+    SD_CHECK(x && w && bias && out, sd::kErrInvalid, "wavlm_pos_conv: null argument");
+    SD_CHECK(D == 768 || D == 1024, sd::kErrInvalid, "wavlm_pos_conv: D must be 768 or 1024");
+    SD_CHECK(precision == 0 || precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    hipStream_t st = S(stream);
+    const bool bf = precision == 1;
+    PackedScratch wt(w, D, D / 16, 128, bf, st);   // (D, D / 16, 128) -> [D][tap * D / 16 + c]
+    sd::wavlm_pos_conv(x, B, T, D, wt.p, bf, bias, out, st);
+  });
+}
+
+int sd_op_wavlm_attention(const float* qkv, const float* xin, int B, int T, int H, const float* grep_w,
+                          const float* grep_b, const float* grep_a, const float* table, float* out, int precision,
+                          void* stream) {
+  return guard([&] {
+    SD_CHECK(qkv && xin && grep_w && grep_b && grep_a && table && out, sd::kErrInvalid, "wavlm_attention: null argument");
+    SD_CHECK(B >= 1 && T >= 1 && H >= 1, sd::kErrInvalid, "wavlm_attention: empty problem");
+    SD_CHECK(precision == 0 || precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    hipStream_t st = S(stream);
+    const bool bf = precision == 1;
+    Activations qa(qkv, (int64_t)B * T * 3 * H * 64, bf ? 2 : 0, st);
+    sd::WavlmAttnArgs a;
+    a.qkv = qa.a; a.bf16 = bf; a.xin = xin; a.B = B; a.T = T; a.D = H * 64; a.H = H;
+    a.grep_w = grep_w; a.grep_b = grep_b; a.grep_a = grep_a; a.table = table;
+    a.out = out; a.out_bf16 = false;
+    sd::wavlm_attention(a, st);
+  });
+}
+
+int sd_op_wavlm_bias_table(const float* emb, int T, int H, float* table, void* stream) {
+  return guard([&] {
+    SD_CHECK(emb && table && T >= 1 && H >= 1, sd::kErrInvalid, "wavlm_bias_table: bad argument");
+    hipStream_t st = S(stream);
+    std::vector<int> bm(2 * T - 1);
+    for (int r = -(T - 1); r <= T - 1; ++r) bm[r + T - 1] = sd::wavlm_bucket(r);
+    Scratch d(bm.size() * sizeof(int), st);
+    SD_HIP(hipMemcpy(d.p, bm.data(), bm.size() * sizeof(int), hipMemcpyHostToDevice));
+    sd::wavlm_bias_table(emb, static_cast<const int*>(d.p), T - 1, T, H, table, st);
+  });
+}
 
 int sd_ssnd_create(const sd_ssnd_config* c, sd_ssnd** out) {
   return guard([&] {

@@ -964,4 +964,53 @@ void mamba2_scan(const Mamba2ScanArgs& a, hipStream_t st);
 // rows of `per_win` floats of every window of a group g with grp[g] set -> NaN: with a scan over the windows of a
 // reference forward, a non-finite input reaches every window of its group (both directions meet in backend_down).
 void poison_groups(float* x, int B, int64_t per_win, const int* grp, int group, hipStream_t st);
+
+// ---------------------------------------------------------------- wavlm (wavlm.hip)
+// Conv front end, layer 0 (wavlm.py:447-505): Conv1d(1 -> 512, k 10, stride 5, no bias, no padding) straight from the
+// waveforms wav (B, n) fp32, its norm and the erf GELU, written channel-last as out (B, T0, 512), T0 = (n - 10) / 5 + 1.
+// K = 10, so the conv is VALU work and is recomputed by every pass rather than stored.
+//   layer_norm false ("default"): Fp32GroupNorm(512, 512), one group per channel over the T0 frames of a window.  A
+//     statistics pass leaves (count, mean, M2) per 64 frames (two passes over each run, fp32), a second kernel merges
+//     them pairwise in fp64 (Chan) into scale / shift per (window, channel), the third normalises.  partial: scratch
+//     of B * wavlm_l0_parts(T0) * 3 * 512 floats, ss: B * 2 * 512 floats.
+//   layer_norm true: Fp32LayerNorm(512) over the channels of each frame, one pass (partial / ss unused).
+// w: (512, 10) fp32; g, b: the norm's affine (512 each).
+int wavlm_l0_parts(int T0);
+void wavlm_layer0(const float* wav, int B, int n, const float* w, const float* g, const float* b, bool layer_norm,
+                  float* partial, float* ss, void* out, bool out_bf16, hipStream_t st);
+// x = GELU(LayerNorm(x) g + b) in place over `rows` rows of 512 values (fp32, or bf16 bits): what follows the conv
+// of layers 1..6 in layer_norm mode; fp32 statistics, eps 1e-5.
+void wavlm_ln_gelu(void* x, bool bf16, int64_t rows, const float* g, const float* b, hipStream_t st);
+// x[i] += t[i] over n values, t fp32 or bf16 bits (the pre-LN layers' residual adds).
+void wavlm_add(float* x, const void* t, bool t_bf16, int64_t n, hipStream_t st);
+// The positional conv of the encoder (wavlm.py:566-581, 635-637): out = x + GELU(conv(x) + bias) with Conv1d(D, D, 128,
+// padding 64, groups 16) and SamePad dropping the last frame, on x (B, T, D) fp32 channel-last, D / 16 = 48 or 64.  Per
+// (window, group, 64 frames) one workgroup stages the 191 zero-padded frames of the group's channels in LDS, where
+// row t of the implicit GEMM's A (K = 128 D / 16, tap-major) is the contiguous run starting at frame t, and reads
+// the weights as MFMA B fragments: bf16 operands (v_mfma_f32_16x16x32_bf16) or exact f32 (v_mfma_f32_16x16x4_f32).
+// wt: [D][128 * D / 16] with k = tap * (D / 16) + c, bf16 bits or fp32 (weight norm folded); out must not alias x.
+void wavlm_pos_conv(const float* x, int B, int T, int D, const void* wt, bool bf16, const float* bias, float* out,
+                    hipStream_t st);
+// table (H, 2 T - 1): table[h][r + T - 1] = emb[bmap[r + off]][h] for the relative positions r = key - query in
+// [-(T - 1), T - 1] (compute_bias, modules.py:449-461); emb (320, H), bmap: the bucket of position r at r + off.
+void wavlm_bias_table(const float* emb, const int* bmap, int off, int T, int H, float* table, hipStream_t st);
+// Self-attention with the gated relative-position bias (modules.py:530-578), head size 64, any T >= 1:
+//   gate[b, h, q] = ga (gb grep_a[h] - 1) + 2, (ga, gb) = sigmoid(sums of 4 of grep_w xin[b, q, h] + grep_b)
+//   out[b, q, h] = softmax_k(q k^T scale + gate * table[h][k - q + T - 1]) v
+// on a packed projection qkv (B T, 3 D) = (q | k | v), fp32 or bf16 bits.  xin (B T, D) fp32 is the layer's INPUT
+// (the normalised one in pre-LN mode), not q.  One workgroup per (16 queries, head, window) walks the keys 64 at a
+// time with a running max / sum (fp32 softmax); Q K^T and P V run on MFMA, bf16 operands when qkv is bf16, else exact
+// f32.  out (B T, D) at column h * 64, bf16 bits when out_bf16.
+struct WavlmAttnArgs {
+  const void* qkv = nullptr;
+  bool bf16 = false;
+  const float* xin = nullptr;
+  int B = 0, T = 0, D = 0, H = 0;
+  const float *grep_w = nullptr, *grep_b = nullptr, *grep_a = nullptr;   // (8, 64), (8), (H)
+  const float* table = nullptr;                                          // (H, 2 T - 1)
+  float scale = 0.125f;
+  void* out = nullptr;
+  bool out_bf16 = false;
+};
+void wavlm_attention(const WavlmAttnArgs& a, hipStream_t st);
 }  // namespace sd

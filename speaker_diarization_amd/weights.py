@@ -871,6 +871,75 @@ def redimnet_embed_state_dict(seed: int = 777, embed_dim: int = 192):
     return synthetic_state_dict(redimnet_layout("", embed_dim), seed)
 
 
+WAVLM_CONV_LAYERS = [(512, 10, 5)] + [(512, 3, 2)] * 4 + [(512, 2, 2)] * 2
+
+
+def wavlm_state_dict(cfg, seed: int = 777):
+    """Seeded WavLM weights under the reference key names (egs/magicdata-ramc/ts_vad2/wavlm.py:256-305; cfg: a
+    WavLMConfig of speaker_diarization_amd.ssl.wavlm or any object with its fields).  The reference's own
+    initialisation leaves the gated relative-position bias nearly inert (zeroing the bias table moves a 2-layer output
+    of max |x| 4 by 8e-3, zeroing grep_linear by 2e-4), so a golden made from it would pass with either wrong.  Here the
+    q / k projections are 6x and the v / out / fc weights 2x the reference's N(0, 0.02), the bias table is N(0, 1.5),
+    grep_linear N(0, 0.5), grep_a 1 + 0.5 N, the weight-norm gains g are 0.7 .. 1.3 of |v|, and every bias and norm
+    affine is perturbed by 0.1 N: tests/golden/make_golden_wavlm.py asserts that each of these terms moves the stored
+    outputs by at least ten times the fp32 bar."""
+    rng = np.random.default_rng(seed)
+    D, F, H, L = cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim, cfg.encoder_attention_heads, cfg.encoder_layers
+    ln_mode = cfg.extractor_mode == "layer_norm"
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+
+    def put(name, v):
+        sd[name] = np.ascontiguousarray(v, dtype=np.float32)
+
+    def normal(shape, std):
+        return rng.standard_normal(shape) * std
+
+    def affine(prefix, n):
+        put(prefix + ".weight", 1.0 + normal(n, 0.1))
+        put(prefix + ".bias", normal(n, 0.1))
+
+    def linear(prefix, n, k, std):
+        put(prefix + ".weight", normal((n, k), std))
+        put(prefix + ".bias", normal(n, 0.1))
+
+    put("mask_emb", rng.uniform(0.0, 1.0, D))
+    cin = 1
+    for i, (dim, k, _) in enumerate(WAVLM_CONV_LAYERS):
+        p = f"feature_extractor.conv_layers.{i}."
+        put(p + "0.weight", normal((dim, cin, k), np.sqrt(2.0 / (cin * k))))
+        if ln_mode:
+            affine(p + "2.1", dim)
+        elif i == 0:
+            affine(p + "2", dim)
+        cin = dim
+    b = 1.0 / np.sqrt(cin)
+    put("post_extract_proj.weight", rng.uniform(-b, b, (D, cin)))
+    put("post_extract_proj.bias", normal(D, 0.1))
+    put("encoder.pos_conv.0.bias", normal(D, 0.1))
+    v = normal((D, D // 16, 128), np.sqrt(4.0 / (128 * D)))
+    g = np.sqrt((v * v).sum(axis=(0, 1), keepdims=True)) * rng.uniform(0.7, 1.3, (1, 1, 128))
+    put("encoder.pos_conv.0.parametrizations.weight.original0", g)
+    put("encoder.pos_conv.0.parametrizations.weight.original1", v)
+    for i in range(L):
+        p = f"encoder.layers.{i}."
+        put(p + "self_attn.grep_a", 1.0 + normal((1, H, 1, 1), 0.5))
+        if i == 0:
+            put(p + "self_attn.relative_attention_bias.weight", normal((320, H), 1.5))
+        linear(p + "self_attn.k_proj", D, D, 0.12)
+        linear(p + "self_attn.v_proj", D, D, 0.04)
+        linear(p + "self_attn.q_proj", D, D, 0.12)
+        linear(p + "self_attn.out_proj", D, D, 0.04)
+        put(p + "self_attn.grep_linear.weight", normal((8, D // H), 0.5))
+        put(p + "self_attn.grep_linear.bias", normal(8, 0.5))
+        affine(p + "self_attn_layer_norm", D)
+        linear(p + "fc1", F, D, 0.04)
+        linear(p + "fc2", D, F, 0.04)
+        affine(p + "final_layer_norm", D)
+    affine("encoder.layer_norm", D)
+    affine("layer_norm", cin)
+    return sd
+
+
 def to_torch(sd):
     import torch
     return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
