@@ -72,7 +72,22 @@ typedef struct {
                                         72-bin fbank + Conv1d(1152 -> speaker_embed_dim, k5, stride 4, pad 2)),
                                         single/multi_backend "transformer"; ref_speech is (B, T, 72); the MagicData
                                         length rule (:1296-1309): mix frames within 3 of the label length, zero-padded
-                                        after the ReLU or cut, SD_ERR_SHAPE beyond */
+                                        after the ReLU or cut, SD_ERR_SHAPE beyond
+                                     5: "WavLM" (egs/magicdata-ramc/ts_vad2/model.py:867-889, 1171-1179): ref_speech is the
+                                        RAW WAVEFORM (B, n_samples); a WavLM of wavlm_layers (= select_encoder_layer_nums)
+                                        encoder layers, extract_features(ref_speech)[0] (with the final encoder.layer_norm
+                                        in pre-LN mode), then Conv1d(wavlm_embed_dim -> speaker_embed_dim, k5, stride 2,
+                                        pad 2); single/multi_backend "transformer".  n samples give T = (n - 400) / 320 + 1
+                                        WavLM frames and (T - 1) / 2 + 1 mix frames; variant 4's length rule applies
+                                     6: "WavLM_weight_sum" with wavlm_fuse_feat_post_norm (:890-927, 1180-1204): all
+                                        wavlm_layers layers run, their outputs (hss[1:], the input to layer 0 dropped)
+                                        are summed with `weights` = Linear(L -> 1, no bias), then wavlmproj = Linear(
+                                        wavlm_embed_dim -> speaker_embed_dim), wavlmlnorm = LayerNorm, and the same conv
+                                        on speaker_embed_dim (192 or 256) channels.  Without wavlm_fuse_feat_post_norm
+                                        the reference's forward raises (:1206-1213 unpack (T, B, D, L) in the wrong
+                                        order and the view fails): not built.
+                                     5 / 6: backend 0 and precision 0 / 1 only (the WavLM trunk has no bf16x3), no
+                                        padding mask (the collater's zero padding takes part, as in the reference) */
   int max_num_speaker;            /* TSVADDataConfig.max_num_speaker (4)                     */
   int rs_len;                     /* seconds; PositionalEncoding max_len = rs_len * 25       */
   int max_batch;                  /* workspace sizing                                        */
@@ -108,6 +123,12 @@ typedef struct {
                                      multiple of 16 up to 256 */
   int expand;                     /* backend 1 / 2: TSVADConfig.expand (4): expand * transformer_embed_dim must be a
                                      multiple of 64 (the Mamba2 head dimension) */
+  /* variants 5 / 6 (all zero otherwise: a config that ends before these fields, zero-extended, is today's model) */
+  int wavlm_embed_dim;            /* 768 (ffn 3072, 12 heads: Base / Base+) or 1024 (4096, 16: Large)             */
+  int wavlm_layers;               /* encoder layers that run and that speech_encoder.encoder.layers.* holds, 1..24  */
+  int wavlm_layer_norm_mode;      /* extractor_mode "layer_norm" (Large); must equal wavlm_pre_ln                   */
+  int wavlm_pre_ln;               /* layer_norm_first                                                                */
+  int max_samples;                /* workspace sizing: the longest window in samples (rs_len * 16000), >= 400        */
 } sd_tsvad_config;
 
 int sd_tsvad_create(const sd_tsvad_config* cfg, sd_tsvad** out);
@@ -133,7 +154,10 @@ int sd_tsvad_status(sd_tsvad* h, void* stream);
  * (the collater's batch, e.g. infer.py's 64) when this call covers several; 0: the call is one batch.
  * force: this call is a slice of a larger reference batch whose non-finite input lies in another slice —
  * bit 0: a non-finite fbank (both BatchNorms skipped for every window), bit 1: a non-finite variant-0
- * target-speaker embedding (backend_down's skipped).  sd_tsvad_forward = forward_batch 0, force 0. */
+ * target-speaker embedding (backend_down's skipped).  sd_tsvad_forward = forward_batch 0, force 0.
+ * Variants 5 / 6 (here and in sd_tsvad_forward / sd_tsvad_forward_graph): ref_speech is the waveform (B, n_samples) fp32
+ * and T_fbank carries n_samples, a multiple of 4 with 400 <= n_samples <= max_samples (SD_ERR_INVALID otherwise); force
+ * bit 0 then stands for a non-finite sample. */
 int sd_tsvad_forward_batched(sd_tsvad* h, const float* ref_speech, const float* target_speech, int B, int T_fbank,
                              int T_label, int forward_batch, int force, float* logits, void* stream);
 int64_t sd_tsvad_device_bytes(const sd_tsvad* h);
@@ -497,6 +521,15 @@ int sd_op_wavlm_conv(const float* x, int B, int T, const float* w, int k, const 
 int sd_op_wavlm_pos_conv(const float* x, int B, int T, int D, const float* w, const float* bias, float* out,
                          int precision, void* stream);
 int sd_op_wavlm_bias_table(const float* emb, int T, int H, float* table, void* stream);
+/* TS-VAD's WavLM_weight_sum head, op by op (test entry points; device pointers).
+ * sd_op_wavlm_layer_mix: acc (n) = sum_l w[l] x[l] over L layer outputs x (L, n) fp32, accumulated layer by layer as the
+ *   model does (acc = w[0] x[0], then acc += w[l] x[l]); w is a HOST array of L floats; n a multiple of 4.
+ * sd_op_wavlm_mix_proj_ln: out (rows, SE) fp32 = LayerNorm(acc (rows, D) W^T + bias) g + beta, W (SE, D) torch layout,
+ *   SE 192 or 256, D a multiple of 32; precision 0: exact f32, 1: bf16 operands (acc and W rounded), fp32 accumulation
+ *   and LayerNorm, the bf16 output widened to fp32. */
+int sd_op_wavlm_layer_mix(const float* x, int L, int64_t n, const float* w_host, float* acc, void* stream);
+int sd_op_wavlm_mix_proj_ln(const float* acc, int rows, int D, const float* w, const float* bias, const float* g,
+                            const float* beta, int SE, float* out, int precision, void* stream);
 int sd_op_wavlm_attention(const float* qkv, const float* xin, int B, int T, int H, const float* grep_w,
                           const float* grep_b, const float* grep_a, const float* table, float* out, int precision,
                           void* stream);
@@ -699,6 +732,10 @@ int sd_fbank_kaldi_ex(const float* wav, int64_t n_samples, float in_scale, int n
 /* Window slicing + per-window mean normalisation (mean_nor=True, :55) + the
  * collater's zero pad to the batch max (ts_vad_dataset.py:664-701).
  * win_start / win_n: device int32 (n_win). out: device (n_win, T_out, n_mels). */
+/* The same gather on a raw waveform (TS-VAD variants 5 / 6; no mean removal, as ts_vad_dataset.py:185-188 does none):
+ * out (n_win, n_out) with out[w, j] = wav[win_start[w] + j] for j < win_n[w] (inside the n_total samples), else 0. */
+int sd_window_wave(const float* wav, int64_t n_total, const int* win_start, const int* win_n, int n_win, int n_out,
+                   float* out, void* stream);
 int sd_window_cmn(const float* feats, int n_mels, const int* win_start, const int* win_n, int n_win,
                   int T_out, float* out, void* stream);
 

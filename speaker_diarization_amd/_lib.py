@@ -40,6 +40,12 @@ class TsvadConfig(ctypes.Structure):
         ("backend", c_int),    # 0 the variant's own; 1 mamba2 + transformer; 2 mamba2 + mamba2 (variant 0 only)
         ("d_state", c_int),
         ("expand", c_int),
+        # variants 5 / 6 (WavLM / WavLM_weight_sum on the raw waveform); all zero otherwise
+        ("wavlm_embed_dim", c_int),
+        ("wavlm_layers", c_int),
+        ("wavlm_layer_norm_mode", c_int),
+        ("wavlm_pre_ln", c_int),
+        ("max_samples", c_int),
     ]
 
 
@@ -236,6 +242,9 @@ _SIGS = {
     "sd_op_wavlm_bias_table": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sd_op_wavlm_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_int, c_void_p]),
+    "sd_op_wavlm_layer_mix": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sd_op_wavlm_mix_proj_ln": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                        c_int, c_void_p]),
     "sd_op_attention_scaled": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
     "sd_op_redim_block2d": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -268,6 +277,7 @@ _SIGS = {
     "sd_fbank_kaldi": (c_int, [c_void_p, c_int64, c_float, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "sd_fbank_kaldi_ex": (c_int, [c_void_p, c_int64, c_float, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sd_window_cmn": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sd_window_wave": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sd_overlap_average": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                    c_void_p, c_void_p]),
     "sd_overlap_mean": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,

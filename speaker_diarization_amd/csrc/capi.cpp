@@ -195,9 +195,12 @@ int sd_probe_lstm_handoff(int steps, float* us_per_step, void* stream) {
 int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
-    SD_CHECK(c->variant >= 0 && c->variant <= 4, sd::kErrInvalid, "unknown TS-VAD variant");
+    SD_CHECK(c->variant >= 0 && c->variant <= 6, sd::kErrInvalid, "unknown TS-VAD variant");
+    const bool wave = c->variant >= 5;
+    SD_CHECK(!wave || c->precision != 2, sd::kErrInvalid,
+             "the WavLM speech encoders (variants 5 / 6) do not build bf16x3: the WavLM trunk runs in fp32 or bf16");
     SD_CHECK(c->precision >= 0 && c->precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
-    SD_CHECK(c->max_batch > 0 && c->max_fbank_frames > 0, sd::kErrInvalid, "bad workspace sizes");
+    SD_CHECK(c->max_batch > 0 && (wave || c->max_fbank_frames > 0), sd::kErrInvalid, "bad workspace sizes");
     SD_CHECK(c->max_num_speaker > 0 && c->num_transformer_layer >= 1 && c->transformer_ffn_embed_dim > 0 &&
                  c->speaker_embed_dim > 0, sd::kErrInvalid, "bad model dimensions");
     SD_CHECK(c->num_attention_head > 0 && c->transformer_embed_dim % c->num_attention_head == 0, sd::kErrInvalid,
@@ -217,6 +220,11 @@ int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
     t.backend = c->backend;
     t.d_state = c->d_state;
     t.expand = c->expand;
+    t.wavlm_embed_dim = c->wavlm_embed_dim;
+    t.wavlm_layers = c->wavlm_layers;
+    t.wavlm_layer_norm_mode = c->wavlm_layer_norm_mode != 0;
+    t.wavlm_pre_ln = c->wavlm_pre_ln != 0;
+    t.max_samples = c->max_samples;
     // proj_layer configurations (speaker_embed_dim * 2 != transformer_embed_dim); backend / d_state / expand
     sd::TsvadModel::validate(t);
     create(out, c->precision == 2, t);
@@ -920,6 +928,33 @@ int sd_op_wavlm_bias_table(const float* emb, int T, int H, float* table, void* s
   });
 }
 
+int sd_op_wavlm_layer_mix(const float* x, int L, int64_t n, const float* w_host, float* acc, void* stream) {
+  return guard([&] {
+    SD_CHECK(x && w_host && acc && L >= 1 && n >= 4, sd::kErrInvalid, "wavlm_layer_mix: bad argument");
+    for (int l = 0; l < L; ++l) sd::wavlm_layer_mix(acc, x + (int64_t)l * n, w_host[l], l == 0, n, S(stream));
+  });
+}
+
+int sd_op_wavlm_mix_proj_ln(const float* acc, int rows, int D, const float* w, const float* bias, const float* g,
+                            const float* beta, int SE, float* out, int precision, void* stream) {
+  return guard([&] {
+    SD_CHECK(acc && w && bias && g && beta && out && rows >= 1, sd::kErrInvalid, "wavlm_mix_proj_ln: bad argument");
+    SD_CHECK(SE == 192 || SE == 256, sd::kErrInvalid, "wavlm_mix_proj_ln: SE must be 192 or 256");
+    SD_CHECK(D >= 32 && D % 32 == 0, sd::kErrInvalid, "wavlm_mix_proj_ln: D must be a multiple of 32");
+    SD_CHECK(precision == 0 || precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    hipStream_t st = S(stream);
+    const bool bf = precision == 1;
+    PackedScratch wt(w, SE, D, 1, bf, st);
+    if (!bf) {
+      sd::wavlm_mix_proj_ln(acc, rows, D, wt.p, false, bias, g, beta, SE, out, st);
+      return;
+    }
+    Scratch ob((size_t)rows * SE * 2, st);
+    sd::wavlm_mix_proj_ln(acc, rows, D, wt.p, true, bias, g, beta, SE, ob.p, st);
+    sd::bf16_to_f32(ob.p, (int64_t)rows * SE, out, st);
+  });
+}
+
 int sd_ssnd_create(const sd_ssnd_config* c, sd_ssnd** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
@@ -970,6 +1005,14 @@ int sd_ssnd_decode(sd_ssnd* h, const float* enc, const float* x, const float* sp
 int64_t sd_ssnd_device_bytes(const sd_ssnd* h) { return device_bytes(h); }
 
 int sd_ssnd_destroy(sd_ssnd* h) { return destroy(h); }
+
+int sd_window_wave(const float* wav, int64_t n_total, const int* win_start, const int* win_n, int n_win, int n_out,
+                   float* out, void* stream) {
+  return guard([&] {
+    if (n_win == 0) return;
+    sd::window_wave(wav, n_total, win_start, win_n, n_win, n_out, out, S(stream));
+  });
+}
 
 int sd_window_cmn(const float* feats, int n_mels, const int* win_start, const int* win_n, int n_win,
                   int T_out, float* out, void* stream) {

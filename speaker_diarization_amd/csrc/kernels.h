@@ -1013,4 +1013,22 @@ struct WavlmAttnArgs {
   bool out_bf16 = false;
 };
 void wavlm_attention(const WavlmAttnArgs& a, hipStream_t st);
+
+// TS-VAD's WavLM_weight_sum head (egs/magicdata-ramc/ts_vad2/model.py:1193-1203).
+// The layer-weighted sum, accumulated as the encoder layers run: acc[i] = w x[i] (first) or acc[i] += w x[i] over n
+// fp32 values, n a multiple of 4, 16-byte aligned pointers.  `weights` = Linear(L -> 1, no bias) over the stacked layer
+// outputs is acc = sum_l w_l x_{l+1}; no (layers, rows, D) buffer exists.
+void wavlm_layer_mix(float* acc, const float* x, float w, bool first, int64_t n, hipStream_t st);
+// out (rows, SE) = LayerNorm_SE(acc (rows, D) Wt^T + bias) g + beta, eps 1e-5 (wavlmproj + wavlmlnorm): one MFMA GEMM
+// over K = D whose N tile spans the whole SE row (SE 192 or 256, four waves of SE / 4 columns over 16 rows), so the
+// LayerNorm runs in the epilogue on the fp32 accumulators (two passes, the row sums exchanged through LDS).  bf16:
+// Wt [SE][D] bf16 bits, acc rounded to bf16 on load (v_mfma_f32_16x16x32_bf16), out bf16 bits; else Wt fp32, exact f32
+// (v_mfma_f32_16x16x4_f32), out fp32.  D a multiple of 32.  out is what speech_down_or_up's conv_gemm reads as A.
+void wavlm_mix_proj_ln(const float* acc, int rows, int D, const void* wt, bool bf16, const float* bias, const float* g,
+                       const float* beta, int SE, void* out, hipStream_t st);
+// The pipeline's window gather on raw waveform, window_cmn's counterpart (no mean removal: ts_vad_dataset.py:185-188,
+// 759-761 hand the samples over as they are, the collater zero-pads :693-707): out[w, j] = wav[start_w + j] for
+// j < n_w (and start_w + j < n_total), else 0, for j < n_out.
+void window_wave(const float* wav, int64_t n_total, const int* win_start, const int* win_n, int n_win, int n_out,
+                 float* out, hipStream_t st);
 }  // namespace sd

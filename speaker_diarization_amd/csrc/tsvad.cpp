@@ -8,10 +8,14 @@
 //          variant 3 (ecapa_channel_1024_wespeaker, model.py:631-654): ECAPA-TDNN trunk (ecapa.h)
 //          variant 4 (ReDimNetB2, egs/magicdata-ramc/ts_vad2/model.py:694-715): ReDimNetB2 trunk on 72-bin fbank
 //                    (redimnet.h), get_frame_level_feat (:1246-1262)
+//          variants 5, 6 (WavLM / WavLM_weight_sum, magicdata model.py:867-927, 1171-1204): ref_speech is the raw
+//                    waveform (B, n_samples); the WavLM trunk (wavlm.h) on the caller's stream; 6 accumulates the
+//                    layer-weighted sum as the layers run, then wavlmproj + wavlmlnorm in one kernel
 //     -> speech_down_or_up (down_gemm) -> mix (B, T3, SE)
 //          variants 0, 1: conv + BN + ReLU                    model.py:385-395 / 406-416
 //          variant 2: SpeechFeatUpsample2 transposed conv + BN + ReLU (model.py:114-134)
 //          variants 3, 4: conv k5 stride 4 pad 2 + BN + ReLU (model.py:641-654; magicdata :703-715)
+//          variants 5, 6: conv k5 stride 2 pad 2 + BN + ReLU (magicdata :879-889, 913-927)
 //     -> transformer_backend, variants 0, 2, 3 and 4 (forward_common, model.py:758-897):
 //          [ts_embed | mix] + PE, 2-layer transformer per speaker (batched over speakers)
 //          -> backend_down conv(1536->384, k5)+BN+ReLU -> PE -> 2-layer transformer -> fc
@@ -27,6 +31,7 @@
 #include "tsvad.h"
 #include "prof.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace sd {
@@ -41,6 +46,22 @@ void TsvadModel::validate(const TsvadConfig& c) {
     SD_CHECK(c.variant == 0, kErrInvalid,
              "backend 1 / 2 (Mamba2 back ends) is built for variant 0 (speech_encoder_type CAM++) only");
     Mamba2Stack::validate(c.embed_dim, c.d_state, c.expand);
+  }
+  if (c.variant == 5 || c.variant == 6) {
+    SD_CHECK(c.backend == 0, kErrInvalid,
+             "the WavLM speech encoders (variants 5 / 6) are built with the transformer back end only (backend 0)");
+    SD_CHECK(c.wavlm_embed_dim == 768 || c.wavlm_embed_dim == 1024, kErrInvalid,
+             "variants 5 / 6 need the WavLM geometry: wavlm_embed_dim must be 768 or 1024");
+    SD_CHECK(c.wavlm_layers >= 1 && c.wavlm_layers <= 24, kErrInvalid, "wavlm_layers must be 1..24");
+    SD_CHECK(c.wavlm_layer_norm_mode == c.wavlm_pre_ln, kErrInvalid,
+             "WavLM (MI355X backend) builds (extractor_mode, layer_norm_first) = (0 default, 0) or (1 layer_norm, 1) only");
+    SD_CHECK(c.max_samples >= WavlmTrunk::kMinSamples, kErrInvalid, "max_samples must be at least 400");
+    SD_CHECK((int64_t)c.max_batch * WavlmTrunk::frames(c.max_samples) * (c.wavlm_embed_dim * 4) < (1ll << 31) &&
+                 (int64_t)std::min(c.max_batch, WavlmTrunk::kSlice) * (c.max_samples / 5) * 512 < (1ll << 31),
+             kErrInvalid, "max_batch * frames(max_samples) * ffn_dim must be below 2^31");
+    SD_CHECK(c.variant != 6 || c.speaker_embed_dim == 192 || c.speaker_embed_dim == 256, kErrInvalid,
+             "WavLM_weight_sum (variant 6) is built for speaker_embed_dim 192 or 256");
+    SD_CHECK(c.speaker_embed_dim % 32 == 0, kErrInvalid, "variants 5 / 6: speaker_embed_dim must be a multiple of 32");
   }
   if (c.speaker_embed_dim * 2 == c.embed_dim) return;
   // proj_layer = nn.Linear(2 SE, E) on cat(ts_embed, mix_embeds) (model.py:212-217, 873-874)
@@ -61,6 +82,37 @@ void TsvadModel::build() {
   } else if (cfg_.variant == 3) {
     ecapa_ = std::make_unique<EcapaTrunk>();
     ecapa_->load(ps_, arena_, se, cfg_.bf16);   // ecapa_tdnn_wespeaker.py:161-209 (no pool / bn / linear keys)
+  } else if (waveform()) {
+    // WavLM(wavlm_cfg) with encoder_layers = select_encoder_layer_nums (5) or the checkpoint's (6)
+    // (magicdata model.py:867-877, 890-899)
+    WavlmConfig w;
+    w.embed_dim = cfg_.wavlm_embed_dim;
+    w.ffn_dim = 4 * w.embed_dim;
+    w.heads = w.embed_dim / 64;
+    w.layers = cfg_.wavlm_layers;
+    w.layer_norm_mode = cfg_.wavlm_layer_norm_mode;
+    w.pre_ln = cfg_.wavlm_pre_ln;
+    w.max_batch = cfg_.max_batch;
+    w.max_samples = cfg_.max_samples;
+    w.bf16 = cfg_.bf16;
+    w.split_k = false;   // windows are sharded over ranks: no row-count-dependent summation order
+    wavlm_ = std::make_unique<WavlmTrunk>(w);
+    wavlm_->load(ps_, arena_, se);
+    if (cfg_.variant == 6) {
+      // weights = Linear(L, 1, bias=False), wavlmproj = Linear(D, SE), wavlmlnorm = LayerNorm(SE) (:904-909)
+      const HostTensor& mw = ps_.get("weights.weight");
+      SD_CHECK(mw.shape.size() == 2 && mw.shape[0] == 1 && mw.shape[1] == cfg_.wavlm_layers, kErrParam,
+               "weights.weight must be (1, wavlm encoder layers)");
+      mix_w_ = mw.data;
+      wproj_ = loader().linear("wavlmproj");
+      SD_CHECK(wproj_.w.N == cfg_.speaker_embed_dim && wproj_.w.K == cfg_.wavlm_embed_dim, kErrParam,
+               "wavlmproj.weight must be (speaker_embed_dim, wavlm embed dim)");
+      SD_CHECK(ps_.get("wavlmproj.bias").numel() == cfg_.speaker_embed_dim, kErrParam, "wavlmproj.bias size");
+      SD_CHECK(ps_.get("wavlmlnorm.weight").numel() == cfg_.speaker_embed_dim &&
+                   ps_.get("wavlmlnorm.bias").numel() == cfg_.speaker_embed_dim, kErrParam, "wavlmlnorm size");
+      wln_g_ = arena_.upload(ps_.get("wavlmlnorm.weight").data);
+      wln_b_ = arena_.upload(ps_.get("wavlmlnorm.bias").data);
+    }
   } else if (cfg_.variant == 4) {
     redim_ = std::make_unique<RedimTrunk>();
     redim_->load(ps_, arena_, se, cfg_.bf16);   // redimnet_wespeaker.py:623-790
@@ -126,6 +178,15 @@ void TsvadModel::build() {
     down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
     SD_CHECK(down_.w.N == cfg_.speaker_embed_dim && down_.w.Cin == RedimTrunk::kChannels && down_.w.kw == 5, kErrParam,
              "speech_down_or_up.0.weight must be (speaker_embed_dim, 1152, 5)");
+    SD_CHECK(ps_.get("speech_down_or_up.0.bias").numel() == cfg_.speaker_embed_dim, kErrParam,
+             "speech_down_or_up.0.bias size");
+    down_bn_ = bn_only("speech_down_or_up.1.bn");
+  } else if (waveform()) {
+    // Conv1d(D -> SE, k5, stride 2, pad 2), D the WavLM width (5) or speaker_embed_dim behind wavlmproj (6): no prologue
+    const int cin = cfg_.variant == 6 ? cfg_.speaker_embed_dim : cfg_.wavlm_embed_dim;
+    down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
+    SD_CHECK(down_.w.N == cfg_.speaker_embed_dim && down_.w.Cin == cin && down_.w.kw == 5, kErrParam,
+             "speech_down_or_up.0.weight must be (speaker_embed_dim, " + std::to_string(cin) + ", 5)");
     SD_CHECK(ps_.get("speech_down_or_up.0.bias").numel() == cfg_.speaker_embed_dim, kErrParam,
              "speech_down_or_up.0.bias size");
     down_bn_ = bn_only("speech_down_or_up.1.bn");
@@ -221,7 +282,7 @@ void TsvadModel::build() {
 
 TsvadModel::Geometry TsvadModel::geometry() const {
   Geometry g;
-  g.T3 = mix_frames(cfg_.max_fbank_frames);
+  g.T3 = mix_frames(max_input());
   g.Tl = std::max<int64_t>(g.T3 + 3, (int64_t)cfg_.rs_len * 25);   // the longest label a forward accepts
   g.rows = (int64_t)cfg_.max_batch * cfg_.max_num_speaker * g.Tl;
   g.mix_elems = (int64_t)cfg_.max_batch * g.T3 * cfg_.speaker_embed_dim;
@@ -235,6 +296,14 @@ void TsvadModel::alloc_workspace() {
   if (res_) res_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
   else if (ecapa_) ecapa_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
   else if (redim_) redim_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
+  else if (wavlm_) {
+    wavlm_->alloc(arena_);
+    if (cfg_.variant == 6) {   // one (B T, D) accumulator and one (B T, SE) map: nothing grows with the layer count
+      const int64_t rows = Bm * WavlmTrunk::frames(cfg_.max_samples);
+      acc_ = ws(rows * cfg_.wavlm_embed_dim);
+      z_ = arena_.alloc(rows * cfg_.speaker_embed_dim * (cfg_.bf16 ? 2 : 4));
+    }
+  }
   else cam_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
   mix_ = ws(g.mix_elems);
   mixg_ = ws(g.mix_elems);
@@ -410,7 +479,7 @@ void TsvadModel::check_label_frames(int T3, int Tl) const {
     SD_CHECK(std::abs(T3 - Tl) <= 3, kErrShape, diff);
     return;
   }
-  if (cfg_.variant == 4) {
+  if (cfg_.variant >= 4) {
     // egs/magicdata-ramc/ts_vad2/model.py:1296-1309: |gap| <= 3; a short encoder output is zero-padded by 1 to 3
     // frames after the ReLU (the consumers read mix rows >= T3 as zeros), a long one is cut at the label length
     SD_CHECK(std::abs(T3 - Tl) <= 3, kErrShape,
@@ -448,6 +517,17 @@ void TsvadModel::run_sliced(int B, bool two, hipStream_t st,
 }
 
 Tens TsvadModel::trunk_forward(const float* ref, int Bh, int Tf, hipStream_t s, int b0) const {
+  if (wavlm_) {
+    SD_CHECK(b0 == 0, kErrInvalid, "the WavLM trunk runs over the whole batch");
+    if (cfg_.variant == 5) return wavlm_->encode(ref, Bh, Tf, s);   // extract_features(ref_speech)[0] (:1174)
+    // hss[1:] weighted by `weights` as the layers run (:1193-1200), then wavlmproj + wavlmlnorm (:1201-1202)
+    const int D = cfg_.wavlm_embed_dim, rows = Bh * WavlmTrunk::frames(Tf);
+    wavlm_->encode_layers(ref, Bh, Tf, [&](int layer, const float* x, hipStream_t q) {
+      wavlm_layer_mix(acc_, x, mix_w_[layer], layer == 0, (int64_t)rows * D, q);
+    }, s);
+    wavlm_mix_proj_ln(acc_, rows, D, wproj_.w.w, cfg_.bf16, wproj_.beta, wln_g_, wln_b_, cfg_.speaker_embed_dim, z_, s);
+    return Tens{z_, cfg_.bf16};
+  }
   if (ecapa_) return ecapa_->forward(ref, Bh, Tf, s, b0);
   if (redim_) {
     SD_CHECK(b0 == 0, kErrInvalid, "the ReDimNetB2 trunk runs over the whole batch");
@@ -465,6 +545,10 @@ ConvGemmArgs TsvadModel::down_gemm(Tens x, int Bh, int Tf, float* out) const {
   if (ecapa_) return cam_conv1d(x, Bh, Tf, EcapaTrunk::kChannels, down_, 4, 2, 1, Tens{out, false}, SE);
   // ReDimNetB2: the same conv over the unsubsampled (Bh, Tf, 1152) frame-level map
   if (redim_) return cam_conv1d(x, Bh, Tf, RedimTrunk::kChannels, down_, 4, 2, 1, Tens{out, false}, SE);
+  // WavLM: k5 stride-2 pad-2 conv over the (Bh, T, D) encoder output (5) or the (Bh, T, SE) projected map (6)
+  if (wavlm_)
+    return cam_conv1d(x, Bh, WavlmTrunk::frames(Tf), cfg_.variant == 6 ? SE : cfg_.wavlm_embed_dim, down_, 2, 2, 1,
+                      Tens{out, false}, SE);
   // CAM++: k5 stride-2 pad-2 conv, out_nonlinear's BN-ReLU fused as its prologue
   return cam_conv1d(x, Bh, CamTrunk::out_frames(Tf), CamTrunk::kChannels, down_, 2, 2, 1, Tens{out, false}, SE);
 }
@@ -484,8 +568,15 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   SD_CHECK(!single_m_ || force == 0, kErrInvalid,
            "force: a Mamba2 back end cannot run a slice of a reference batch (raise max_batch to forward_batch)");
   // ECAPA and ReDimNetB2 never subsample inside the trunk: any window of at least one frame runs
-  SD_CHECK(Tf >= (cfg_.variant >= 3 ? 1 : 8) && Tf <= cfg_.max_fbank_frames, kErrInvalid,
-           "fbank frames exceed max_fbank_frames");
+  if (waveform()) {
+    SD_CHECK(Tf >= WavlmTrunk::kMinSamples, kErrInvalid, "n_samples must be at least 400");
+    SD_CHECK(Tf <= cfg_.max_samples, kErrInvalid, "n_samples exceeds max_samples");
+    SD_CHECK(Tf % 4 == 0, kErrInvalid, "n_samples must be a multiple of 4 (16-byte window rows)");
+    SD_CHECK(!gemm_x3(), kErrInvalid, "the WavLM speech encoders (variants 5 / 6) do not build bf16x3");
+  } else {
+    SD_CHECK(Tf >= (cfg_.variant >= 3 ? 1 : 8) && Tf <= cfg_.max_fbank_frames, kErrInvalid,
+             "fbank frames exceed max_fbank_frames");
+  }
   raise_if_set();
   const int T3 = mix_frames(Tf);
   check_label_frames(T3, Tl);
@@ -497,7 +588,7 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   // Under the libsdiar kernel timer (bench.py's extra profiled step) the forward stays on one stream, so
   // each kernel's HIP-event time is its own and not shared with the other slice's kernels.
   static const bool one_stream_env = getenv("SDIAR_CAM_ONE_STREAM") != nullptr;
-  const bool two = !(one_stream_env || prof_enabled()) && B >= 384 && !redim_;   // RedimTrunk takes no window slice
+  const bool two = !(one_stream_env || prof_enabled()) && B >= 384 && !redim_ && !wavlm_;   // RedimTrunk / WavlmTrunk take no window slice
   // ---------------- BatchNorm1D's NaN bypass: which windows hold a non-finite input, which reference forwards
   // (groups of forward_batch windows) therefore skip the BatchNorm (from the inputs alone, so first: the window
   // slices below then need nothing from each other until the LSTM)

@@ -8,6 +8,7 @@
 #include "mamba2.h"
 #include "redimnet.h"
 #include "resnet.h"
+#include "wavlm.h"
 
 namespace sd {
 
@@ -17,6 +18,10 @@ struct TsvadConfig {
                               // 3: ecapa_channel_1024_wespeaker + conv k5 stride 4 + transformer (631-654)
                               // 4: ReDimNetB2 on 72-bin fbank + conv k5 stride 4 + transformer
                               //    (egs/magicdata-ramc/ts_vad2/model.py:694-715, 1246-1262, 1296-1309)
+                              // 5: WavLM on the raw waveform (wavlm_layers = select_encoder_layer_nums encoder layers,
+                              //    extract_features(ref_speech)[0]) + conv k5 stride 2 + transformer (:867-889, 1171-1179)
+                              // 6: WavLM_weight_sum with wavlm_fuse_feat_post_norm: every layer's output weighted by
+                              //    `weights`, wavlmproj, wavlmlnorm, the same conv (:890-927, 1180-1204)
   int max_num_speaker = 4;
   int rs_len = 4;
   int max_batch = 64;
@@ -39,6 +44,12 @@ struct TsvadConfig {
   int backend = 0;
   int d_state = 64;
   int expand = 4;
+  // variants 5 / 6: the WavLM geometry (the checkpoint's cfg) and the longest window; ref_speech is (B, n_samples)
+  int wavlm_embed_dim = 0;            // 768 (ffn 3072, 12 heads) or 1024 (4096, 16)
+  int wavlm_layers = 0;               // encoder layers that run (and that the state_dict holds)
+  bool wavlm_layer_norm_mode = false; // extractor_mode "layer_norm"
+  bool wavlm_pre_ln = false;          // layer_norm_first
+  int max_samples = 0;
 };
 
 class TsvadModel : public ModelCore {
@@ -47,7 +58,8 @@ class TsvadModel : public ModelCore {
   // Raises kErrInvalid for a configuration the runner does not build (sd_tsvad_create calls it): with
   // speaker_embed_dim * 2 != embed_dim the reference inserts proj_layer (model.py:212-217), built for variants 0, 2 and 3.
   static void validate(const TsvadConfig& c);
-  // ref_speech (B, T_fb, 80) fbank ((B, T_fb, 72) for variant 4), target_speech (B, NS, speaker_embed_dim), logits out (B, NS, T_lab).
+  // ref_speech (B, T_fb, 80) fbank ((B, T_fb, 72) for variant 4; variants 5 / 6: (B, n_samples) waveform, T_fb carries
+  // n_samples, a multiple of 4 in [400, max_samples]), target_speech (B, NS, speaker_embed_dim), logits out (B, NS, T_lab).
   // forward_batch: windows per reference forward call, the scope of BatchNorm1D's NaN bypass (model.py:161-171),
   // i.e. the batch a NaN window disables speech_down_or_up's / backend_down's BatchNorm for; 0: the whole call.
   // force: the call is part of a larger reference batch that holds a non-finite input elsewhere: bit 0 skips
@@ -106,10 +118,16 @@ class TsvadModel : public ModelCore {
   std::unique_ptr<ResTrunk> res_;   // ResNet34, variant 2
   std::unique_ptr<EcapaTrunk> ecapa_;   // ECAPA-TDNN c1024, variant 3
   std::unique_ptr<RedimTrunk> redim_;   // ReDimNetB2, variant 4
-  int feat_dim() const { return cfg_.variant == 4 ? RedimTrunk::kF : 80; }   // mel bins of ref_speech
+  std::unique_ptr<WavlmTrunk> wavlm_;   // WavLM on the waveform, variants 5 and 6
+  // values per frame of ref_speech: mel bins, or 1 for the waveform variants
+  int feat_dim() const { return wavlm_ ? 1 : cfg_.variant == 4 ? RedimTrunk::kF : 80; }
+  bool waveform() const { return cfg_.variant == 5 || cfg_.variant == 6; }
+  // the longest ref_speech time axis: fbank frames, or samples
+  int max_input() const { return waveform() ? cfg_.max_samples : cfg_.max_fbank_frames; }
   // frames of the speech_down_or_up output for T_fb fbank frames (the conv's stride 2, the upsampler's 2 T', or
   // ECAPA's and ReDimNetB2's stride 4 on the unsubsampled time axis)
   int mix_frames(int Tf) const {
+    if (waveform()) return (WavlmTrunk::frames(Tf) - 1) / 2 + 1;   // WavLM's 50 frames / s through the stride-2 conv
     if (cfg_.variant == 3 || cfg_.variant == 4) return (Tf - 1) / 4 + 1;
     return cfg_.variant == 2 ? 2 * ResTrunk::out_frames(Tf) : (CamTrunk::out_frames(Tf) - 1) / 2 + 1;
   }
@@ -119,6 +137,13 @@ class TsvadModel : public ModelCore {
   // ConvTranspose1d(2560 -> D, k5, stride 2, pad 2, output_padding 1) as ONE k-3 pad-1 conv with 2 D outputs per
   // input frame j, [even phase y[2j] | odd phase y[2j+1]] = two consecutive rows of the (B, 2 T', D) output.
   ConvL down_;
+  // variant 6: `weights` (L), wavlmproj (SE, D) + wavlmlnorm; acc_ (B T, D) fp32 takes the layer-weighted sum as the
+  // layers run, z_ (B T, SE) the projected and normalised map (bf16 in bf16 mode), the conv's A operand
+  std::vector<float> mix_w_;
+  ConvL wproj_;
+  const float *wln_g_ = nullptr, *wln_b_ = nullptr;
+  float* acc_ = nullptr;
+  void* z_ = nullptr;
   BnRelu down_bn_, backend_bn_;   // folded BatchNorms, applied (or bypassed) by the consumers
   int* nonfinite_ = nullptr;      // [win_fbank B | win_ts B | grp_speech B | grp_backend B]
   const float *gsp_w_ = nullptr, *gsp_b_ = nullptr;

@@ -37,22 +37,22 @@ void wavlm_fold_pos_weight(const float* g, const float* v, int D, float* out) {
   for (size_t i = 0; i < n; ++i) out[i] = (float)((double)g[i % kPosTaps] * v[i] / std::sqrt(nrm[i % kPosTaps]));
 }
 
-int WavlmModel::conv_frames(int n, int layer) {
+int WavlmTrunk::conv_frames(int n, int layer) {
   for (int i = 0; i <= layer; ++i) n = n < kConvK[i] ? 0 : (n - kConvK[i]) / kConvS[i] + 1;
   return n;
 }
 
-int WavlmModel::frames(int n_samples) { return conv_frames(n_samples, 6); }
+int WavlmTrunk::frames(int n_samples) { return conv_frames(n_samples, 6); }
 
-void WavlmModel::build() {
+void WavlmTrunk::load(ParamStore& ps_, DeviceArena& arena_, const std::string& pre) {
   const int D = cfg_.embed_dim, F = cfg_.ffn_dim, H = cfg_.heads, Dg = D / kPosGroups;
   const bool bf = cfg_.bf16, lnm = cfg_.layer_norm_mode;
   SD_CHECK((D == 768 && F == 3072 && H == 12) || (D == 1024 && F == 4096 && H == 16), kErrInvalid,
            "WavLM (MI355X backend) builds (embed_dim, ffn_dim, heads) = (768, 3072, 12) or (1024, 4096, 16) only");
   LayerLoader ld{ps_, arena_, bf}, f32{ps_, arena_, false};
-  SD_CHECK(ps_.get("mask_emb").numel() == D, kErrParam, "mask_emb size");   // training-time masking only
+  SD_CHECK(ps_.get(pre + "mask_emb").numel() == D, kErrParam, pre + "mask_emb size");   // training-time masking only
   {
-    const std::string p = "feature_extractor.conv_layers.";
+    const std::string p = pre + "feature_extractor.conv_layers.";
     const HostTensor& w0 = ps_.get(p + "0.0.weight");
     SD_CHECK(w0.shape.size() == 3 && w0.shape[0] == kConvC && w0.shape[1] == 1 && w0.shape[2] == kConvK[0], kErrParam,
              p + "0.0.weight must be (512,1,10)");
@@ -72,16 +72,16 @@ void WavlmModel::build() {
                q + ".0.weight must be (512,512," + std::to_string(kConvK[i]) + ")");
     }
   }
-  SD_CHECK(ps_.get("layer_norm.weight").numel() == kConvC && ps_.get("layer_norm.bias").numel() == kConvC, kErrParam,
-           "layer_norm size");
-  ln_g_ = f32.up("layer_norm.weight");
-  ln_b_ = f32.up("layer_norm.bias");
-  proj_ = ld.linear("post_extract_proj");
-  SD_CHECK(proj_.w.N == D && proj_.w.K == kConvC, kErrParam, "post_extract_proj.weight must be (embed_dim,512)");
+  SD_CHECK(ps_.get(pre + "layer_norm.weight").numel() == kConvC && ps_.get(pre + "layer_norm.bias").numel() == kConvC, kErrParam,
+           pre + "layer_norm size");
+  ln_g_ = f32.up(pre + "layer_norm.weight");
+  ln_b_ = f32.up(pre + "layer_norm.bias");
+  proj_ = ld.linear(pre + "post_extract_proj");
+  SD_CHECK(proj_.w.N == D && proj_.w.K == kConvC, kErrParam, pre + "post_extract_proj.weight must be (embed_dim,512)");
   {
     // weight_norm(dim = 2) of pos_conv (wavlm.py:578-580): w[n, c, tap] = g[tap] v[n, c, tap] / |v[:, :, tap]|, the
     // norm over the output and input channels of each tap; both spellings of the pair
-    const std::string p = "encoder.pos_conv.0.";
+    const std::string p = pre + "encoder.pos_conv.0.";
     const bool old_keys = ps_.has(p + "weight_g");
     const HostTensor& g = ps_.get(p + (old_keys ? "weight_g" : "parametrizations.weight.original0"));
     const HostTensor& v = ps_.get(p + (old_keys ? "weight_v" : "parametrizations.weight.original1"));
@@ -99,7 +99,7 @@ void WavlmModel::build() {
     pos_b_ = f32.up(p + "bias");
   }
   for (int i = 0; i < cfg_.layers; ++i) {
-    const std::string p = "encoder.layers." + std::to_string(i) + ".", a = p + "self_attn.";
+    const std::string p = pre + "encoder.layers." + std::to_string(i) + ".", a = p + "self_attn.";
     Layer L;
     std::vector<float> w, b;
     for (const char* nm : {"q_proj", "k_proj", "v_proj"}) {   // k_proj has a bias, as in F.multi_head_attention_forward
@@ -136,12 +136,16 @@ void WavlmModel::build() {
     }
     layers_.push_back(L);
   }
-  SD_CHECK(ps_.get("encoder.layer_norm.weight").numel() == D && ps_.get("encoder.layer_norm.bias").numel() == D,
-           kErrParam, "encoder.layer_norm size");
-  enc_g_ = f32.up("encoder.layer_norm.weight");
-  enc_b_ = f32.up("encoder.layer_norm.bias");
-  ps_.require_all_used();
+  SD_CHECK(ps_.get(pre + "encoder.layer_norm.weight").numel() == D && ps_.get(pre + "encoder.layer_norm.bias").numel() == D,
+           kErrParam, pre + "encoder.layer_norm size");
+  enc_g_ = f32.up(pre + "encoder.layer_norm.weight");
+  enc_b_ = f32.up(pre + "encoder.layer_norm.bias");
+}
 
+void WavlmTrunk::alloc(DeviceArena& arena_) {
+  const int D = cfg_.embed_dim, F = cfg_.ffn_dim, H = cfg_.heads;
+  const bool bf = cfg_.bf16, lnm = cfg_.layer_norm_mode;
+  auto ws = [&](size_t n) { return static_cast<float*>(arena_.alloc(n * sizeof(float))); };
   max_T_ = frames(cfg_.max_samples);
   SD_CHECK(max_T_ >= 1, kErrInvalid, "max_samples must be at least 400");
   {
@@ -172,7 +176,7 @@ void WavlmModel::build() {
   table_ = ws((size_t)H * (2 * max_T_ - 1));
 }
 
-void WavlmModel::front_end(const float* source, int B, int n, hipStream_t st) {
+void WavlmTrunk::front_end(const float* source, int B, int n, hipStream_t st) {
   const bool bf = cfg_.bf16, lnm = cfg_.layer_norm_mode;
   const int T = frames(n);
   for (int b0 = 0; b0 < B; b0 += kSlice) {
@@ -202,7 +206,7 @@ void WavlmModel::front_end(const float* source, int B, int n, hipStream_t st) {
   }
 }
 
-void WavlmModel::run_layer(const Layer& L, int B, int T, hipStream_t st) {
+void WavlmTrunk::run_layer(const Layer& L, int B, int T, hipStream_t st) {
   const bool bf = cfg_.bf16;
   const int D = cfg_.embed_dim, rows = B * T;
   const Tens qkv{QKV_, bf}, ao{AO_, bf}, t{Y_, bf}, h{H_, bf};
@@ -222,7 +226,7 @@ void WavlmModel::run_layer(const Layer& L, int B, int T, hipStream_t st) {
     ConvGemmArgs p = lin(xa, rows, D, L.fc1, L.b1, h, L.fc1.N);
     p.act = kActGelu;
     conv_gemm(p, bf, st);
-    ffn_down_add_ln(lin(h, rows, L.fc1.N, L.fc2, L.b2, t, D), H_, X_, L.n2g, L.n2b, bf, Yb_, st, true);
+    ffn_down_add_ln(lin(h, rows, L.fc1.N, L.fc2, L.b2, t, D), H_, X_, L.n2g, L.n2b, bf, Yb_, st, cfg_.split_k);
     return;
   }
   // pre-LN (:754-777): X += SA(LN1(X)); X += FFN(LN2(X)); the gate reads the normalised input in fp32
@@ -241,29 +245,37 @@ void WavlmModel::run_layer(const Layer& L, int B, int T, hipStream_t st) {
   wavlm_add(X_, Y_, bf, (int64_t)rows * D, st);
 }
 
-void WavlmModel::forward(const float* source, int B, int n_samples, int output_layer, float* x_out,
-                         float* features_out, float* layers_out, hipStream_t st) {
-  require_finalized();
+void WavlmTrunk::check_input(int B, int n_samples) const {
   SD_CHECK(B >= 1 && B <= cfg_.max_batch, kErrInvalid, "batch exceeds max_batch");
   SD_CHECK(n_samples >= kMinSamples, kErrInvalid, "n_samples must be at least 400");
   SD_CHECK(n_samples <= cfg_.max_samples, kErrInvalid, "n_samples exceeds max_samples");
-  SD_CHECK(output_layer >= 0 && output_layer <= cfg_.layers, kErrInvalid,
-           "output_layer must be 0 (all layers) or 1..encoder_layers");
-  SD_CHECK(!layers_out || output_layer >= 1, kErrInvalid, "layers_out needs output_layer >= 1");
+}
+
+void WavlmTrunk::stem(const float* source, int B, int n_samples, hipStream_t st) {
   const bool bf = cfg_.bf16;
   const int D = cfg_.embed_dim, T = frames(n_samples), rows = B * T;
-  const size_t nx = (size_t)rows * D;
   front_end(source, B, n_samples, st);
   // features = post_extract_proj(LayerNorm(conv features)) (wavlm.py:377-384)
   layernorm(feat_, rows, kConvC, kConvC, ln_g_, ln_b_, 1e-5f, featn_, kConvC, bf, st);
   conv_gemm(lin(Tens{featn_, bf}, rows, kConvC, proj_.w, proj_.beta, Tens{F_, false}, D), bf, st);
+}
+
+void WavlmTrunk::forward(const float* source, int B, int n_samples, int output_layer, float* x_out,
+                         float* features_out, float* layers_out, hipStream_t st) {
+  check_input(B, n_samples);
+  SD_CHECK(output_layer >= 0 && output_layer <= cfg_.layers, kErrInvalid,
+           "output_layer must be 0 (all layers) or 1..encoder_layers");
+  SD_CHECK(!layers_out || output_layer >= 1, kErrInvalid, "layers_out needs output_layer >= 1");
+  const int D = cfg_.embed_dim, T = frames(n_samples), rows = B * T;
+  const size_t nx = (size_t)rows * D;
+  stem(source, B, n_samples, st);
   if (features_out) copy_async(features_out, F_, nx, st);
   if (!x_out && !layers_out) return;
   // x = x + GELU(pos_conv(x)); post-LN mode normalises right after (wavlm.py:635-640)
   if (cfg_.pre_ln) {
-    wavlm_pos_conv(F_, B, T, D, pos_w_.w, bf, pos_b_, X_, st);
+    wavlm_pos_conv(F_, B, T, D, pos_w_.w, cfg_.bf16, pos_b_, X_, st);
   } else {
-    wavlm_pos_conv(F_, B, T, D, pos_w_.w, bf, pos_b_, Y_, st);
+    wavlm_pos_conv(F_, B, T, D, pos_w_.w, cfg_.bf16, pos_b_, Y_, st);
     layernorm(Y_, rows, D, D, enc_g_, enc_b_, 1e-5f, X_, D, false, st, Yb_);
   }
   wavlm_bias_table(rel_emb_, bmap_, max_T_ - 1, T, cfg_.heads, table_, st);
@@ -279,6 +291,35 @@ void WavlmModel::forward(const float* source, int B, int n_samples, int output_l
     layernorm(X_, rows, D, D, enc_g_, enc_b_, 1e-5f, x_out, D, false, st);
   else
     copy_async(x_out, X_, nx, st);
+}
+
+void WavlmTrunk::encode_layers(const float* source, int B, int n_samples, const LayerSink& sink, hipStream_t st) {
+  check_input(B, n_samples);
+  const int D = cfg_.embed_dim, T = frames(n_samples), rows = B * T;
+  stem(source, B, n_samples, st);
+  if (cfg_.pre_ln) {
+    wavlm_pos_conv(F_, B, T, D, pos_w_.w, cfg_.bf16, pos_b_, X_, st);
+  } else {
+    wavlm_pos_conv(F_, B, T, D, pos_w_.w, cfg_.bf16, pos_b_, Y_, st);
+    layernorm(Y_, rows, D, D, enc_g_, enc_b_, 1e-5f, X_, D, false, st, Yb_);
+  }
+  wavlm_bias_table(rel_emb_, bmap_, max_T_ - 1, T, cfg_.heads, table_, st);
+  for (int i = 0; i < cfg_.layers; ++i) {
+    run_layer(layers_[i], B, T, st);
+    if (sink) sink(i, X_, st);
+  }
+}
+
+Tens WavlmTrunk::encode(const float* source, int B, int n_samples, hipStream_t st) {
+  encode_layers(source, B, n_samples, nullptr, st);
+  const bool bf = cfg_.bf16;
+  const int D = cfg_.embed_dim, rows = B * frames(n_samples);
+  if (cfg_.pre_ln) {   // the final encoder.layer_norm (wavlm.py:623-624) into the layers' scratch
+    layernorm(X_, rows, D, D, enc_g_, enc_b_, 1e-5f, Y_, D, bf, st);
+    return Tens{Y_, bf};
+  }
+  // post-LN: the last layer's LayerNorm left bf16(X) beside X in bf16 mode
+  return bf ? Tens{Yb_, true} : Tens{X_, false};
 }
 
 }  // namespace sd

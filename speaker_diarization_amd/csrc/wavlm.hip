@@ -1,8 +1,12 @@
 // WavLM kernels for gfx950 (declarations and contracts in kernels.h): the waveform conv layer with its norm, the
-// grouped 128-tap positional conv, the relative-position bias table and self-attention with the gated bias.
+// grouped 128-tap positional conv, the relative-position bias table and self-attention with the gated bias; for TS-VAD's
+// WavLM speech encoders the layer-weighted sum, its projection + LayerNorm and the waveform window gather.
+#include <algorithm>
 #include <cmath>
 
 #include "kernels.h"
+#include "launch.h"
+#include "prof.h"
 
 namespace sd {
 
@@ -391,7 +395,182 @@ __global__ __launch_bounds__(256) void wavlm_attn_kernel(WavlmAttnArgs a) {
   }
 }
 
+// ---- TS-VAD's WavLM_weight_sum head and the waveform window gather
+__global__ __launch_bounds__(256) void wavlm_layer_mix_kernel(float4* __restrict__ acc, const float4* __restrict__ x,
+                                                              float w, int first, int64_t n4) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const float4 v = x[i];
+    float4 a;
+    if (first) {
+      a = float4{w * v.x, w * v.y, w * v.z, w * v.w};
+    } else {
+      a = acc[i];
+      a = float4{fmaf(w, v.x, a.x), fmaf(w, v.y, a.y), fmaf(w, v.z, a.z), fmaf(w, v.w, a.w)};
+    }
+    acc[i] = a;
+  }
+}
+
+constexpr int kMixRows = 16;   // rows per workgroup of wavlm_mix_proj_ln
+
+// 16 rows x SE columns per workgroup, wave w the columns [w SE / 4, (w + 1) SE / 4) as SE / 64 MFMA tiles.  Fragment
+// layout as in wavlm_pos_conv_kernel: lane (lrow, lk) holds A row lrow / B column lrow at the k slots of lk, and
+// accumulator element r is (row 4 lk + r, column lrow).  Rows past `rows` read row rows - 1 and are not stored.
+template <bool BF, int SE>
+__global__ __launch_bounds__(256) void wavlm_mix_proj_ln_kernel(const float* __restrict__ acc, int rows, int D,
+                                                                const act_t<BF>* __restrict__ wt,
+                                                                const float* __restrict__ bias,
+                                                                const float* __restrict__ g,
+                                                                const float* __restrict__ beta,
+                                                                act_t<BF>* __restrict__ out) {
+  using lt = act_t<BF>;
+  constexpr int NT = SE / 64;
+  __shared__ float red[2][4][kMixRows];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lrow = lane & 15, lk = lane >> 4;
+  const int r0 = blockIdx.x * kMixRows;
+  const float* arow = acc + (int64_t)min(r0 + lrow, rows - 1) * D;
+  const int col0 = wave * (SE / 4);
+  const lt* wrow = wt + (int64_t)(col0 + lrow) * D;
+  floatx4 c[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) c[nt] = floatx4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (BF) {
+#pragma unroll 2
+    for (int ks = 0; ks < D / 32; ++ks) {
+      const int k = ks * 32 + lk * 8;
+      const float4 a0 = *reinterpret_cast<const float4*>(arow + k);
+      const float4 a1 = *reinterpret_cast<const float4*>(arow + k + 4);
+      const u32x4_t pk = {pack_bf16x2(a0.x, a0.y), pack_bf16x2(a0.z, a0.w), pack_bf16x2(a1.x, a1.y),
+                          pack_bf16x2(a1.z, a1.w)};
+      const bf16x8 a = __builtin_bit_cast(bf16x8, pk);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const bf16x8 w8 = *reinterpret_cast<const bf16x8*>(wrow + (int64_t)nt * 16 * D + k);
+        c[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, w8, c[nt], 0, 0, 0);
+      }
+    }
+  } else {
+    // 16 k per step as four MFMAs of 4 (slot lk of MFMA j takes k = 16 s + 4 lk + j in A and B alike)
+#pragma unroll 2
+    for (int s = 0; s < D / 16; ++s) {
+      const int k = s * 16 + lk * 4;
+      const floatx4 a = *reinterpret_cast<const floatx4*>(arow + k);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const floatx4 w4 = *reinterpret_cast<const floatx4*>(wrow + (int64_t)nt * 16 * D + k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], w4[j], c[nt], 0, 0, 0);
+      }
+    }
+  }
+  // + bias, then LayerNorm over the SE columns of each row: the sum over this wave's columns (NT tiles x the 16 lanes
+  // of a lk group), then over the four waves through LDS; mean first, then the centred squares
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const float bv = bias[col0 + nt * 16 + lrow];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      c[nt][r] += bv;
+      s[r] += c[nt][r];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) s[r] += __shfl_xor(s[r], o, 64);
+    if (lrow == 0) red[0][wave][lk * 4 + r] = s[r];
+  }
+  __syncthreads();
+  float mean[4], q[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = lk * 4 + r;
+    mean[r] = (red[0][0][row] + red[0][1][row] + red[0][2][row] + red[0][3][row]) * (1.f / SE);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      c[nt][r] -= mean[r];
+      q[r] = fmaf(c[nt][r], c[nt][r], q[r]);
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) q[r] += __shfl_xor(q[r], o, 64);
+    if (lrow == 0) red[1][wave][row] = q[r];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = lk * 4 + r;
+    if (r0 + row >= rows) continue;
+    const float rstd = rsqrtf((red[1][0][row] + red[1][1][row] + red[1][2][row] + red[1][3][row]) * (1.f / SE) + 1e-5f);
+    lt* o = out + (int64_t)(r0 + row) * SE;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const int col = col0 + nt * 16 + lrow;
+      st_act(o, col, fmaf(c[nt][r] * rstd, g[col], beta[col]));
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void window_wave_kernel(const float* __restrict__ wav, int64_t n_total,
+                                                          const int* __restrict__ win_start,
+                                                          const int* __restrict__ win_n, int n_out,
+                                                          float* __restrict__ out) {
+  const int w = blockIdx.y;
+  const int64_t start = win_start[w];
+  const int n = win_n[w];
+  for (int j = blockIdx.x * 256 + threadIdx.x; j < n_out; j += gridDim.x * 256) {
+    const int64_t i = start + j;
+    out[(int64_t)w * n_out + j] = (j < n && i >= 0 && i < n_total) ? wav[i] : 0.f;
+  }
+}
+
 }  // namespace
+
+void wavlm_layer_mix(float* acc, const float* x, float w, bool first, int64_t n, hipStream_t st) {
+  SD_CHECK(acc && x && acc != x && n >= 4 && n % 4 == 0, kErrInvalid, "wavlm_layer_mix: n must be a positive multiple of 4");
+  SD_CHECK(((reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(x)) & 15) == 0, kErrInvalid,
+           "wavlm_layer_mix: pointers must be 16-byte aligned");
+  const int64_t n4 = n / 4;
+  const int64_t blocks = std::min<int64_t>((n4 + 255) / 256, (int64_t)device_cus() * 8);
+  ProfScope prof("wavlm_layer_mix", 2.0 * n, (first ? 8.0 : 12.0) * n, st);
+  hipLaunchKernelGGL(wavlm_layer_mix_kernel, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<float4*>(acc),
+                     reinterpret_cast<const float4*>(x), w, first ? 1 : 0, n4);
+  SD_LAUNCH_CHECK();
+}
+
+void wavlm_mix_proj_ln(const float* acc, int rows, int D, const void* wt, bool bf16, const float* bias, const float* g,
+                       const float* beta, int SE, void* out, hipStream_t st) {
+  SD_CHECK(acc && wt && bias && g && beta && out && rows >= 1, kErrInvalid, "wavlm_mix_proj_ln: bad argument");
+  SD_CHECK(SE == 192 || SE == 256, kErrInvalid, "wavlm_mix_proj_ln: speaker_embed_dim must be 192 or 256");
+  SD_CHECK(D >= 32 && D % 32 == 0, kErrInvalid, "wavlm_mix_proj_ln: D must be a multiple of 32");
+  SD_CHECK(((reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(wt)) & 15) == 0, kErrInvalid,
+           "wavlm_mix_proj_ln: pointers must be 16-byte aligned");
+  const dim3 grid(cdiv(rows, kMixRows));
+  ProfScope prof("wavlm_mix_proj_ln", 2.0 * rows * SE * (double)D,
+                 4.0 * rows * D + (bf16 ? 2.0 : 4.0) * ((double)SE * D + (double)rows * SE), st);
+  auto go = [&](auto kernel, auto* w, auto* o) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, acc, rows, D, w, bias, g, beta, o);
+  };
+  if (bf16) {
+    auto* w = static_cast<const uint16_t*>(wt);
+    auto* o = static_cast<uint16_t*>(out);
+    if (SE == 192) go(wavlm_mix_proj_ln_kernel<true, 192>, w, o); else go(wavlm_mix_proj_ln_kernel<true, 256>, w, o);
+  } else {
+    auto* w = static_cast<const float*>(wt);
+    auto* o = static_cast<float*>(out);
+    if (SE == 192) go(wavlm_mix_proj_ln_kernel<false, 192>, w, o); else go(wavlm_mix_proj_ln_kernel<false, 256>, w, o);
+  }
+  SD_LAUNCH_CHECK();
+}
+
+void window_wave(const float* wav, int64_t n_total, const int* win_start, const int* win_n, int n_win, int n_out,
+                 float* out, hipStream_t st) {
+  SD_CHECK(wav && win_start && win_n && out && n_total >= 0 && n_win >= 1 && n_win <= 65535 && n_out >= 1, kErrInvalid,
+           "window_wave: bad argument");
+  hipLaunchKernelGGL(window_wave_kernel, dim3(std::min(cdiv(n_out, 256), 64), n_win), dim3(256), 0, st, wav, n_total,
+                     win_start, win_n, n_out, out);
+  SD_LAUNCH_CHECK();
+}
 
 int wavlm_l0_parts(int T0) { return cdiv(T0, kL0Block) * 4; }
 

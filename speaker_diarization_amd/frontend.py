@@ -86,3 +86,15 @@ def window_cmn(feats, win_start, win_n, T_out: int, out=None):
     _lib.call("sd_window_cmn", _lib.ptr(feats), n_mels, _lib.ptr(win_start), _lib.ptr(win_n), n_win, T_out,
               _lib.ptr(out), _lib.stream_ptr(feats.device))
     return out
+
+
+def window_wave(wav, win_start, win_n, n_out: int, out=None):
+    """wav (n,) CUDA float32; win_start/win_n int32 CUDA (n_win) -> (n_win, n_out) raw-waveform windows, zero past
+    each window's win_n samples (the waveform-input speech encoders: no features, no mean removal)."""
+    import torch
+    n_win = win_start.numel()
+    if out is None:
+        out = torch.empty(n_win, n_out, device=wav.device, dtype=torch.float32)
+    _lib.call("sd_window_wave", _lib.ptr(wav), wav.numel(), _lib.ptr(win_start), _lib.ptr(win_n), n_win, n_out,
+              _lib.ptr(out), _lib.stream_ptr(wav.device))
+    return out

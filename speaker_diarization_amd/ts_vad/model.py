@@ -39,13 +39,23 @@ class TSVADModel(_lib.Handle):
         self.max_num_speaker = self.cfg.max_num_speaker
         self.max_fbank = fbank_frames(self.cfg.rs_len, self.cfg.sample_rate)
         c = self.cfg
+        wav = {}
+        if c.variant in (5, 6):
+            # the WavLM speech encoders read the raw waveform: the geometry of wavlm_cfg and the longest window
+            if precision == "bf16x3":
+                raise ValueError("the WavLM speech encoders do not build bf16x3 (the WavLM trunk runs in fp32 or bf16)")
+            w = c.effective_wavlm_cfg()
+            self.max_samples = c.rs_len * c.sample_rate
+            wav = dict(wavlm_embed_dim=w.encoder_embed_dim, wavlm_layers=w.encoder_layers,
+                       wavlm_layer_norm_mode=int(w.extractor_mode == "layer_norm"),
+                       wavlm_pre_ln=int(bool(w.layer_norm_first)), max_samples=self.max_samples)
         self._create(_lib.TsvadConfig(
             variant=c.variant, max_num_speaker=c.max_num_speaker, rs_len=c.rs_len, max_batch=self.max_batch,
             max_fbank_frames=self.max_fbank, precision=_lib.PRECISION[precision],
             num_transformer_layer=c.num_transformer_layer, num_attention_head=c.num_attention_head,
             transformer_embed_dim=c.transformer_embed_dim,
             transformer_ffn_embed_dim=c.transformer_ffn_embed_dim, speaker_embed_dim=c.speaker_embed_dim,
-            backend=c.backend, d_state=c.d_state if c.backend else 0, expand=c.expand if c.backend else 0))
+            backend=c.backend, d_state=c.d_state if c.backend else 0, expand=c.expand if c.backend else 0, **wav))
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Strict load (missing/unexpected keys raise RuntimeError like torch)."""
@@ -70,7 +80,8 @@ class TSVADModel(_lib.Handle):
     # ------------------------------------------------------------------ forward
     def forward(self, ref_speech, target_speech, labels, num_updates: int = 0, out=None, check: bool = True,
                 forward_batch: int = 0, _force: int = 0):
-        """ref_speech (B, T_fb, 80) ((B, T_fb, 72) with the ReDimNetB2 speech encoder), target_speech (B, NS, speaker_embed_dim), labels (B, NS, T) (only
+        """ref_speech (B, T_fb, 80) ((B, T_fb, 72) with the ReDimNetB2 speech encoder; the raw waveform (B, n_samples),
+        400 <= n_samples <= rs_len * sample_rate and a multiple of 4, with the WavLM ones), target_speech (B, NS, speaker_embed_dim), labels (B, NS, T) (only
         labels.size(-1) is read, model.py:681/770) -> logits (B, NS, T).  check: wait for the
         stream and raise RuntimeError in this call if the BiLSTM's persistent recurrence lost
         co-residency (its logits are NaN); check=False defers that to status().
@@ -84,9 +95,16 @@ class TSVADModel(_lib.Handle):
         reference scans along the windows of each forward call (sdiar.h, sd_tsvad_config.backend), so the logits
         depend on which windows share a group and in which order; a group wider than max_batch is refused."""
         import torch
-        B, T_fb, F = ref_speech.shape
         T_lab = labels if isinstance(labels, int) else labels.size(-1)
-        assert F == self.cfg.n_mels, f"{self.cfg.speech_encoder_type} expects {self.cfg.n_mels}-dim fbank"
+        if self.cfg.waveform_input:
+            # the WavLM speech encoders: ref_speech (B, n_samples) raw waveform, n_samples goes where T_fb does
+            if ref_speech.dim() != 2:
+                raise ValueError(f"{self.cfg.speech_encoder_type} expects the raw waveform (B, n_samples), got "
+                                 f"{tuple(ref_speech.shape)}")
+            B, T_fb = ref_speech.shape
+        else:
+            B, T_fb, F = ref_speech.shape
+            assert F == self.cfg.n_mels, f"{self.cfg.speech_encoder_type} expects {self.cfg.n_mels}-dim fbank"
         ref = ref_speech.to(self.device, torch.float32).contiguous()
         ts = target_speech.to(self.device, torch.float32).contiguous()
         assert ts.shape == (B, self.max_num_speaker, self.cfg.speaker_embed_dim)

@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib
-from ..frontend import kaldi_fbank, window_cmn
+from ..frontend import kaldi_fbank, window_cmn, window_wave
 from .model import TSVADModel
 from .windows import WindowPlan, plan_windows, shard_batches
 
@@ -89,6 +89,8 @@ class TSVADPipeline:
         # every host-side step (plan slices, device tables, the per-batch target-speaker block) comes before the
         # first launch, so the fbank -> window CMN -> forward launches reach the GPU back to back (round 4's
         # trace: 0.59 ms of idle GPU between the fbank and the first window CMN)
+        if getattr(self.cfg, "waveform_input", False):
+            return self._wave_logits(wav, ts, plan, w0, w1, out, check)
         spl = plan.samples_per_label
         s0 = int(plan.starts[w0]) * spl
         s1 = min(wav.numel(), int(plan.ends[w1 - 1]) * spl)
@@ -110,6 +112,30 @@ class TSVADPipeline:
             self._check()
         return out
 
+    def _wave_logits(self, wav, ts, plan: WindowPlan, w0: int, w1: int, out, check: bool):
+        """window_logits for a waveform-input model (the WavLM speech encoders): no fbank and no CMN, each device
+        batch gathers its windows' samples zero-padded to the batch's longest (ts_vad_dataset.py:693-707)."""
+        dev = self.model.device
+        NS, chunk = self.model.max_num_speaker, plan.chunk
+        s0 = int(plan.wave_start[w0])
+        s1 = min(wav.numel(), int(plan.ends[w1 - 1]) * plan.samples_per_label)
+        wstart = _plan_i32(plan, "wstart", plan.wave_start[w0:w1] - s0, dev, w0, w1)
+        wn = _plan_i32(plan, "wn", plan.wave_n[w0:w1], dev, w0, w1)
+        batches = self.device_batches(plan, w0, w1)
+        ts_all = _ts_block(ts, dev, NS, max(b1 - b0 for b0, b1, _, _ in batches))
+        src = wav[s0:s1]
+        for b0, b1, n_out, T_lab in batches:
+            ref = window_wave(src, wstart[b0 - w0:b1 - w0], wn[b0 - w0:b1 - w0], n_out)
+            dst = out[b0 - w0:b1 - w0]
+            if T_lab == chunk:
+                self.model.forward(ref, ts_all[: b1 - b0], T_lab, out=dst, check=False, **self._fwd_kw)
+            else:
+                dst[:, :, :T_lab] = self.model.forward(ref, ts_all[: b1 - b0], T_lab, check=False, **self._fwd_kw)
+                dst[:, :, T_lab:] = 0.0
+        if check:
+            self._check()
+        return out
+
     def _check(self):
         status = getattr(self.model, "status", None)
         if status is not None:
@@ -120,19 +146,20 @@ class TSVADPipeline:
         ts_vad_dataset.py:664-701) of [w0, w1); consecutive batches with the same
         padded shape are fused into one device launch of up to model.max_batch
         windows — identical inputs per window, fewer and larger kernels."""
-        key = ("_batches", self.batch_size, self.model.max_batch, w0, w1)
+        wave = getattr(self.cfg, "waveform_input", False)   # group by (max samples, max labels) instead of fbank frames
+        key = ("_batches", self.batch_size, self.model.max_batch, w0, w1, wave)
         hit = plan.__dict__.get(key)
         if hit is not None:
             return list(hit)
         groups = []
         for b0 in range(w0, w1, self.batch_size):
             b1 = min(w1, b0 + self.batch_size)
-            key = (int(plan.fbank_n[b0:b1].max()), int(plan.lens[b0:b1].max()))
+            key = (int((plan.wave_n if wave else plan.fbank_n)[b0:b1].max()), int(plan.lens[b0:b1].max()))
             if groups and groups[-1][2:] == key and b1 - groups[-1][0] <= self.model.max_batch:
                 groups[-1] = (groups[-1][0], b1) + key
             else:
                 groups.append((b0, b1) + key)
-        plan.__dict__[("_batches", self.batch_size, self.model.max_batch, w0, w1)] = tuple(groups)
+        plan.__dict__[("_batches", self.batch_size, self.model.max_batch, w0, w1, wave)] = tuple(groups)
         return groups
 
     @staticmethod

@@ -57,6 +57,17 @@ class WindowPlan:
             self.__dict__["_fbank_n"] = n
         return n
 
+    @property
+    def wave_start(self) -> np.ndarray:
+        """First sample of each window (waveform-input speech encoders)."""
+        return self.starts * self.samples_per_label
+
+    @property
+    def wave_n(self) -> np.ndarray:
+        """Samples of each window: with waveform input the dataset extracts no features (ts_vad_dataset.py:185-188,
+        759-761) and the collater zero-pads a batch's windows to its longest (:693-707)."""
+        return self.lens * self.samples_per_label
+
     def batches(self, batch_size: int) -> List[Tuple[int, int]]:
         """Consecutive windows in dataset order (DataLoader shuffle=False, infer.py:232-238)."""
         return [(s, min(self.n_win, s + batch_size)) for s in range(0, self.n_win, batch_size)]
