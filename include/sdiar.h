@@ -786,6 +786,59 @@ int sd_op_linear(const float* x, int M, int K, const float* w, const float* b, i
 int sd_op_gemm_bf16(const void* x, int M, int K, int lda, int a_coff, const float* w, int N,
                     const float* pre_scale, const float* pre_shift, const float* alpha, const float* beta,
                     int act, void* out, int ldo, void* stream);
+/* One conv_gemm call with every option of its argument struct (kernels.h ConvGemmArgs), through the production
+ * dispatch: which kernel runs follows from the arguments alone, as in the models (tests/test_gpu_gemm_paths.py).
+ *   A: channel-last activations, element (b, h, w, c) at A[((b*H + h)*W + w)*lda + a_coff + c], fp32 or bf16 bits
+ *      (a_bf16); a_tiled: in the row programs' fragment layout (lda == Cin, rows % 16 == 0).
+ *   w: fp32 (N, Cin, kh, kw) in torch order; packed here (rounded to bf16 at precision 1; with glu the rows are
+ *      [N/2 values | N/2 gates], as are alpha / beta, and all are interleaved here in groups of 16).
+ *   precision: 0 exact fp32, 1 bf16 MFMA, 2 bf16x3 (0 and 2 take fp32 tensors).
+ *   x = acc * alpha[n] + beta[n] + res[m * res_ld + n]; x = act(x); x = x * post_scale[n] + post_shift[n];
+ *   x *= gate[(b * gate_nseg + wo / gate_seg) * N + n]; out[b*o_sb + ho*o_sh + wo*o_sw + n*o_sn] (fp32 or bf16 bits).
+ *   pre_scale / pre_shift [Cin]: a' = relu(a * s + h) on load (padding stays 0).  act: 0 none, 1 relu, 2 sigmoid,
+ *   3 silu, 4 clamp to [0, 20], 5 erf GELU, 6 tanh GELU.  glu: out channel c = value_c * sigmoid(gate_c), N / 2 wide.
+ *   ln_* / pro_* / kv_*: the prologues and the K-V epilogue of the <= 16-row kernel, as documented in kernels.h.
+ *   ksplit_out (device int, nullable): receives gemm_splitk_count; above 1 the product is written as that many fp32
+ *   (M, N) slabs to `slabs` (slab_cap of them allocated) instead of `out`, beta in slab 0 only.
+ * Every pointer is a device pointer or NULL.  Synchronises `stream` when ksplit_out or glu is set. */
+typedef struct sd_gemm_op {
+  int precision;
+  const void* A;
+  int a_bf16, a_tiled;
+  int B, H, W, Cin, lda, a_coff;
+  int kh, kw, sh, sw, ph, pw, dh, dw;
+  const float* w;
+  int N;
+  const float *pre_scale, *pre_shift, *alpha, *beta;
+  const void* res;
+  int res_bf16, res_ld;
+  int act;
+  const float *post_scale, *post_shift;
+  const float* gate;
+  int gate_seg, gate_nseg;
+  void* out;
+  int out_bf16;
+  int64_t o_sb, o_sh, o_sw, o_sn;
+  int glu;
+  const float* ln_x;
+  const void* ln_t;
+  int ln_t_bf16;
+  const float *ln_g, *ln_b;
+  float ln_eps;
+  float* ln_out;
+  int pro_mode;
+  const float* pro_p;
+  int pro_C, pro_pad;
+  const int *pro_cursor, *pro_nvalid;
+  void* kv_out;
+  const int* kv_cursor;
+  int kv_mult, kv_col0;
+  int64_t kv_ld;
+  int* ksplit_out;
+  float* slabs;
+  int slab_cap;
+} sd_gemm_op;
+int sd_op_conv_gemm(const sd_gemm_op* op, void* stream);
 /* One CAM++ dense layer, bf16 (CAMDenseTDNNLayer + CAMLayer, egs/alimeeting/ts_vad2/cam_pplus_wespeaker.py:
  * 79-168) as the TS-VAD / embedding trunk runs it (cam_dense.hip): x bf16 bits (B, T, ld), input channels
  * [0, cin); out: bf16 bits at x's channels [cin, cin + 32) (out may alias x + cin).  s1/h1: nonlinear1

@@ -198,7 +198,34 @@ class RowprogOp(ctypes.Structure):
     ]
 
 
+class GemmOp(ctypes.Structure):
+    """sd_gemm_op (include/sdiar.h): one conv_gemm call, every pointer a device pointer or None."""
+    _fields_ = [
+        ("precision", c_int),
+        ("A", c_void_p), ("a_bf16", c_int), ("a_tiled", c_int),
+        ("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("lda", c_int), ("a_coff", c_int),
+        ("kh", c_int), ("kw", c_int), ("sh", c_int), ("sw", c_int), ("ph", c_int), ("pw", c_int), ("dh", c_int),
+        ("dw", c_int),
+        ("w", c_void_p), ("N", c_int),
+        ("pre_scale", c_void_p), ("pre_shift", c_void_p), ("alpha", c_void_p), ("beta", c_void_p),
+        ("res", c_void_p), ("res_bf16", c_int), ("res_ld", c_int),
+        ("act", c_int),
+        ("post_scale", c_void_p), ("post_shift", c_void_p),
+        ("gate", c_void_p), ("gate_seg", c_int), ("gate_nseg", c_int),
+        ("out", c_void_p), ("out_bf16", c_int),
+        ("o_sb", c_int64), ("o_sh", c_int64), ("o_sw", c_int64), ("o_sn", c_int64),
+        ("glu", c_int),
+        ("ln_x", c_void_p), ("ln_t", c_void_p), ("ln_t_bf16", c_int), ("ln_g", c_void_p), ("ln_b", c_void_p),
+        ("ln_eps", ctypes.c_float), ("ln_out", c_void_p),
+        ("pro_mode", c_int), ("pro_p", c_void_p), ("pro_C", c_int), ("pro_pad", c_int),
+        ("pro_cursor", c_void_p), ("pro_nvalid", c_void_p),
+        ("kv_out", c_void_p), ("kv_cursor", c_void_p), ("kv_mult", c_int), ("kv_col0", c_int), ("kv_ld", c_int64),
+        ("ksplit_out", c_void_p), ("slabs", c_void_p), ("slab_cap", c_int),
+    ]
+
+
 _SIGS = {
+    "sd_op_conv_gemm": (c_int, [POINTER(GemmOp), c_void_p]),
     "sd_last_error": (c_char_p, []),
     "sd_version": (c_int, []),
     "sd_prof_enable": (None, [c_int]),

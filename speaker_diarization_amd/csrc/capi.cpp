@@ -1104,6 +1104,93 @@ int sd_op_gemm_bf16(const void* x, int M, int K, int lda, int a_coff, const floa
   });
 }
 
+int sd_op_conv_gemm(const sd_gemm_op* op, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(op, sd::kErrInvalid, "conv_gemm op: null argument");
+    SD_CHECK(op->precision >= 0 && op->precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
+    SD_CHECK(op->w && op->N > 0 && op->B > 0 && op->H > 0 && op->W > 0 && op->Cin > 0, sd::kErrInvalid,
+             "conv_gemm op: bad shape");
+    SD_CHECK(op->kh > 0 && op->kw > 0 && op->sh > 0 && op->sw > 0 && op->dh > 0 && op->dw > 0 && op->ph >= 0 &&
+                 op->pw >= 0,
+             sd::kErrInvalid, "conv_gemm op: bad conv geometry");
+    const int Ho = (op->H + 2 * op->ph - op->dh * (op->kh - 1) - 1) / op->sh + 1;
+    const int Wo = (op->W + 2 * op->pw - op->dw * (op->kw - 1) - 1) / op->sw + 1;
+    SD_CHECK(Ho > 0 && Wo > 0, sd::kErrInvalid, "conv_gemm op: empty output");
+    const bool prologue_rows = op->ln_g || op->pro_mode != 0;   // the A rows come from ln_x
+    SD_CHECK(op->A || prologue_rows, sd::kErrInvalid, "conv_gemm op: no A");
+    SD_CHECK(op->a_coff >= 0 && op->lda >= op->a_coff + op->Cin, sd::kErrInvalid, "conv_gemm op: lda < a_coff + Cin");
+    SD_CHECK((op->pre_scale == nullptr) == (op->pre_shift == nullptr), sd::kErrInvalid,
+             "conv_gemm op: pre_scale and pre_shift come together");
+    SD_CHECK(!op->res || op->res_ld >= op->N, sd::kErrInvalid, "conv_gemm op: res_ld < N");
+    SD_CHECK(!op->gate || (op->gate_seg > 0 && op->gate_nseg > 0 && (Wo - 1) / op->gate_seg < op->gate_nseg),
+             sd::kErrInvalid, "conv_gemm op: gate segments do not cover the output");
+    SD_CHECK(!op->glu || op->N % 32 == 0, sd::kErrInvalid, "conv_gemm op: GLU needs N % 32 == 0");
+    SD_CHECK(op->ksplit_out ? op->slabs != nullptr : op->out != nullptr, sd::kErrInvalid, "conv_gemm op: no output");
+    const bool bf = op->precision == 1;
+    const int taps = op->kh * op->kw, K = taps * op->Cin;
+    // GLU: rows [0, N/2) are the values and [N/2, N) their gates in torch order; the kernels read 32-row groups
+    // (glu_interleave_row), alpha and beta with them, as the encoder packs its pointwise_conv1
+    Scratch perm(op->glu ? (size_t)op->N * K * sizeof(float) : 0, st);
+    Scratch ab(op->glu ? (size_t)2 * op->N * sizeof(float) : 0, st);
+    const float *w = op->w, *alpha = op->alpha, *beta = op->beta;
+    if (op->glu) {
+      for (int r = 0; r < op->N; ++r)
+        SD_HIP(hipMemcpyAsync(static_cast<float*>(perm.p) + (size_t)sd::glu_interleave_row(r, op->N / 2) * K,
+                              op->w + (size_t)r * K, (size_t)K * sizeof(float), hipMemcpyDeviceToDevice, st));
+      w = static_cast<const float*>(perm.p);
+      SD_HIP(hipStreamSynchronize(st));
+      std::vector<float> src(op->N), dst(op->N);
+      int slot = 0;
+      for (const float** v : {&alpha, &beta}) {
+        if (!*v) continue;
+        SD_HIP(hipMemcpy(src.data(), *v, op->N * sizeof(float), hipMemcpyDeviceToHost));
+        for (int r = 0; r < op->N; ++r) dst[sd::glu_interleave_row(r, op->N / 2)] = src[r];
+        float* d = static_cast<float*>(ab.p) + (size_t)slot++ * op->N;
+        SD_HIP(hipMemcpy(d, dst.data(), op->N * sizeof(float), hipMemcpyHostToDevice));
+        *v = d;
+      }
+    }
+    PackedScratch wt(w, op->N, op->Cin, taps, bf, st);
+    sd::ConvGemmArgs p;
+    p.A = op->A; p.a_bf16 = op->a_bf16 != 0; p.a_tiled = op->a_tiled;
+    p.B = op->B; p.H = op->H; p.W = op->W; p.Cin = op->Cin; p.lda = op->lda; p.a_coff = op->a_coff;
+    p.Ho = Ho; p.Wo = Wo;
+    p.kh = op->kh; p.kw = op->kw; p.sh = op->sh; p.sw = op->sw; p.ph = op->ph; p.pw = op->pw; p.dh = op->dh;
+    p.dw = op->dw;
+    p.Wt = wt.p; p.N = op->N; p.K = K;
+    p.pre_scale = op->pre_scale; p.pre_shift = op->pre_shift; p.alpha = alpha; p.beta = beta;
+    p.res = op->res; p.res_bf16 = op->res_bf16 != 0; p.res_ld = op->res_ld;
+    p.act = op->act;
+    p.post_scale = op->post_scale; p.post_shift = op->post_shift;
+    p.gate = op->gate; p.gate_seg = op->gate ? op->gate_seg : 1; p.gate_nseg = op->gate ? op->gate_nseg : 1;
+    p.out = op->out; p.out_bf16 = op->out_bf16 != 0;
+    p.o_sb = op->o_sb; p.o_sh = op->o_sh; p.o_sw = op->o_sw; p.o_sn = op->o_sn;
+    p.glu = op->glu;
+    p.ln_x = op->ln_x; p.ln_t = op->ln_t; p.ln_t_bf16 = op->ln_t_bf16 != 0; p.ln_g = op->ln_g; p.ln_b = op->ln_b;
+    p.ln_eps = op->ln_eps; p.ln_out = op->ln_out;
+    p.pro_mode = op->pro_mode; p.pro_p = op->pro_p; p.pro_C = op->pro_C; p.pro_pad = op->pro_pad;
+    p.pro_cursor = op->pro_cursor; p.pro_nvalid = op->pro_nvalid;
+    p.kv_out = op->kv_out; p.kv_cursor = op->kv_cursor; p.kv_mult = op->kv_mult; p.kv_col0 = op->kv_col0;
+    p.kv_ld = op->kv_ld;
+    if (op->ksplit_out) {
+      SD_CHECK(bf, sd::kErrInvalid, "conv_gemm op: split-K is a bf16 path");
+      const int ks = sd::gemm_splitk_count(p);
+      SD_HIP(hipMemcpyAsync(op->ksplit_out, &ks, sizeof(int), hipMemcpyHostToDevice, st));
+      SD_HIP(hipStreamSynchronize(st));
+      if (ks > 1) {
+        SD_CHECK(ks <= op->slab_cap, sd::kErrInvalid, "conv_gemm op: fewer slabs than the split count");
+        sd::conv_gemm_splitk(p, ks, op->slabs, st);
+        return;
+      }
+      SD_CHECK(op->out, sd::kErrInvalid, "conv_gemm op: no split and no output");
+    }
+    // the production dispatch: which kernel runs follows from the arguments alone, as in the models
+    const sd::GemmX3Scope x3(op->precision == 2);
+    sd::conv_gemm(p, bf, st);
+  });
+}
+
 int sd_op_tstp_pool(const void* x, int x_bf16, int B, int T, int C, float* stats, void* stream) {
   return guard([&] {
     SD_CHECK(x && stats, sd::kErrInvalid, "tstp_pool: null argument");

@@ -1,5 +1,7 @@
 """Kernel-level parity through the C ABI vs torch-CPU fp32 references."""
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -7,6 +9,9 @@ import torch
 import torch.nn.functional as F
 
 from speaker_diarization_amd import _lib, frontend
+
+sys.path.insert(0, os.path.dirname(__file__))
+from conformer_ref import profiled  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -40,10 +45,40 @@ def _rel_err(a, b):
     return float((a - b).abs().max() / (b.abs().max() + 1e-12))
 
 
+_GEMM_LAUNCHES = ("gemm_bf16_reg", "gemm_dma", "gemm_ring", "gemm_stream", "gemm_areg", "gemm_skinny_bf16",
+                  "gemm_skinny_f32", "conv_gemm_f32", "conv_gemm_bf16x3", "fcm_conv3x3_band")
+
+
+def _assert_gemm_launch(launches, name):
+    ran = {k: v for k, v in launches.items() if k.split(" ")[0] in _GEMM_LAUNCHES and v}
+    assert ran == {name: 1}, f"annotated {name}, ran {ran}"
+
+
+# The bf16-A (precision 2) kernel of the test_linear cases annotated with a path, per conv_gemm_bf16's dispatch (the
+# output is fp32 here).  Two of the "streaming" shapes are other kernels' today: K > 384 with N >= 256 goes to the
+# ring GEMM's wide form, and K 64 is below the streaming kernel's 3 k-tiles while the output rows of 130 floats are
+# not the 16-byte multiple the ring GEMM stores, which leaves the LDS-DMA kernel.  At precision 1 (fp32 A) every tall case is the
+# register-staged kernel's, at precision 0 conv_gemm_f32's; the <= 16-row cases are the skinny kernel's everywhere.
+_LINEAR_PATH = {(20000, 384, 512): "gemm_stream", (9001, 384, 1152): "gemm_stream", (7777, 512, 384): "gemm_ring",
+                (5003, 448, 200): "gemm_stream", (3000, 768, 96): "gemm_stream", (2048, 64, 130): "gemm_dma",
+                (1, 2048, 256): "skinny", (6, 256, 2048): "skinny", (16, 768, 256): "skinny",
+                (12, 352, 256): "skinny", (3, 4864, 256): "skinny", (9, 256, 768): "skinny"}
+
+
+def _linear_launch(M, K, N, precision):
+    path = _LINEAR_PATH.get((M, K, N))
+    if path is None:
+        return None
+    if path == "skinny":
+        return "gemm_skinny_f32" if precision == 0 else "gemm_skinny_bf16"
+    return ("conv_gemm_f32", "gemm_bf16_reg", path)[precision]
+
+
 @pytest.mark.parametrize("precision", [0, 1, 2])
 @pytest.mark.parametrize("M,K,N,act", [(1, 32, 4, 0), (257, 384, 1152, 0), (1000, 1536, 384, 1),
                                        (64, 512, 4, 0), (333, 96, 130, 3), (4096, 256, 2048, 2),
-                                       # weight-resident streaming path (bf16 A, K % 64 == 0, M >= 2048):
+                                       # weight-resident streaming path (bf16 A, K % 64 == 0, K >= 192, M >= 2048)
+                                       # and, for (7777, 512, 384) and (2048, 64, 130), the ring and DMA paths: _LINEAR_PATH
                                        (20000, 384, 512, 3), (9001, 384, 1152, 0), (7777, 512, 384, 0),
                                        (5003, 448, 200, 1), (3000, 768, 96, 0), (2048, 64, 130, 2),
                                        # skinny weight-streaming path (M <= 16, streaming FS-EEND chunks):
@@ -58,9 +93,12 @@ def test_linear(gpu, precision, M, K, N, act):
     ref = [ref, F.relu(ref), torch.sigmoid(ref), F.silu(ref)][act]
     out = torch.empty(M, N, device=gpu)
     xd, wd, bd = x.to(gpu), w.to(gpu), b.to(gpu)
-    _lib.call("sd_op_linear", xd.data_ptr(), M, K, wd.data_ptr(), bd.data_ptr(), N, act, out.data_ptr(),
-              precision, _lib.stream_ptr(gpu))
-    torch.cuda.synchronize()
+    with profiled() as launches:
+        _lib.call("sd_op_linear", xd.data_ptr(), M, K, wd.data_ptr(), bd.data_ptr(), N, act, out.data_ptr(),
+                  precision, _lib.stream_ptr(gpu))
+        torch.cuda.synchronize()
+    if _linear_launch(M, K, N, precision):
+        _assert_gemm_launch(launches, _linear_launch(M, K, N, precision))
     if precision == 0:
         torch.testing.assert_close(out.cpu(), ref, **FP32_TOL)
     else:
@@ -88,9 +126,12 @@ def test_conv1d(gpu, precision, B, T, Cin, Cout, k, stride, pad, dil):
     ref = F.conv1d(x, w, b, stride=stride, padding=pad, dilation=dil).permute(0, 2, 1)
     xd = x.permute(0, 2, 1).contiguous().to(gpu)
     out = torch.empty(ref.shape, device=gpu)
-    _lib.call("sd_op_conv1d", xd.data_ptr(), B, T, Cin, _d(w, gpu), _d(b, gpu), Cout, k,
-              stride, pad, dil, 0, out.data_ptr(), precision, _lib.stream_ptr(gpu))
-    torch.cuda.synchronize()
+    with profiled() as launches:
+        _lib.call("sd_op_conv1d", xd.data_ptr(), B, T, Cin, _d(w, gpu), _d(b, gpu), Cout, k,
+                  stride, pad, dil, 0, out.data_ptr(), precision, _lib.stream_ptr(gpu))
+        torch.cuda.synchronize()
+    if k == 19:                                           # the cases annotated (skinny)
+        _assert_gemm_launch(launches, "gemm_skinny_f32" if precision == 0 else "gemm_skinny_bf16")
     if precision == 0:
         torch.testing.assert_close(out.cpu(), ref, **FP32_TOL)
     else:
@@ -270,12 +311,15 @@ def _bf16_round(x):
 
 
 # (M, N, K, lda, a_coff, pre, act): ring path (tall, K <= 1024, N >= 96, bf16 out), its K
-# tail / partial-N / multi-n-tile cases, the stream path (no prologue), the DMA path
-# (K > 1024 or short M).  act 1 = relu (CAM++ nonlinear2).
+# tail / partial-N / multi-n-tile cases and, without a prologue, its K > 384 with N >= 256 rule; the stream path (no
+# prologue, K <= 384 here); the register-staged kernel (a prologue over more than the 1024 channels the ring and DMA
+# kernels stage); the DMA path (short M).  act 1 = relu (CAM++ nonlinear2).  GEMM_BF16_LAUNCH: the kernel of each.
 GEMM_BF16_CASES = [(5000, 128, 640, 1024, 32, True, 1), (4096, 128, 256, 256, 0, True, 1),
                    (3000, 512, 1024, 1024, 0, True, 0), (2100, 132, 360, 400, 8, True, 1),
                    (5000, 384, 512, 512, 0, False, 0), (3000, 128, 1536, 1536, 0, True, 1),
-                   (700, 128, 256, 512, 64, True, 1)]
+                   (700, 128, 256, 512, 64, True, 1), (5000, 384, 384, 384, 0, False, 0)]
+GEMM_BF16_LAUNCH = dict(zip(GEMM_BF16_CASES, ["gemm_ring", "gemm_ring", "gemm_ring", "gemm_ring", "gemm_ring",
+                                              "gemm_bf16_reg", "gemm_dma", "gemm_stream"]))
 
 
 @pytest.mark.parametrize("M,N,K,lda,a_coff,pre,act", GEMM_BF16_CASES)
@@ -295,10 +339,12 @@ def test_gemm_bf16(gpu, M, N, K, lda, a_coff, pre, act):
         ref = torch.relu(ref)
     xd = x.to(torch.bfloat16).view(torch.int16).to(gpu)
     out = torch.zeros(M, N, dtype=torch.int16, device=gpu)
-    _lib.call("sd_op_gemm_bf16", xd.data_ptr(), M, K, lda, a_coff, _d(w, gpu), N,
-              _d(s, gpu) if pre else None, _d(h, gpu) if pre else None, _d(al, gpu), _d(be, gpu), act,
-              out.data_ptr(), N, _lib.stream_ptr(gpu))
-    torch.cuda.synchronize()
+    with profiled() as launches:
+        _lib.call("sd_op_gemm_bf16", xd.data_ptr(), M, K, lda, a_coff, _d(w, gpu), N,
+                  _d(s, gpu) if pre else None, _d(h, gpu) if pre else None, _d(al, gpu), _d(be, gpu), act,
+                  out.data_ptr(), N, _lib.stream_ptr(gpu))
+        torch.cuda.synchronize()
+    _assert_gemm_launch(launches, GEMM_BF16_LAUNCH[(M, N, K, lda, a_coff, pre, act)])
     got = out.cpu().view(torch.bfloat16).float()
     torch.testing.assert_close(got, _bf16_round(ref), atol=2e-2, rtol=1e-2)
 
