@@ -87,7 +87,15 @@ typedef struct {
                                         the reference's forward raises (:1206-1213 unpack (T, B, D, L) in the wrong
                                         order and the view fails): not built.
                                      5 / 6: backend 0 and precision 0 / 1 only (the WavLM trunk has no bf16x3), no
-                                        padding mask (the collater's zero padding takes part, as in the reference) */
+                                        padding mask (the collater's zero padding takes part, as in the reference)
+                                     7: "w2v-bert2" (egs/magicdata-ramc/ts_vad2/model.py:805-840, 1225-1237): ref_speech is
+                                        80-bin fbank (B, T, 80) with T EVEN (the reference's reshape to (B, T / 2, 160)
+                                        raises on an odd T; SD_ERR_INVALID here); the first w2vbert_layers (=
+                                        select_encoder_layer_nums) Conformer layers of w2v-BERT 2.0 (sd_w2vbert_* below),
+                                        hidden_states[-1], then Conv1d(1024 -> speaker_embed_dim, k5, stride 2, pad 2);
+                                        single/multi_backend "transformer".  T frames give T / 2 encoder frames and
+                                        (T / 2 - 1) / 2 + 1 mix frames; variant 4's length rule applies.  backend 0 and
+                                        precision 0 / 1 only; proj_layer as in variants 5 / 6 */
   int max_num_speaker;            /* TSVADDataConfig.max_num_speaker (4)                     */
   int rs_len;                     /* seconds; PositionalEncoding max_len = rs_len * 25       */
   int max_batch;                  /* workspace sizing                                        */
@@ -129,6 +137,8 @@ typedef struct {
   int wavlm_layer_norm_mode;      /* extractor_mode "layer_norm" (Large); must equal wavlm_pre_ln                   */
   int wavlm_pre_ln;               /* layer_norm_first                                                                */
   int max_samples;                /* workspace sizing: the longest window in samples (rs_len * 16000), >= 400        */
+  /* variant 7 (zero otherwise, and last: a config that ends before it, zero-extended, is today's model) */
+  int w2vbert_layers;             /* encoder layers that run and that speech_encoder.encoder.layers.* holds, 1..24   */
 } sd_tsvad_config;
 
 int sd_tsvad_create(const sd_tsvad_config* cfg, sd_tsvad** out);
@@ -533,6 +543,62 @@ int sd_op_wavlm_mix_proj_ln(const float* acc, int rows, int D, const float* w, c
 int sd_op_wavlm_attention(const float* qkv, const float* xin, int B, int T, int H, const float* grep_w,
                           const float* grep_b, const float* grep_a, const float* table, float* out, int precision,
                           void* stream);
+
+/* ------------------------------------------------------------------ w2v-BERT 2.0 speech encoder
+ * Replaces transformers' Wav2Vec2BertModel.forward (models/wav2vec2_bert/modeling_wav2vec2_bert.py:991-1050) in eval
+ * mode, as egs/magicdata-ramc/ts_vad2/model.py:805-840 builds it (hidden_act "swish", num_hidden_layers cut to
+ * select_encoder_layer_nums), at the published geometry only:
+ *   feature_projection    :119-131 (LayerNorm(160) -> Linear(160 -> 1024))
+ *   encoder layer         :398-461 (x += 0.5 ffn1(LN x); x += attn(LN x); x += conv(x); x += 0.5 ffn2(LN x); final LN)
+ *   self-attention        :229-337, position_embeddings_type "relative_key": scores[l, r] = (q_l . k_r + q_l .
+ *                         E[clamp(r - l, -64, 8) + 64]) / 8, E = distance_embedding.weight (73, 64) per layer
+ *   conv module           :157-226 (LN, pointwise_conv1 no bias, GLU, LEFT zero pad 30 + depthwise k31 no bias,
+ *                         depthwise_layer_norm over channels, swish, pointwise_conv2 no bias)
+ * No encoder-level LayerNorm follows the last layer.  State-dict keys are the HF module's (masked_spec_embed, which is
+ * loaded and never read; feature_projection.*; encoder.layers.<i>.*).  No attention_mask, no masking, no adapter. */
+typedef struct sd_w2vbert sd_w2vbert;
+
+typedef struct {
+  int hidden;        /* 1024 */
+  int heads;         /* 16 */
+  int ffn;           /* 4096 */
+  int layers;        /* 1..24 (the TS-VAD recipe cuts the stack to 6) */
+  int conv_kernel;   /* 31 */
+  int left;          /* 64: left_max_position_embeddings */
+  int right;         /* 8: right_max_position_embeddings */
+  int in_dim;        /* 160: feature_projection_input_dim */
+  int precision;     /* 0: fp32 (exact-f32 MFMA), 1: bf16 GEMM / attention operands (LayerNorms, softmax, the depthwise
+                        conv and the residual stream stay fp32) */
+  int max_batch;     /* workspace: windows per forward */
+  int max_frames;    /* workspace: frames per window after the pairing (200 = 4 s) */
+  int position_embeddings;   /* 0: "relative_key" (the only one built) */
+  int add_adapter;           /* 0 (the only one built) */
+} sd_w2vbert_config;
+
+/* Wav2Vec2BertModel.__init__ (:923-945); anything outside the geometry above gives SD_ERR_INVALID with a message naming
+ * the field */
+int sd_w2vbert_create(const sd_w2vbert_config* cfg, sd_w2vbert** out);
+/* load_state_dict (strict here) */
+int sd_w2vbert_set_param(sd_w2vbert* h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+int sd_w2vbert_finalize(sd_w2vbert* h);
+/* Wav2Vec2BertModel.forward (:991-1050).  input_features: device (B, T2, 160) fp32; x_out: device (B, T2, 1024) or NULL,
+ * last_hidden_state; layers_out: device (layers + 1, B, T2, 1024) or NULL, hidden_states with output_hidden_states=True
+ * (the input to layer 0, then each layer's output).  At least one output is required. */
+int sd_w2vbert_forward(sd_w2vbert* h, const float* input_features, int B, int T2, float* x_out, float* layers_out,
+                       void* stream);
+int64_t sd_w2vbert_device_bytes(const sd_w2vbert* h);
+int sd_w2vbert_destroy(sd_w2vbert* h);
+
+/* Test-only single ops of the w2v-BERT trunk (csrc/w2vbert.hip); every pointer is a device pointer, precision 0 or 1.
+ * sd_op_w2vbert_attention: Wav2Vec2BertSelfAttention.forward's core (:306-331) on qkv (B T, 3 H 64) = (q | k | v) with
+ *   dist = distance_embedding.weight (73, 64); out (B T, H 64) fp32.
+ * sd_op_w2vbert_conv_mix: Wav2Vec2BertConvolutionModule.forward's middle (:211-221) on x (B, T, 2048) = pointwise_conv1's
+ *   output [value | gate]: GLU, causal depthwise conv w (1024, 31), LayerNorm (g, beta) over channels, swish; out
+ *   (B, T, 1024) fp32.  precision 1: x rounded to bf16 on entry and the output rounded to bf16, as in the model. */
+int sd_op_w2vbert_attention(const float* qkv, int B, int T, int H, const float* dist, float* out, int precision,
+                            void* stream);
+int sd_op_w2vbert_conv_mix(const float* x, int B, int T, const float* w, const float* g, const float* beta, float* out,
+                           int precision, void* stream);
 
 /* ------------------------------------------------------------------ SSND
  * Replaces SSNDModel.infer (egs/alimeeting/ssnd/ssnd_model.py:752-776) with extractor

@@ -46,6 +46,8 @@ class TsvadConfig(ctypes.Structure):
         ("wavlm_layer_norm_mode", c_int),
         ("wavlm_pre_ln", c_int),
         ("max_samples", c_int),
+        # variant 7 (w2v-bert2): encoder layers; zero otherwise
+        ("w2vbert_layers", c_int),
     ]
 
 
@@ -154,6 +156,12 @@ class WavlmConfig(ctypes.Structure):
     _fields_ = [(n, c_int) for n in (
         "embed_dim", "ffn_dim", "heads", "encoder_layers", "extractor_mode", "layer_norm_first", "max_batch",
         "max_samples", "precision")]
+
+
+class W2vbertConfig(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in (
+        "hidden", "heads", "ffn", "layers", "conv_kernel", "left", "right", "in_dim", "precision", "max_batch",
+        "max_frames", "position_embeddings", "add_adapter")]
 
 
 class SsndConfig(ctypes.Structure):
@@ -272,6 +280,10 @@ _SIGS = {
     "sd_op_wavlm_layer_mix": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     "sd_op_wavlm_mix_proj_ln": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                         c_int, c_void_p]),
+    "sd_w2vbert_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sd_op_w2vbert_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "sd_op_w2vbert_conv_mix": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                       c_void_p]),
     "sd_op_attention_scaled": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
     "sd_op_redim_block2d": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -375,7 +387,7 @@ _SIGS = {
 KINDS = {"tsvad": TsvadConfig, "tsvad_stream": TsvadStreamConfig, "eda": EdaConfig, "fseend": FseendConfig,
          "campp": CamppConfig, "resnet34": Resnet34Config, "simam_resnet34": SimamResnet34Config,
          "eres2netv2": Eres2netv2Config, "ecapa": EcapaConfig, "redimnet": RedimnetConfig, "wavlm": WavlmConfig,
-         "ssnd": SsndConfig}
+         "w2vbert": W2vbertConfig, "ssnd": SsndConfig}
 for _kind, _conf in KINDS.items():
     _SIGS[f"sd_{_kind}_create"] = (c_int, [POINTER(_conf), POINTER(c_void_p)])
     _SIGS[f"sd_{_kind}_set_param"] = (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int])

@@ -24,6 +24,7 @@
 #include "ecapa.h"
 #include "redimnet.h"
 #include "wavlm.h"
+#include "w2vbert.h"
 #include "tsvad_stream.h"
 #include "ssnd.h"
 
@@ -52,6 +53,7 @@ struct sd_eres2netv2 : Handle<sd::ERes2NetV2Model> {};
 struct sd_ecapa : Handle<sd::EcapaModel> {};
 struct sd_redimnet : Handle<sd::RedimNetModel> {};
 struct sd_wavlm : Handle<sd::WavlmModel> {};
+struct sd_w2vbert : Handle<sd::W2vBertModel> {};
 struct sd_ssnd : Handle<sd::SsndModel> {};
 
 namespace {
@@ -195,8 +197,10 @@ int sd_probe_lstm_handoff(int steps, float* us_per_step, void* stream) {
 int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
-    SD_CHECK(c->variant >= 0 && c->variant <= 6, sd::kErrInvalid, "unknown TS-VAD variant");
-    const bool wave = c->variant >= 5;
+    SD_CHECK(c->variant >= 0 && c->variant <= 7, sd::kErrInvalid, "unknown TS-VAD variant");
+    const bool wave = c->variant == 5 || c->variant == 6;
+    SD_CHECK(c->variant != 7 || c->precision != 2, sd::kErrInvalid,
+             "the w2v-bert2 speech encoder (variant 7) does not build bf16x3: the w2v-BERT trunk runs in fp32 or bf16");
     SD_CHECK(!wave || c->precision != 2, sd::kErrInvalid,
              "the WavLM speech encoders (variants 5 / 6) do not build bf16x3: the WavLM trunk runs in fp32 or bf16");
     SD_CHECK(c->precision >= 0 && c->precision <= 2, sd::kErrInvalid, "precision must be 0, 1 or 2");
@@ -225,6 +229,7 @@ int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
     t.wavlm_layer_norm_mode = c->wavlm_layer_norm_mode != 0;
     t.wavlm_pre_ln = c->wavlm_pre_ln != 0;
     t.max_samples = c->max_samples;
+    t.w2vbert_layers = c->w2vbert_layers;
     // proj_layer configurations (speaker_embed_dim * 2 != transformer_embed_dim); backend / d_state / expand
     sd::TsvadModel::validate(t);
     create(out, c->precision == 2, t);
@@ -952,6 +957,91 @@ int sd_op_wavlm_mix_proj_ln(const float* acc, int rows, int D, const float* w, c
     Scratch ob((size_t)rows * SE * 2, st);
     sd::wavlm_mix_proj_ln(acc, rows, D, wt.p, true, bias, g, beta, SE, ob.p, st);
     sd::bf16_to_f32(ob.p, (int64_t)rows * SE, out, st);
+  });
+}
+
+int sd_w2vbert_create(const sd_w2vbert_config* c, sd_w2vbert** out) {
+  return guard([&] {
+    using T = sd::W2vBertTrunk;
+    SD_CHECK(c && out, sd::kErrInvalid, "null argument");
+    SD_CHECK(c->precision == 0 || c->precision == 1, sd::kErrInvalid,
+             "precision must be 0 or 1 (w2v-BERT 2.0 does not build bf16x3)");
+    SD_CHECK(c->hidden == T::kHidden, sd::kErrInvalid, "w2v-BERT 2.0 (MI355X backend) builds hidden 1024 only");
+    SD_CHECK(c->heads == T::kHeads, sd::kErrInvalid, "w2v-BERT 2.0 (MI355X backend) builds heads 16 only");
+    SD_CHECK(c->ffn == T::kFfn, sd::kErrInvalid, "w2v-BERT 2.0 (MI355X backend) builds ffn 4096 only");
+    SD_CHECK(c->layers >= 1 && c->layers <= 24, sd::kErrInvalid, "layers must be 1..24");
+    SD_CHECK(c->conv_kernel == T::kConvK, sd::kErrInvalid, "w2v-BERT 2.0 (MI355X backend) builds conv_kernel 31 only");
+    SD_CHECK(c->left == T::kLeft, sd::kErrInvalid, "w2v-BERT 2.0 (MI355X backend) builds left 64 only");
+    SD_CHECK(c->right == T::kRight, sd::kErrInvalid, "w2v-BERT 2.0 (MI355X backend) builds right 8 only");
+    SD_CHECK(c->in_dim == T::kInDim, sd::kErrInvalid, "w2v-BERT 2.0 (MI355X backend) builds in_dim 160 only");
+    SD_CHECK(c->position_embeddings == 0, sd::kErrInvalid,
+             "w2v-BERT 2.0 (MI355X backend) builds position_embeddings 0 (relative_key) only");
+    SD_CHECK(c->add_adapter == 0, sd::kErrInvalid, "w2v-BERT 2.0 (MI355X backend) builds add_adapter 0 only");
+    SD_CHECK(c->max_batch > 0, sd::kErrInvalid, "max_batch must be positive");
+    SD_CHECK(c->max_frames > 0, sd::kErrInvalid, "max_frames must be positive");
+    // rows (B T2) times the widest row are counted in int
+    SD_CHECK((int64_t)c->max_batch * c->max_frames * T::kFfn < (1ll << 31), sd::kErrInvalid,
+             "max_batch * max_frames * ffn must be below 2^31");
+    sd::W2vBertConfig t;
+    t.layers = c->layers; t.max_batch = c->max_batch; t.max_frames = c->max_frames; t.bf16 = c->precision == 1;
+    create(out, false, t);
+  });
+}
+
+int sd_w2vbert_set_param(sd_w2vbert* h, const char* name, const float* data, const int64_t* shape, int ndim) {
+  return set_param(h, name, data, shape, ndim);
+}
+
+int sd_w2vbert_finalize(sd_w2vbert* h) { return finalize(h); }
+
+int sd_w2vbert_forward(sd_w2vbert* h, const float* in, int B, int T2, float* x_out, float* layers_out, void* stream) {
+  return guard([&] {
+    SD_CHECK(h && in && (x_out || layers_out), sd::kErrInvalid, "null argument");
+    h->model->forward(in, B, T2, x_out, layers_out, S(stream));
+  });
+}
+
+int64_t sd_w2vbert_device_bytes(const sd_w2vbert* h) { return device_bytes(h); }
+
+int sd_w2vbert_destroy(sd_w2vbert* h) { return destroy(h); }
+
+int sd_op_w2vbert_attention(const float* qkv, int B, int T, int H, const float* dist, float* out, int precision,
+                            void* stream) {
+  return guard([&] {
+    SD_CHECK(qkv && dist && out, sd::kErrInvalid, "w2vbert_attention: null argument");
+    SD_CHECK(B >= 1 && T >= 1 && H >= 1, sd::kErrInvalid, "w2vbert_attention: empty problem");
+    SD_CHECK(precision == 0 || precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    hipStream_t st = S(stream);
+    const bool bf = precision == 1;
+    Activations qa(qkv, (int64_t)B * T * 3 * H * 64, bf ? 2 : 0, st);
+    // distance_embedding.weight (73, 64) zero-padded to the kernel's 80 rows, in the operands' type
+    Scratch e32((size_t)sd::kW2vDistRows * 64 * 4, st), e16((size_t)sd::kW2vDistRows * 64 * 2, st);
+    sd::zero_fill(e32.p, (size_t)sd::kW2vDistRows * 64 * 4, st);
+    SD_HIP(hipMemcpyAsync(e32.p, dist, (size_t)73 * 64 * 4, hipMemcpyDeviceToDevice, st));
+    if (bf) sd::f32_to_bf16(static_cast<const float*>(e32.p), (int64_t)sd::kW2vDistRows * 64, e16.p, st);
+    sd::W2vAttnArgs a;
+    a.qkv = qa.a; a.bf16 = bf; a.dist = bf ? e16.p : e32.p; a.B = B; a.T = T; a.D = H * 64; a.H = H;
+    a.out = out; a.out_bf16 = false;
+    sd::w2vbert_attention(a, st);
+  });
+}
+
+int sd_op_w2vbert_conv_mix(const float* x, int B, int T, const float* w, const float* g, const float* beta, float* out,
+                           int precision, void* stream) {
+  return guard([&] {
+    SD_CHECK(x && w && g && beta && out, sd::kErrInvalid, "w2vbert_conv_mix: null argument");
+    SD_CHECK(B >= 1 && T >= 1, sd::kErrInvalid, "w2vbert_conv_mix: empty problem");
+    SD_CHECK(precision == 0 || precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    hipStream_t st = S(stream);
+    if (precision == 0) {
+      sd::w2vbert_conv_mix(x, B, T, w, g, beta, out, false, st);
+      return;
+    }
+    const int64_t rows = (int64_t)B * T;
+    Activations xa(x, rows * 2 * sd::kW2vConvC, 2, st);
+    Scratch ob((size_t)rows * sd::kW2vConvC * 2, st);
+    sd::w2vbert_conv_mix(xa.a, B, T, w, g, beta, ob.p, true, st);
+    sd::bf16_to_f32(ob.p, rows * sd::kW2vConvC, out, st);
   });
 }
 

@@ -1031,4 +1031,35 @@ void wavlm_mix_proj_ln(const float* acc, int rows, int D, const void* wt, bool b
 // j < n_w (and start_w + j < n_total), else 0, for j < n_out.
 void window_wave(const float* wav, int64_t n_total, const int* win_start, const int* win_n, int n_win, int n_out,
                  float* out, hipStream_t st);
+
+// ---------------------------------------------------------------- w2v-BERT 2.0 (w2vbert.hip)
+// Self-attention with the relative_key distance embedding (transformers' Wav2Vec2BertSelfAttention.forward,
+// modeling_wav2vec2_bert.py:263-337), head size 64, left 64 / right 8, no mask, any T >= 1:
+//   out[b, l, h] = softmax_r((q_l . k_r + q_l . E[clamp(r - l, -64, 8) + 64]) scale) v
+// on a packed projection qkv (B T, 3 D) = (q | k | v), fp32 or bf16 bits.  dist: the layer's distance_embedding.weight
+// (73, 64), shared by the heads, zero-padded to kW2vDistRows rows, in qkv's type.  One workgroup per (16 queries, head,
+// window) computes R = Q E^T (16 x 80) on MFMA once into LDS, then walks the keys 64 at a time with a running max / sum
+// (fp32 softmax), adding R[l][clamp(r - l)] to Q K^T before the scale; Q K^T and P V on MFMA, bf16 operands when qkv is
+// bf16, else exact f32.  Keys >= T score -inf, queries >= T are not stored.  out (B T, D) at column h * 64, bf16 bits
+// when out_bf16.  Nothing of size (T, T) exists in global memory.
+constexpr int kW2vDistRows = 80;
+struct W2vAttnArgs {
+  const void* qkv = nullptr;
+  bool bf16 = false;
+  const void* dist = nullptr;   // (kW2vDistRows, 64)
+  int B = 0, T = 0, D = 0, H = 0;
+  float scale = 0.125f;
+  void* out = nullptr;
+  bool out_bf16 = false;
+};
+void w2vbert_attention(const W2vAttnArgs& a, hipStream_t st);
+// The middle of Wav2Vec2BertConvolutionModule.forward (:211-221) in one launch: GLU over channels, left zero pad of 30
+// + depthwise Conv1d(k 31, no bias) (causal), depthwise_layer_norm over the 1024 channels (fp32 statistics, eps 1e-5),
+// swish.  x (B, T, 2048): pointwise_conv1's output as plain halves [value 1024 | gate 1024], fp32 or bf16 bits; w
+// (1024, 31) fp32; g / beta: the LayerNorm affine; out (B, T, 1024) in x's type.  A workgroup owns kW2vConvTile frames of
+// one window with all channels; its 30-frame left halo reads zeros before the window's first frame, never another
+// window's frames.  out must not alias x.
+constexpr int kW2vConvC = 1024, kW2vConvK = 31, kW2vConvTile = 16;
+void w2vbert_conv_mix(const void* x, int B, int T, const float* w, const float* g, const float* beta, void* out,
+                      bool bf16, hipStream_t st);
 }  // namespace sd

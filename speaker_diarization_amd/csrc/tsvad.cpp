@@ -11,11 +11,14 @@
 //          variants 5, 6 (WavLM / WavLM_weight_sum, magicdata model.py:867-927, 1171-1204): ref_speech is the raw
 //                    waveform (B, n_samples); the WavLM trunk (wavlm.h) on the caller's stream; 6 accumulates the
 //                    layer-weighted sum as the layers run, then wavlmproj + wavlmlnorm in one kernel
+//          variant 7 (w2v-bert2, magicdata model.py:805-840, 1225-1237): ref_speech (B, T, 80) read as (B, T / 2, 160)
+//                    (a plain reshape: the same memory); the w2v-BERT 2.0 trunk (w2vbert.h) on the caller's stream
 //     -> speech_down_or_up (down_gemm) -> mix (B, T3, SE)
 //          variants 0, 1: conv + BN + ReLU                    model.py:385-395 / 406-416
 //          variant 2: SpeechFeatUpsample2 transposed conv + BN + ReLU (model.py:114-134)
 //          variants 3, 4: conv k5 stride 4 pad 2 + BN + ReLU (model.py:641-654; magicdata :703-715)
 //          variants 5, 6: conv k5 stride 2 pad 2 + BN + ReLU (magicdata :879-889, 913-927)
+//          variant 7: the same conv on 1024 channels (magicdata :830-840)
 //     -> transformer_backend, variants 0, 2, 3 and 4 (forward_common, model.py:758-897):
 //          [ts_embed | mix] + PE, 2-layer transformer per speaker (batched over speakers)
 //          -> backend_down conv(1536->384, k5)+BN+ReLU -> PE -> 2-layer transformer -> fc
@@ -62,6 +65,16 @@ void TsvadModel::validate(const TsvadConfig& c) {
     SD_CHECK(c.variant != 6 || c.speaker_embed_dim == 192 || c.speaker_embed_dim == 256, kErrInvalid,
              "WavLM_weight_sum (variant 6) is built for speaker_embed_dim 192 or 256");
     SD_CHECK(c.speaker_embed_dim % 32 == 0, kErrInvalid, "variants 5 / 6: speaker_embed_dim must be a multiple of 32");
+  }
+  if (c.variant == 7) {
+    SD_CHECK(c.backend == 0, kErrInvalid,
+             "the w2v-bert2 speech encoder (variant 7) is built with the transformer back end only (backend 0)");
+    SD_CHECK(c.w2vbert_layers >= 1 && c.w2vbert_layers <= 24, kErrInvalid,
+             "variant 7 (w2v-bert2): w2vbert_layers must be 1..24");
+    SD_CHECK(c.max_fbank_frames >= 2, kErrInvalid, "variant 7: max_fbank_frames must be at least 2");
+    SD_CHECK((int64_t)c.max_batch * (c.max_fbank_frames / 2) * W2vBertTrunk::kFfn < (1ll << 31), kErrInvalid,
+             "max_batch * (max_fbank_frames / 2) * 4096 must be below 2^31");
+    SD_CHECK(c.speaker_embed_dim % 32 == 0, kErrInvalid, "variant 7: speaker_embed_dim must be a multiple of 32");
   }
   if (c.speaker_embed_dim * 2 == c.embed_dim) return;
   // proj_layer = nn.Linear(2 SE, E) on cat(ts_embed, mix_embeds) (model.py:212-217, 873-874)
@@ -113,6 +126,15 @@ void TsvadModel::build() {
       wln_g_ = arena_.upload(ps_.get("wavlmlnorm.weight").data);
       wln_b_ = arena_.upload(ps_.get("wavlmlnorm.bias").data);
     }
+  } else if (cfg_.variant == 7) {
+    // Wav2Vec2BertModel with num_hidden_layers = select_encoder_layer_nums (magicdata model.py:811-824)
+    W2vBertConfig w;
+    w.layers = cfg_.w2vbert_layers;
+    w.max_batch = cfg_.max_batch;
+    w.max_frames = cfg_.max_fbank_frames / 2;
+    w.bf16 = cfg_.bf16;
+    w2v_ = std::make_unique<W2vBertTrunk>(w);
+    w2v_->load(ps_, arena_, se);
   } else if (cfg_.variant == 4) {
     redim_ = std::make_unique<RedimTrunk>();
     redim_->load(ps_, arena_, se, cfg_.bf16);   // redimnet_wespeaker.py:623-790
@@ -181,9 +203,11 @@ void TsvadModel::build() {
     SD_CHECK(ps_.get("speech_down_or_up.0.bias").numel() == cfg_.speaker_embed_dim, kErrParam,
              "speech_down_or_up.0.bias size");
     down_bn_ = bn_only("speech_down_or_up.1.bn");
-  } else if (waveform()) {
-    // Conv1d(D -> SE, k5, stride 2, pad 2), D the WavLM width (5) or speaker_embed_dim behind wavlmproj (6): no prologue
-    const int cin = cfg_.variant == 6 ? cfg_.speaker_embed_dim : cfg_.wavlm_embed_dim;
+  } else if (waveform() || cfg_.variant == 7) {
+    // Conv1d(D -> SE, k5, stride 2, pad 2), D the WavLM width (5), speaker_embed_dim behind wavlmproj (6) or w2v-BERT's
+    // 1024 (7): no prologue
+    const int cin = cfg_.variant == 7 ? W2vBertTrunk::kHidden
+                    : cfg_.variant == 6 ? cfg_.speaker_embed_dim : cfg_.wavlm_embed_dim;
     down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
     SD_CHECK(down_.w.N == cfg_.speaker_embed_dim && down_.w.Cin == cin && down_.w.kw == 5, kErrParam,
              "speech_down_or_up.0.weight must be (speaker_embed_dim, " + std::to_string(cin) + ", 5)");
@@ -304,6 +328,7 @@ void TsvadModel::alloc_workspace() {
       z_ = arena_.alloc(rows * cfg_.speaker_embed_dim * (cfg_.bf16 ? 2 : 4));
     }
   }
+  else if (w2v_) w2v_->alloc(arena_);
   else cam_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
   mix_ = ws(g.mix_elems);
   mixg_ = ws(g.mix_elems);
@@ -528,6 +553,11 @@ Tens TsvadModel::trunk_forward(const float* ref, int Bh, int Tf, hipStream_t s, 
     wavlm_mix_proj_ln(acc_, rows, D, wproj_.w.w, cfg_.bf16, wproj_.beta, wln_g_, wln_b_, cfg_.speaker_embed_dim, z_, s);
     return Tens{z_, cfg_.bf16};
   }
+  if (w2v_) {
+    SD_CHECK(b0 == 0, kErrInvalid, "the w2v-BERT trunk runs over the whole batch");
+    // torch.reshape(ref_speech, (B, T // 2, 160)) is the same memory (:1228-1231); hidden_states[-1] (:1232-1235)
+    return w2v_->encode(ref, Bh, Tf / 2, s);
+  }
   if (ecapa_) return ecapa_->forward(ref, Bh, Tf, s, b0);
   if (redim_) {
     SD_CHECK(b0 == 0, kErrInvalid, "the ReDimNetB2 trunk runs over the whole batch");
@@ -549,6 +579,8 @@ ConvGemmArgs TsvadModel::down_gemm(Tens x, int Bh, int Tf, float* out) const {
   if (wavlm_)
     return cam_conv1d(x, Bh, WavlmTrunk::frames(Tf), cfg_.variant == 6 ? SE : cfg_.wavlm_embed_dim, down_, 2, 2, 1,
                       Tens{out, false}, SE);
+  // w2v-BERT: the same conv over the (Bh, T / 2, 1024) encoder output
+  if (w2v_) return cam_conv1d(x, Bh, Tf / 2, W2vBertTrunk::kHidden, down_, 2, 2, 1, Tens{out, false}, SE);
   // CAM++: k5 stride-2 pad-2 conv, out_nonlinear's BN-ReLU fused as its prologue
   return cam_conv1d(x, Bh, CamTrunk::out_frames(Tf), CamTrunk::kChannels, down_, 2, 2, 1, Tens{out, false}, SE);
 }
@@ -576,6 +608,11 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   } else {
     SD_CHECK(Tf >= (cfg_.variant >= 3 ? 1 : 8) && Tf <= cfg_.max_fbank_frames, kErrInvalid,
              "fbank frames exceed max_fbank_frames");
+    // the reference's torch.reshape(ref_speech, (B, T // 2, 160)) raises on an odd T (magicdata model.py:1228-1231)
+    SD_CHECK(!w2v_ || Tf % 2 == 0, kErrInvalid,
+             "w2v-bert2 needs an even number of fbank frames: the reference reshapes (B, T, 80) to (B, T / 2, 160) "
+             "and raises on an odd T (shape is invalid for input of size)");
+    SD_CHECK(!w2v_ || !gemm_x3(), kErrInvalid, "the w2v-bert2 speech encoder (variant 7) does not build bf16x3");
   }
   raise_if_set();
   const int T3 = mix_frames(Tf);
@@ -588,7 +625,7 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   // Under the libsdiar kernel timer (bench.py's extra profiled step) the forward stays on one stream, so
   // each kernel's HIP-event time is its own and not shared with the other slice's kernels.
   static const bool one_stream_env = getenv("SDIAR_CAM_ONE_STREAM") != nullptr;
-  const bool two = !(one_stream_env || prof_enabled()) && B >= 384 && !redim_ && !wavlm_;   // RedimTrunk / WavlmTrunk take no window slice
+  const bool two = !(one_stream_env || prof_enabled()) && B >= 384 && !redim_ && !wavlm_ && !w2v_;   // these trunks take no window slice
   // ---------------- BatchNorm1D's NaN bypass: which windows hold a non-finite input, which reference forwards
   // (groups of forward_batch windows) therefore skip the BatchNorm (from the inputs alone, so first: the window
   // slices below then need nothing from each other until the LSTM)

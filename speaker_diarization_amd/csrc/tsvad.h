@@ -9,6 +9,7 @@
 #include "redimnet.h"
 #include "resnet.h"
 #include "wavlm.h"
+#include "w2vbert.h"
 
 namespace sd {
 
@@ -22,6 +23,9 @@ struct TsvadConfig {
                               //    extract_features(ref_speech)[0]) + conv k5 stride 2 + transformer (:867-889, 1171-1179)
                               // 6: WavLM_weight_sum with wavlm_fuse_feat_post_norm: every layer's output weighted by
                               //    `weights`, wavlmproj, wavlmlnorm, the same conv (:890-927, 1180-1204)
+                              // 7: w2v-bert2 on 80-bin fbank paired to (B, T / 2, 160): the first w2vbert_layers Conformer
+                              //    layers of w2v-BERT 2.0, hidden_states[-1] + conv k5 stride 2 + transformer (:805-840,
+                              //    1225-1237)
   int max_num_speaker = 4;
   int rs_len = 4;
   int max_batch = 64;
@@ -50,6 +54,7 @@ struct TsvadConfig {
   bool wavlm_layer_norm_mode = false; // extractor_mode "layer_norm"
   bool wavlm_pre_ln = false;          // layer_norm_first
   int max_samples = 0;
+  int w2vbert_layers = 0;             // variant 7: encoder layers that run (and that the state_dict holds)
 };
 
 class TsvadModel : public ModelCore {
@@ -119,6 +124,7 @@ class TsvadModel : public ModelCore {
   std::unique_ptr<EcapaTrunk> ecapa_;   // ECAPA-TDNN c1024, variant 3
   std::unique_ptr<RedimTrunk> redim_;   // ReDimNetB2, variant 4
   std::unique_ptr<WavlmTrunk> wavlm_;   // WavLM on the waveform, variants 5 and 6
+  std::unique_ptr<W2vBertTrunk> w2v_;   // w2v-BERT 2.0 on paired fbank frames, variant 7
   // values per frame of ref_speech: mel bins, or 1 for the waveform variants
   int feat_dim() const { return wavlm_ ? 1 : cfg_.variant == 4 ? RedimTrunk::kF : 80; }
   bool waveform() const { return cfg_.variant == 5 || cfg_.variant == 6; }
@@ -129,6 +135,7 @@ class TsvadModel : public ModelCore {
   int mix_frames(int Tf) const {
     if (waveform()) return (WavlmTrunk::frames(Tf) - 1) / 2 + 1;   // WavLM's 50 frames / s through the stride-2 conv
     if (cfg_.variant == 3 || cfg_.variant == 4) return (Tf - 1) / 4 + 1;
+    if (cfg_.variant == 7) return (Tf / 2 - 1) / 2 + 1;   // w2v-BERT's 50 frames / s through the stride-2 conv
     return cfg_.variant == 2 ? 2 * ResTrunk::out_frames(Tf) : (CamTrunk::out_frames(Tf) - 1) / 2 + 1;
   }
   // the back end of forward_common (variant 0's; also behind the ResNet34 and ECAPA encoders)

@@ -1,2 +1,3 @@
 """Self-supervised speech front ends on the HIP path."""
 from .wavlm import WavLM, WavLMConfig, num_frames  # noqa: F401
+from .w2vbert import W2vBert, W2vBertConfig  # noqa: F401

@@ -49,6 +49,14 @@ class TSVADModel(_lib.Handle):
             wav = dict(wavlm_embed_dim=w.encoder_embed_dim, wavlm_layers=w.encoder_layers,
                        wavlm_layer_norm_mode=int(w.extractor_mode == "layer_norm"),
                        wavlm_pre_ln=int(bool(w.layer_norm_first)), max_samples=self.max_samples)
+        if c.variant == 7:
+            # w2v-bert2 reads variant 0's fbank windows; only the encoder depth is its own
+            if precision == "bf16x3":
+                raise ValueError("the w2v-bert2 speech encoder does not build bf16x3 (the w2v-BERT trunk runs in fp32 "
+                                 "or bf16)")
+            wav = dict(w2vbert_layers=c.effective_w2vbert_cfg().num_hidden_layers)
+            # the reference takes any even frame count; rs_len seconds at 100 frames / s is the longest a window gives
+            self.max_fbank = max(self.max_fbank, c.rs_len * 100)
         self._create(_lib.TsvadConfig(
             variant=c.variant, max_num_speaker=c.max_num_speaker, rs_len=c.rs_len, max_batch=self.max_batch,
             max_fbank_frames=self.max_fbank, precision=_lib.PRECISION[precision],
@@ -105,6 +113,11 @@ class TSVADModel(_lib.Handle):
         else:
             B, T_fb, F = ref_speech.shape
             assert F == self.cfg.n_mels, f"{self.cfg.speech_encoder_type} expects {self.cfg.n_mels}-dim fbank"
+            if self.cfg.variant == 7 and T_fb % 2:
+                # torch.reshape(ref_speech, (B, T // 2, 160)) of the reference (magicdata model.py:1228-1231)
+                raise ValueError(f"w2v-bert2 needs an even number of fbank frames, got {T_fb}: the reference reshapes "
+                                 f"(B, T, 80) to (B, T // 2, 160) and raises (shape '[{B}, {T_fb // 2}, 160]' is "
+                                 f"invalid for input of size {B * T_fb * 80})")
         ref = ref_speech.to(self.device, torch.float32).contiguous()
         ts = target_speech.to(self.device, torch.float32).contiguous()
         assert ts.shape == (B, self.max_num_speaker, self.cfg.speaker_embed_dim)

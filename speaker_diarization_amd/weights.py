@@ -57,6 +57,10 @@ class TSVADConfig:
     wavlm_cfg: Optional[Any] = None
     select_encoder_layer_nums: int = 6         # "WavLM": encoder layers kept (model.py:870)
     wavlm_fuse_feat_post_norm: bool = False    # "WavLM_weight_sum": weights -> wavlmproj -> wavlmlnorm (:904-909)
+    # "w2v-bert2" (egs/magicdata-ramc/ts_vad2/model.py:805-840): w2vbert_cfg stands in for the config.json of
+    # cfg.speech_encoder_config, a W2vBertConfig of speaker_diarization_amd.ssl.w2vbert; None: the published geometry.
+    # select_encoder_layer_nums overrides its depth (model.py:816).
+    w2vbert_cfg: Optional[Any] = None
 
     @property
     def waveform_input(self) -> bool:
@@ -76,6 +80,25 @@ class TSVADConfig:
         c = copy.copy(self.wavlm_cfg)
         c.encoder_layers = self.wavlm_encoder_layers
         return c
+
+    def effective_w2vbert_cfg(self):
+        """w2vbert_cfg (None: the published geometry) with num_hidden_layers = select_encoder_layer_nums (a copy)."""
+        import copy
+        from .ssl.w2vbert import W2vBertConfig
+        c = copy.copy(self.w2vbert_cfg) if self.w2vbert_cfg is not None else W2vBertConfig()
+        c.num_hidden_layers = self.select_encoder_layer_nums
+        return c
+
+    def _w2vbert_variant(self) -> int:
+        se = self.speech_encoder_type
+        if self.ots_vad_style or (self.single_backend_type, self.multi_backend_type) != ("transformer", "transformer"):
+            raise ValueError(
+                f"unsupported TS-VAD configuration {se}/{self.single_backend_type}/{self.multi_backend_type}"
+                f"{' ots_vad_style ' + self.ots_vad_style if self.ots_vad_style else ''}: the w2v-bert2 speech encoder "
+                "is built with the transformer single and multi back ends only (no Mamba2, no ots_vad)")
+        from .ssl.w2vbert import check_config
+        check_config(self.effective_w2vbert_cfg())
+        return 7
 
     def _wavlm_variant(self) -> int:
         se = self.speech_encoder_type
@@ -109,6 +132,8 @@ class TSVADConfig:
     def variant(self) -> int:
         if self.waveform_input:
             return self._wavlm_variant()   # 5 "WavLM", 6 "WavLM_weight_sum" with wavlm_fuse_feat_post_norm
+        if self.speech_encoder_type == "w2v-bert2":
+            return self._w2vbert_variant()   # 7
         if self.ots_vad_style == "v1":
             if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) != (
                     "CAM++_ots_vad", "conformer_ots_vad", "lstm_ots_vad"):
@@ -133,7 +158,7 @@ class TSVADConfig:
                 f"{self.single_backend_type}/{self.multi_backend_type} (MI355X backend builds CAM++ "
                 "with transformer, mamba2 + transformer, mamba2 + mamba2 or conformer_ots_vad/lstm_ots_vad, "
                 "resnet34_wespeaker, ecapa_channel_1024_wespeaker and ReDimNetB2 with transformer, WavLM / "
-                "WavLM_weight_sum with transformer given wavlm_cfg)")
+                "WavLM_weight_sum with transformer given wavlm_cfg, w2v-bert2 with transformer)")
         return 0
 
     @property
@@ -479,6 +504,14 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         k.append(("speech_down_or_up.0.weight", (se, se if cfg.variant == 6 else d, 5), "conv1d"))
         k.append(("speech_down_or_up.0.bias", (se,), "small"))
         _bn(k, "speech_down_or_up.1.bn", se)
+    elif cfg.variant == 7:
+        # the first select_encoder_layer_nums layers of w2v-BERT 2.0 + Conv1d(1024 -> D, k5, stride 2, pad 2)
+        # (egs/magicdata-ramc/ts_vad2/model.py:805-840); the back end is variant 0's
+        w = cfg.effective_w2vbert_cfg()
+        k = w2vbert_layout(w, "speech_encoder.")
+        k.append(("speech_down_or_up.0.weight", (se, w.output_hidden_size, 5), "conv1d"))
+        k.append(("speech_down_or_up.0.bias", (se,), "small"))
+        _bn(k, "speech_down_or_up.1.bn", se)
     else:
         k = campplus_layout()
         if cfg.variant == 1:
@@ -492,7 +525,7 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         # 873-874); the reference registers it for every variant, its ots_vad forward never applies it
         k.append(("proj_layer.weight", (e, 2 * se), "linear"))
         k.append(("proj_layer.bias", (e,), "small"))
-    if cfg.variant in (0, 2, 3, 4, 5, 6):
+    if cfg.variant in (0, 2, 3, 4, 5, 6, 7):
         k.append(("pos_encoder.pe", (cfg.rs_len * cfg.label_rate, 1, e), "pe"))
         backend = cfg.backend
         if backend:
@@ -781,6 +814,13 @@ def tsvad_state_dict(cfg: TSVADConfig, seed: int = 777, spread: bool = False, dy
         enc = wavlm_state_dict(cfg.effective_wavlm_cfg(), seed)
         rest = synthetic_state_dict([e for e in layout if not e[0].startswith("speech_encoder.")], seed + 1)
         return OrderedDict([("speech_encoder." + k, v) for k, v in enc.items()] + list(rest.items()))
+    if cfg.variant == 7:
+        # the encoder part: w2vbert_state_dict's sharp weights; the rest seeded as for every other variant
+        if spread or dynamic:
+            raise ValueError("no spread / dynamic calibration for the w2v-bert2 speech encoder")
+        enc = w2vbert_state_dict(cfg.effective_w2vbert_cfg(), seed)
+        rest = synthetic_state_dict([e for e in layout if not e[0].startswith("speech_encoder.")], seed + 1)
+        return OrderedDict([("speech_encoder." + k, v) for k, v in enc.items()] + list(rest.items()))
     sd = synthetic_state_dict(layout, seed)
     if spread and dynamic:
         raise ValueError("spread and dynamic are two different variants")
@@ -1051,6 +1091,83 @@ def wavlm_state_dict(cfg, seed: int = 777):
         affine(p + "final_layer_norm", D)
     affine("encoder.layer_norm", D)
     affine("layer_norm", cin)
+    return sd
+
+
+def w2vbert_layout(cfg, prefix: str = "") -> list:
+    """Key layout of transformers' Wav2Vec2BertModel(cfg) (modeling_wav2vec2_bert.py:923-945) with relative_key position
+    embeddings and no adapter, under `prefix`: (name, shape, kind), in the module's registration order; the kind names no
+    seeding (w2vbert_state_dict seeds these).  cfg: a W2vBertConfig of speaker_diarization_amd.ssl.w2vbert or any
+    object with its fields."""
+    D, F, L = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
+    hd = D // cfg.num_attention_heads
+    nd = cfg.left_max_position_embeddings + cfg.right_max_position_embeddings + 1
+    kk, din = cfg.conv_depthwise_kernel_size, cfg.feature_projection_input_dim
+
+    def ln(p, n):
+        return [(p + ".weight", (n,), "w2vbert"), (p + ".bias", (n,), "w2vbert")]
+
+    def lin(p, n, m):
+        return [(p + ".weight", (n, m), "w2vbert"), (p + ".bias", (n,), "w2vbert")]
+
+    k = [("masked_spec_embed", (D,), "w2vbert")]
+    k += ln("feature_projection.layer_norm", din) + lin("feature_projection.projection", D, din)
+    for i in range(L):
+        p = f"encoder.layers.{i}."
+        k += ln(p + "ffn1_layer_norm", D)
+        k += lin(p + "ffn1.intermediate_dense", F, D) + lin(p + "ffn1.output_dense", D, F)
+        k += ln(p + "self_attn_layer_norm", D)
+        for n in ("linear_q", "linear_k", "linear_v", "linear_out"):
+            k += lin(p + "self_attn." + n, D, D)
+        k.append((p + "self_attn.distance_embedding.weight", (nd, hd), "w2vbert"))
+        k += ln(p + "conv_module.layer_norm", D)
+        k.append((p + "conv_module.pointwise_conv1.weight", (2 * D, D, 1), "w2vbert"))
+        k.append((p + "conv_module.depthwise_conv.weight", (D, 1, kk), "w2vbert"))
+        k += ln(p + "conv_module.depthwise_layer_norm", D)
+        k.append((p + "conv_module.pointwise_conv2.weight", (D, D, 1), "w2vbert"))
+        k += ln(p + "ffn2_layer_norm", D)
+        k += lin(p + "ffn2.intermediate_dense", F, D) + lin(p + "ffn2.output_dense", D, F)
+        k += ln(p + "final_layer_norm", D)
+    return [(prefix + n, s, kind) for n, s, kind in k]
+
+
+# Seeded w2v-BERT 2.0 init (w2vbert_layout).  The q / k projections give per-head q . k / 8 a standard deviation of about
+# 2.3 on LayerNorm'd rows (q and k entries ~ N(0, 1.5^2): 1.5 * 1.5 * sqrt(64) / 8 = 2.25), and the distance embedding is
+# N(0, 1.5^2) too, so q . E / 8 has the same spread: the attention is sharp and the distance term carries half of the
+# score variance.  tests/golden/make_golden_w2vbert.py asserts that zeroing it, flipping the distance's sign or swapping
+# the clamp bounds each move the stored logits by at least ten fp32 bars.
+W2V_QK_STD = 1.5 / 32.0       # on 1024 unit-variance inputs: output std 1.5
+W2V_DIST_STD = 1.5
+
+
+def w2vbert_state_dict(cfg, seed: int = 777):
+    """Seeded w2v-BERT 2.0 weights under the HF key names (see W2V_QK_STD above); every bias and norm affine is
+    perturbed by 0.1 N, the value / output / FFN / pointwise weights are drawn so that each sub-block's output is O(1)
+    on the LayerNorm'd stream, the depthwise taps so that the 31-tap sum has unit gain."""
+    rng = np.random.default_rng(seed)
+    D, F = cfg.hidden_size, cfg.intermediate_size
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for name, shape, _ in w2vbert_layout(cfg):
+        leaf = name.rsplit(".", 2)[-2] if name.count(".") else name
+        if name == "masked_spec_embed":
+            v = rng.uniform(0.0, 1.0, shape)
+        elif name.endswith(".bias"):
+            v = rng.standard_normal(shape) * 0.1
+        elif "layer_norm" in leaf:
+            v = 1.0 + rng.standard_normal(shape) * 0.1
+        elif leaf in ("linear_q", "linear_k"):
+            v = rng.standard_normal(shape) * W2V_QK_STD
+        elif leaf == "distance_embedding":
+            v = rng.standard_normal(shape) * W2V_DIST_STD
+        elif leaf == "depthwise_conv":
+            v = rng.standard_normal(shape) / np.sqrt(shape[-1])
+        elif leaf == "pointwise_conv1":
+            v = rng.standard_normal(shape) * (1.5 / np.sqrt(shape[1]))   # gates of standard deviation 1.5: a live GLU
+        elif leaf == "output_dense":
+            v = rng.standard_normal(shape) * (2.0 / np.sqrt(shape[1]))   # swish halves the hidden layer's scale
+        else:   # projection, linear_v, linear_out, intermediate_dense, pointwise_conv2
+            v = rng.standard_normal(shape) / np.sqrt(shape[1])
+        sd[name] = np.ascontiguousarray(v, dtype=np.float32)
     return sd
 
 
