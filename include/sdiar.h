@@ -95,7 +95,16 @@ typedef struct {
                                         hidden_states[-1], then Conv1d(1024 -> speaker_embed_dim, k5, stride 2, pad 2);
                                         single/multi_backend "transformer".  T frames give T / 2 encoder frames and
                                         (T / 2 - 1) / 2 + 1 mix frames; variant 4's length rule applies.  backend 0 and
-                                        precision 0 / 1 only; proj_layer as in variants 5 / 6 */
+                                        precision 0 / 1 only; proj_layer as in variants 5 / 6
+                                     8: "whisper" (egs/magicdata-ramc/ts_vad2/model.py:928-955, 1216-1223): ref_speech is
+                                        the raw waveform (B, n_samples) as for 5 / 6 (n_samples carried by T_fb, a multiple
+                                        of 4 in [400, max_samples]); the Whisper-PMFA encoder (sd_whisper_* below), then
+                                        Conv1d(n_audio_state * n_cat -> speaker_embed_dim, k5, stride 2, pad 2);
+                                        single/multi_backend "transformer".  n samples give T' = (n / 160 - 1) / 2 + 1
+                                        encoder frames (T' > n_audio_ctx is refused) and (T' - 1) / 2 + 1 mix frames;
+                                        variant 4's length rule applies.  backend 0 and precision 0 / 1 only.  This struct
+                                        has no field for the trunk's geometry: sd_tsvad_create returns SD_ERR_INVALID for
+                                        variant 8, sd_tsvad_create_whisper (below) builds it */
   int max_num_speaker;            /* TSVADDataConfig.max_num_speaker (4)                     */
   int rs_len;                     /* seconds; PositionalEncoding max_len = rs_len * 25       */
   int max_batch;                  /* workspace sizing                                        */
@@ -599,6 +608,64 @@ int sd_op_w2vbert_attention(const float* qkv, int B, int T, int H, const float* 
                             void* stream);
 int sd_op_w2vbert_conv_mix(const float* x, int B, int T, const float* w, const float* g, const float* beta, float* out,
                            int precision, void* stream);
+
+/* ------------------------------------------------------------------ Whisper-PMFA encoder
+ * Replaces WhisperEncoder.forward (egs/magicdata-ramc/ts_vad2/whisper_encoder.py:150-244; ModelDimensions :19-27) in
+ * eval mode: per-window whisper.log_mel_spectrogram (no 30-s padding), conv1 k3 + GELU, conv2 k3 stride 2 + GELU, the
+ * loaded positional_embedding[:T'], n_audio_layer pre-LN blocks (:116-147; key projection without bias :66), and
+ * ln_post2 over the concatenated outputs of blocks layer_st .. layer_ed.  State-dict keys are the reference class's own
+ * (conv1.*, conv2.*, positional_embedding, layers.<i>.{attn.{query,key,value,out},attn_ln,mlp.0,mlp.2,mlp_ln}.*,
+ * ln_post2.*), plus one key that is not the reference's: mel_filters (n_mels, 201), the slaney mel matrix computed on the
+ * host (speaker_diarization_amd.feature.whisper_mel_filters).  The front end is restated from the published formula
+ * (torch.stft form), not taken from the whisper package. */
+typedef struct sd_whisper sd_whisper;
+
+typedef struct {
+  int n_mels;          /* 80 or 128 */
+  int n_audio_ctx;     /* rows of positional_embedding (1500); a window of more frames is refused */
+  int n_audio_state;   /* 64 * n_audio_head, a multiple of 32 (1280) */
+  int n_audio_head;    /* head size 64 only (20) */
+  int n_audio_layer;   /* 1..32 (24) */
+  int layer_st;        /* 0 <= layer_st <= layer_ed < n_audio_layer (16, 23); n_audio_state * (layer_ed - layer_st + 1) */
+  int layer_ed;        /*   at most 16384 */
+  int precision;       /* 0: fp32 (exact-f32 MFMA), 1: bf16 GEMM / conv / attention operands (the log-mel front end, the
+                          LayerNorms, the softmax, GELU inputs, the residual stream and the output stay fp32) */
+  int max_batch;       /* workspace: windows per forward */
+  int max_samples;     /* workspace: samples per window (64000 = 4 s) */
+} sd_whisper_config;
+
+/* anything outside the ranges above gives SD_ERR_INVALID with a message naming the field */
+int sd_whisper_create(const sd_whisper_config* cfg, sd_whisper** out);
+/* load_state_dict (strict here) */
+int sd_whisper_set_param(sd_whisper* h, const char* name, const float* host_data, const int64_t* shape, int ndim);
+int sd_whisper_finalize(sd_whisper* h);
+/* T' = ((n_samples / 160) - 1) / 2 + 1 frames of a window of n_samples (0 below 400 samples) */
+int sd_whisper_frames(int n_samples);
+/* wavs: device (B, n_samples) fp32, 400 <= n_samples <= max_samples and T' <= n_audio_ctx (the reference truncates there
+ * and TS-VAD's label-length assertion then fails: SD_ERR_INVALID here).  out: device (B, T', n_audio_state * (layer_ed -
+ * layer_st + 1)) fp32.  A window holding a non-finite sample comes out all NaN; the other windows are untouched. */
+int sd_whisper_forward(sd_whisper* h, const float* wavs, int B, int n_samples, float* out, void* stream);
+int64_t sd_whisper_device_bytes(const sd_whisper* h);
+int sd_whisper_destroy(sd_whisper* h);
+
+/* TS-VAD variant 8: an sd_tsvad_config with variant 8 and max_samples set, plus the trunk's own geometry; wcfg's precision,
+ * max_batch and max_samples are ignored (cfg's hold).  State-dict keys: speech_encoder.<the keys above, mel_filters
+ * included>, speech_down_or_up.{0,1.bn}.* and the usual back-end keys.  Any other variant: SD_ERR_INVALID. */
+int sd_tsvad_create_whisper(const sd_tsvad_config* cfg, const sd_whisper_config* wcfg, sd_tsvad** out);
+
+/* Test-only single ops of the Whisper trunk (csrc/whisper.hip); every pointer is a device pointer.
+ * sd_op_whisper_logmel: the log-mel front end of wav (B, n) with mel (n_mels, 201) -> out (B, n / 160, n_mels) fp32.
+ * sd_op_whisper_stem: feat (B, F, n_mels) -> out (B, (F - 1) / 2 + 1, D) = gelu(conv2(gelu(conv1(feat)))) + pe, w1 (D,
+ *   n_mels, 3), w2 (D, D, 3), pe (>= T', D); precision 0 or 1.
+ * sd_op_whisper_add: out[r, :D] = x[r, :D] + t[r, :D] with x / out rows at strides ldx / ldo, t dense.
+ * sd_op_whisper_ln_wide: LayerNorm (eps 1e-5) over rows of W values at stride ldx -> out (rows, W) fp32; precision 1:
+ *   the output rounded to bf16, as the model hands it to the next GEMM. */
+int sd_op_whisper_logmel(const float* wav, int B, int n, int n_mels, const float* mel, float* out, void* stream);
+int sd_op_whisper_stem(const float* feat, int B, int F, int n_mels, int D, const float* w1, const float* b1,
+                       const float* w2, const float* b2, const float* pe, float* out, int precision, void* stream);
+int sd_op_whisper_add(const float* x, int ldx, const float* t, float* out, int ldo, int64_t rows, int D, void* stream);
+int sd_op_whisper_ln_wide(const float* x, int ldx, int64_t rows, int W, const float* g, const float* b, float* out,
+                          int precision, void* stream);
 
 /* ------------------------------------------------------------------ SSND
  * Replaces SSNDModel.infer (egs/alimeeting/ssnd/ssnd_model.py:752-776) with extractor

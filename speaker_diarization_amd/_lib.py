@@ -164,6 +164,12 @@ class W2vbertConfig(ctypes.Structure):
         "max_frames", "position_embeddings", "add_adapter")]
 
 
+class WhisperConfig(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in (
+        "n_mels", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_layer", "layer_st", "layer_ed", "precision",
+        "max_batch", "max_samples")]
+
+
 class SsndConfig(ctypes.Structure):
     _fields_ = [(n, c_int) for n in (
         "max_batch", "max_fbank_frames", "max_speakers", "feat_dim", "emb_dim", "q_det_aux_dim", "q_rep_aux_dim",
@@ -284,6 +290,15 @@ _SIGS = {
     "sd_op_w2vbert_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "sd_op_w2vbert_conv_mix": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                        c_void_p]),
+    "sd_whisper_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sd_whisper_frames": (c_int, [c_int]),
+    "sd_tsvad_create_whisper": (c_int, [POINTER(TsvadConfig), POINTER(WhisperConfig), POINTER(c_void_p)]),
+    "sd_op_whisper_logmel": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sd_op_whisper_stem": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_int, c_void_p]),
+    "sd_op_whisper_add": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p]),
+    "sd_op_whisper_ln_wide": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_void_p]),
     "sd_op_attention_scaled": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p]),
     "sd_op_redim_block2d": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, c_int, c_void_p]),
@@ -387,7 +402,7 @@ _SIGS = {
 KINDS = {"tsvad": TsvadConfig, "tsvad_stream": TsvadStreamConfig, "eda": EdaConfig, "fseend": FseendConfig,
          "campp": CamppConfig, "resnet34": Resnet34Config, "simam_resnet34": SimamResnet34Config,
          "eres2netv2": Eres2netv2Config, "ecapa": EcapaConfig, "redimnet": RedimnetConfig, "wavlm": WavlmConfig,
-         "w2vbert": W2vbertConfig, "ssnd": SsndConfig}
+         "w2vbert": W2vbertConfig, "whisper": WhisperConfig, "ssnd": SsndConfig}
 for _kind, _conf in KINDS.items():
     _SIGS[f"sd_{_kind}_create"] = (c_int, [POINTER(_conf), POINTER(c_void_p)])
     _SIGS[f"sd_{_kind}_set_param"] = (c_int, [c_void_p, c_char_p, c_void_p, POINTER(c_int64), c_int])

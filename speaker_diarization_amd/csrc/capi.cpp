@@ -25,6 +25,7 @@
 #include "redimnet.h"
 #include "wavlm.h"
 #include "w2vbert.h"
+#include "whisper.h"
 #include "tsvad_stream.h"
 #include "ssnd.h"
 
@@ -54,6 +55,7 @@ struct sd_ecapa : Handle<sd::EcapaModel> {};
 struct sd_redimnet : Handle<sd::RedimNetModel> {};
 struct sd_wavlm : Handle<sd::WavlmModel> {};
 struct sd_w2vbert : Handle<sd::W2vBertModel> {};
+struct sd_whisper : Handle<sd::WhisperModel> {};
 struct sd_ssnd : Handle<sd::SsndModel> {};
 
 namespace {
@@ -194,11 +196,46 @@ int sd_probe_lstm_handoff(int steps, float* us_per_step, void* stream) {
   });
 }
 
-int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
+// sd_whisper_config's geometry rules, shared by sd_whisper_create and sd_tsvad_create_whisper
+static void check_whisper_geometry(const sd_whisper_config* c) {
+  SD_CHECK(c->n_mels == 80 || c->n_mels == 128, sd::kErrInvalid, "n_mels must be 80 or 128");
+  SD_CHECK(c->n_audio_ctx >= 1, sd::kErrInvalid, "n_audio_ctx must be positive");
+  SD_CHECK(c->n_audio_head >= 1 && c->n_audio_state == 64 * c->n_audio_head, sd::kErrInvalid,
+           "n_audio_state must be 64 * n_audio_head (head size 64 only)");
+  SD_CHECK(c->n_audio_state % 32 == 0, sd::kErrInvalid, "n_audio_state must be a multiple of 32");
+  SD_CHECK(c->n_audio_layer >= 1 && c->n_audio_layer <= 32, sd::kErrInvalid, "n_audio_layer must be 1..32");
+  SD_CHECK(c->layer_st >= 0 && c->layer_st <= c->layer_ed, sd::kErrInvalid, "layer_st must be 0..layer_ed");
+  SD_CHECK(c->layer_ed < c->n_audio_layer, sd::kErrInvalid, "layer_ed must be below n_audio_layer");
+  SD_CHECK((int64_t)c->n_audio_state * (c->layer_ed - c->layer_st + 1) <= sd::kWhisperMaxWide, sd::kErrInvalid,
+           "n_audio_state * (layer_ed - layer_st + 1) must be at most 16384 (ln_post2's row)");
+}
+
+// rows times the widest row are counted in int: the DFT's (B F, 402) and the MLP's (B T', 4 D)
+static void check_whisper_workspace(const sd_whisper_config* c, int max_batch, int max_samples) {
+  SD_CHECK(max_batch > 0 && max_batch <= 65535, sd::kErrInvalid, "max_batch must be 1..65535");
+  SD_CHECK(max_samples >= sd::WhisperTrunk::kMinSamples, sd::kErrInvalid, "max_samples must be at least 400");
+  const int64_t rf = (int64_t)max_batch * sd::WhisperTrunk::mel_frames(max_samples);
+  SD_CHECK(rf * std::max(2 * sd::kWhisperBins, 2 * c->n_audio_state) < (1ll << 31), sd::kErrInvalid,
+           "max_batch * frames * row width must be below 2^31");
+}
+
+static sd::WhisperConfig whisper_geometry(const sd_whisper_config* c) {
+  sd::WhisperConfig t;
+  t.n_mels = c->n_mels; t.n_ctx = c->n_audio_ctx; t.state = c->n_audio_state; t.heads = c->n_audio_head;
+  t.layers = c->n_audio_layer; t.layer_st = c->layer_st; t.layer_ed = c->layer_ed;
+  return t;
+}
+
+static int tsvad_create(const sd_tsvad_config* c, const sd_whisper_config* wc, sd_tsvad** out) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
-    SD_CHECK(c->variant >= 0 && c->variant <= 7, sd::kErrInvalid, "unknown TS-VAD variant");
-    const bool wave = c->variant == 5 || c->variant == 6;
+    SD_CHECK(c->variant >= 0 && c->variant <= 8, sd::kErrInvalid, "unknown TS-VAD variant");
+    SD_CHECK(c->variant != 8 || wc, sd::kErrInvalid,
+             "variant 8 (whisper) takes the trunk's own geometry: create it with sd_tsvad_create_whisper");
+    SD_CHECK(c->variant == 8 || !wc, sd::kErrInvalid, "sd_tsvad_create_whisper builds variant 8 only");
+    const bool wave = c->variant == 5 || c->variant == 6 || c->variant == 8;
+    SD_CHECK(c->variant != 8 || c->precision != 2, sd::kErrInvalid,
+             "the whisper speech encoder (variant 8) does not build bf16x3: the Whisper trunk runs in fp32 or bf16");
     SD_CHECK(c->variant != 7 || c->precision != 2, sd::kErrInvalid,
              "the w2v-bert2 speech encoder (variant 7) does not build bf16x3: the w2v-BERT trunk runs in fp32 or bf16");
     SD_CHECK(!wave || c->precision != 2, sd::kErrInvalid,
@@ -230,10 +267,22 @@ int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) {
     t.wavlm_pre_ln = c->wavlm_pre_ln != 0;
     t.max_samples = c->max_samples;
     t.w2vbert_layers = c->w2vbert_layers;
+    if (wc) {
+      check_whisper_geometry(wc);
+      check_whisper_workspace(wc, c->max_batch, c->max_samples);
+      t.whisper = whisper_geometry(wc);
+    }
     // proj_layer configurations (speaker_embed_dim * 2 != transformer_embed_dim); backend / d_state / expand
     sd::TsvadModel::validate(t);
     create(out, c->precision == 2, t);
   });
+}
+
+int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) { return tsvad_create(c, nullptr, out); }
+
+int sd_tsvad_create_whisper(const sd_tsvad_config* c, const sd_whisper_config* wc, sd_tsvad** out) {
+  if (!wc) return guard([] { SD_CHECK(false, sd::kErrInvalid, "null argument"); });
+  return tsvad_create(c, wc, out);
 }
 
 int sd_tsvad_set_param(sd_tsvad* h, const char* name, const float* data, const int64_t* shape, int ndim) {
@@ -1042,6 +1091,116 @@ int sd_op_w2vbert_conv_mix(const float* x, int B, int T, const float* w, const f
     Scratch ob((size_t)rows * sd::kW2vConvC * 2, st);
     sd::w2vbert_conv_mix(xa.a, B, T, w, g, beta, ob.p, true, st);
     sd::bf16_to_f32(ob.p, rows * sd::kW2vConvC, out, st);
+  });
+}
+
+int sd_whisper_create(const sd_whisper_config* c, sd_whisper** out) {
+  return guard([&] {
+    SD_CHECK(c && out, sd::kErrInvalid, "null argument");
+    SD_CHECK(c->precision == 0 || c->precision == 1, sd::kErrInvalid,
+             "precision must be 0 or 1 (the Whisper encoder does not build bf16x3)");
+    check_whisper_geometry(c);
+    check_whisper_workspace(c, c->max_batch, c->max_samples);
+    sd::WhisperConfig t = whisper_geometry(c);
+    t.max_batch = c->max_batch; t.max_samples = c->max_samples; t.bf16 = c->precision == 1;
+    create(out, false, t);
+  });
+}
+
+int sd_whisper_set_param(sd_whisper* h, const char* name, const float* data, const int64_t* shape, int ndim) {
+  return set_param(h, name, data, shape, ndim);
+}
+
+int sd_whisper_finalize(sd_whisper* h) { return finalize(h); }
+
+int sd_whisper_frames(int n_samples) { return n_samples < 400 ? 0 : sd::WhisperTrunk::frames(n_samples); }
+
+int sd_whisper_forward(sd_whisper* h, const float* wavs, int B, int n_samples, float* out, void* stream) {
+  return guard([&] {
+    SD_CHECK(h && wavs && out, sd::kErrInvalid, "null argument");
+    h->model->forward(wavs, B, n_samples, out, S(stream));
+  });
+}
+
+int64_t sd_whisper_device_bytes(const sd_whisper* h) { return device_bytes(h); }
+
+int sd_whisper_destroy(sd_whisper* h) { return destroy(h); }
+
+int sd_op_whisper_logmel(const float* wav, int B, int n, int n_mels, const float* mel, float* out, void* stream) {
+  return guard([&] {
+    SD_CHECK(wav && mel && out, sd::kErrInvalid, "whisper_logmel: null argument");
+    SD_CHECK(B >= 1 && n >= 400 && (n_mels == 80 || n_mels == 128), sd::kErrInvalid, "whisper_logmel: bad argument");
+    hipStream_t st = S(stream);
+    const int64_t rows = (int64_t)B * (n / sd::kWhisperHop);
+    std::vector<float> basis, hann, m((size_t)n_mels * sd::kWhisperBins), mt(m.size());
+    sd::whisper_dft_basis(basis, hann);
+    SD_HIP(hipStreamSynchronize(st));
+    SD_HIP(hipMemcpy(m.data(), mel, m.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n_mels; ++i)
+      for (int k = 0; k < sd::kWhisperBins; ++k) mt[(size_t)k * n_mels + i] = m[(size_t)i * sd::kWhisperBins + k];
+    Scratch db(basis.size() * 4, st), dh(hann.size() * 4, st), dm(mt.size() * 4, st);
+    SD_HIP(hipMemcpy(db.p, basis.data(), basis.size() * 4, hipMemcpyHostToDevice));
+    SD_HIP(hipMemcpy(dh.p, hann.data(), hann.size() * 4, hipMemcpyHostToDevice));
+    SD_HIP(hipMemcpy(dm.p, mt.data(), mt.size() * 4, hipMemcpyHostToDevice));
+    Scratch fr((size_t)rows * sd::kWhisperNfft * 4, st), sp((size_t)rows * 2 * sd::kWhisperBins * 4, st),
+        raw((size_t)rows * n_mels * 4, st), mx((size_t)B * 4, st);
+    sd::WhisperLogmelArgs a;
+    a.wav = wav; a.B = B; a.n = n; a.n_mels = n_mels;
+    a.hann = static_cast<const float*>(dh.p); a.basis = static_cast<const float*>(db.p);
+    a.melT = static_cast<const float*>(dm.p);
+    a.frames = static_cast<float*>(fr.p); a.spec = static_cast<float*>(sp.p); a.raw = static_cast<float*>(raw.p);
+    a.wmax = static_cast<uint32_t*>(mx.p);
+    a.out = out; a.ldo = n_mels; a.out_bf16 = false;
+    sd::whisper_logmel(a, st);
+  });
+}
+
+int sd_op_whisper_stem(const float* feat, int B, int F, int n_mels, int D, const float* w1, const float* b1,
+                       const float* w2, const float* b2, const float* pe, float* out, int precision, void* stream) {
+  return guard([&] {
+    SD_CHECK(feat && w1 && b1 && w2 && b2 && pe && out, sd::kErrInvalid, "whisper_stem: null argument");
+    SD_CHECK(B >= 1 && F >= 1 && n_mels >= 4 && n_mels % 4 == 0 && D >= 32 && D % 32 == 0, sd::kErrInvalid,
+             "whisper_stem: bad argument");
+    SD_CHECK(precision == 0 || precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    hipStream_t st = S(stream);
+    const bool bf = precision == 1;
+    const int ld = (n_mels + 31) / 32 * 32;
+    const int64_t rows = (int64_t)B * F;
+    // the rows padded to ld channels, and conv1's weight (D, n_mels, 3) padded alike
+    Scratch f32((size_t)rows * ld * 4, st), wp((size_t)D * ld * 3 * 4, st);
+    sd::zero_fill(f32.p, (size_t)rows * ld * 4, st);
+    SD_HIP(hipMemcpy2DAsync(f32.p, (size_t)ld * 4, feat, (size_t)n_mels * 4, (size_t)n_mels * 4, rows,
+                            hipMemcpyDeviceToDevice, st));
+    sd::zero_fill(wp.p, (size_t)D * ld * 3 * 4, st);
+    // (n, c, tap): the n_mels * 3 values of output channel n start at n * ld * 3 of the padded weight
+    SD_HIP(hipMemcpy2DAsync(wp.p, (size_t)ld * 12, w1, (size_t)n_mels * 12, (size_t)n_mels * 12, D,
+                            hipMemcpyDeviceToDevice, st));
+    Activations fa(static_cast<const float*>(f32.p), rows * ld, bf ? 2 : 0, st);
+    PackedScratch p1(static_cast<const float*>(wp.p), D, ld, 3, bf, st), p2(w2, D, D, 3, bf, st);
+    Scratch c1((size_t)rows * D * (bf ? 2 : 4), st);
+    sd::WhisperStemW w;
+    w.conv1 = p1.p; w.conv2 = p2.p; w.b1 = b1; w.b2 = b2; w.pe = pe; w.mel_ld = ld; w.D = D;
+    sd::whisper_stem(w, fa.a, B, F, bf, c1.p, out, st);
+  });
+}
+
+int sd_op_whisper_add(const float* x, int ldx, const float* t, float* out, int ldo, int64_t rows, int D, void* stream) {
+  return guard([&] { sd::whisper_add(x, ldx, t, out, ldo, rows, D, S(stream)); });
+}
+
+int sd_op_whisper_ln_wide(const float* x, int ldx, int64_t rows, int W, const float* g, const float* b, float* out,
+                          int precision, void* stream) {
+  return guard([&] {
+    SD_CHECK(precision == 0 || precision == 1, sd::kErrInvalid, "precision must be 0 or 1");
+    SD_CHECK(rows >= 1 && W >= 4, sd::kErrInvalid, "whisper_ln_wide: empty problem");
+    hipStream_t st = S(stream);
+    if (precision == 0) {
+      sd::whisper_ln_wide(x, ldx, rows, W, g, b, 1e-5f, out, W, false, st);
+      return;
+    }
+    Scratch ob((size_t)rows * W * 2, st);
+    sd::whisper_ln_wide(x, ldx, rows, W, g, b, 1e-5f, ob.p, W, true, st);
+    sd::bf16_to_f32(ob.p, rows * W, out, st);
   });
 }
 

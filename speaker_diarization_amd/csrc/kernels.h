@@ -1062,4 +1062,42 @@ void w2vbert_attention(const W2vAttnArgs& a, hipStream_t st);
 constexpr int kW2vConvC = 1024, kW2vConvK = 31, kW2vConvTile = 16;
 void w2vbert_conv_mix(const void* x, int B, int T, const float* w, const float* g, const float* beta, void* out,
                       bool bf16, hipStream_t st);
+
+// ---------------------------------------------------------------- whisper (whisper.hip)
+// whisper.log_mel_spectrogram(wav, n_mels) per window, no 30-s padding (the published formula: torch.stft(wav, 400, 160,
+// hann_window(400)) with center=True / reflect, the last frame dropped, |.|^2, the (n_mels, 201) slaney mel matrix,
+// log10(clamp(., 1e-10)), maximum(., max over the WHOLE window - 8), (. + 4) / 4), all fp32.  wav (B, n), n >= 400,
+// F = n / 160 frames.  The 400-point DFT runs as conv_gemm's exact-f32 MFMA GEMM of the windowed frames (B F, 400)
+// against `basis` (402, 400) = [cos | -sin] rows (whisper_dft_basis), whatever the caller's precision.  The window
+// maximum is an unsigned atomic max over an order-preserving key (bit-identical for any order) in which NaN ranks top:
+// a non-finite sample makes every feature of its window NaN, as torch's max / maximum do, and leaves the other windows
+// untouched.  wmax is re-initialised in the stream by every call.  out (B F, ldo): columns [0, n_mels) the features,
+// columns [n_mels, ldo) zeros (conv_gemm's multi-tap form needs Cin % 32 == 0: 80 mels ride in rows of 96); fp32, or
+// bf16 bits when out_bf16.
+constexpr int kWhisperNfft = 400, kWhisperHop = 160, kWhisperBins = 201, kWhisperMaxWide = 16384;
+struct WhisperLogmelArgs {
+  const float* wav = nullptr;
+  int B = 0, n = 0, n_mels = 0;
+  const float* hann = nullptr;    // (400)
+  const float* basis = nullptr;   // (402, 400) fp32, conv_gemm's Wt[N][K]
+  const float* melT = nullptr;    // (201, n_mels): the mel matrix transposed
+  float* frames = nullptr;        // scratch (B F, 400)
+  float* spec = nullptr;          // scratch (B F, 402)
+  float* raw = nullptr;           // scratch (B F, n_mels)
+  uint32_t* wmax = nullptr;       // scratch (B)
+  void* out = nullptr;
+  int ldo = 0;
+  bool out_bf16 = false;
+};
+void whisper_dft_basis(std::vector<float>& basis, std::vector<float>& hann);   // host images, angles reduced exactly
+void whisper_logmel(const WhisperLogmelArgs& a, hipStream_t st);
+// out[r, 0..D) = x[r, 0..D) + t[r, 0..D) over `rows` rows: x at stride ldx, t (rows, D) dense, out at stride ldo (the
+// pointers already at their column slice; out may alias x).  The PMFA residual stream: block i + 1 reads slice i of the
+// wide buffer and writes slice i + 1.  D, ldx, ldo multiples of 4, 16-byte aligned pointers.
+void whisper_add(const float* x, int ldx, const float* t, float* out, int ldo, int64_t rows, int D, hipStream_t st);
+// y = LN(x) g + b over rows of W <= 16384 floats (W % 4 == 0) at strides ldx / ldy: one workgroup per row, the row in
+// registers, two-pass fp32 statistics; y fp32 or bf16 bits (the A operand of the GEMM that follows).  ln_post2 over the
+// concatenated block outputs, and the blocks' own LayerNorms where the state is wider than layernorm()'s 1024.
+void whisper_ln_wide(const float* x, int64_t ldx, int64_t rows, int W, const float* g, const float* b, float eps,
+                     void* y, int64_t ldy, bool y_bf16, hipStream_t st);
 }  // namespace sd

@@ -11,6 +11,8 @@
 //          variants 5, 6 (WavLM / WavLM_weight_sum, magicdata model.py:867-927, 1171-1204): ref_speech is the raw
 //                    waveform (B, n_samples); the WavLM trunk (wavlm.h) on the caller's stream; 6 accumulates the
 //                    layer-weighted sum as the layers run, then wavlmproj + wavlmlnorm in one kernel
+//          variant 8 (whisper, magicdata model.py:928-955, 1216-1223): ref_speech is the raw waveform; the Whisper-PMFA
+//                    trunk (whisper.h) on the caller's stream, its ln_post2 output the conv's A operand
 //          variant 7 (w2v-bert2, magicdata model.py:805-840, 1225-1237): ref_speech (B, T, 80) read as (B, T / 2, 160)
 //                    (a plain reshape: the same memory); the w2v-BERT 2.0 trunk (w2vbert.h) on the caller's stream
 //     -> speech_down_or_up (down_gemm) -> mix (B, T3, SE)
@@ -19,6 +21,7 @@
 //          variants 3, 4: conv k5 stride 4 pad 2 + BN + ReLU (model.py:641-654; magicdata :703-715)
 //          variants 5, 6: conv k5 stride 2 pad 2 + BN + ReLU (magicdata :879-889, 913-927)
 //          variant 7: the same conv on 1024 channels (magicdata :830-840)
+//          variant 8: the same conv on n_audio_state * n_cat channels (10240 published; magicdata :945-955)
 //     -> transformer_backend, variants 0, 2, 3 and 4 (forward_common, model.py:758-897):
 //          [ts_embed | mix] + PE, 2-layer transformer per speaker (batched over speakers)
 //          -> backend_down conv(1536->384, k5)+BN+ReLU -> PE -> 2-layer transformer -> fc
@@ -66,6 +69,12 @@ void TsvadModel::validate(const TsvadConfig& c) {
              "WavLM_weight_sum (variant 6) is built for speaker_embed_dim 192 or 256");
     SD_CHECK(c.speaker_embed_dim % 32 == 0, kErrInvalid, "variants 5 / 6: speaker_embed_dim must be a multiple of 32");
   }
+  if (c.variant == 8) {
+    SD_CHECK(c.backend == 0, kErrInvalid,
+             "the whisper speech encoder (variant 8) is built with the transformer back end only (backend 0)");
+    SD_CHECK(c.max_samples >= WhisperTrunk::kMinSamples, kErrInvalid, "max_samples must be at least 400");
+    SD_CHECK(c.speaker_embed_dim % 32 == 0, kErrInvalid, "variant 8: speaker_embed_dim must be a multiple of 32");
+  }
   if (c.variant == 7) {
     SD_CHECK(c.backend == 0, kErrInvalid,
              "the w2v-bert2 speech encoder (variant 7) is built with the transformer back end only (backend 0)");
@@ -95,6 +104,14 @@ void TsvadModel::build() {
   } else if (cfg_.variant == 3) {
     ecapa_ = std::make_unique<EcapaTrunk>();
     ecapa_->load(ps_, arena_, se, cfg_.bf16);   // ecapa_tdnn_wespeaker.py:161-209 (no pool / bn / linear keys)
+  } else if (cfg_.variant == 8) {
+    // WhisperEncoder(ModelDimensions) under speech_encoder.* (magicdata model.py:936-943)
+    WhisperConfig w = cfg_.whisper;
+    w.max_batch = cfg_.max_batch;
+    w.max_samples = cfg_.max_samples;
+    w.bf16 = cfg_.bf16;
+    whisper_ = std::make_unique<WhisperTrunk>(w);
+    whisper_->load(ps_, arena_, se);
   } else if (waveform()) {
     // WavLM(wavlm_cfg) with encoder_layers = select_encoder_layer_nums (5) or the checkpoint's (6)
     // (magicdata model.py:867-877, 890-899)
@@ -204,9 +221,9 @@ void TsvadModel::build() {
              "speech_down_or_up.0.bias size");
     down_bn_ = bn_only("speech_down_or_up.1.bn");
   } else if (waveform() || cfg_.variant == 7) {
-    // Conv1d(D -> SE, k5, stride 2, pad 2), D the WavLM width (5), speaker_embed_dim behind wavlmproj (6) or w2v-BERT's
-    // 1024 (7): no prologue
-    const int cin = cfg_.variant == 7 ? W2vBertTrunk::kHidden
+    // Conv1d(D -> SE, k5, stride 2, pad 2), D the WavLM width (5), speaker_embed_dim behind wavlmproj (6), w2v-BERT's
+    // 1024 (7) or Whisper's n_audio_state * n_cat (8): no prologue
+    const int cin = cfg_.variant == 8 ? whisper_->wide() : cfg_.variant == 7 ? W2vBertTrunk::kHidden
                     : cfg_.variant == 6 ? cfg_.speaker_embed_dim : cfg_.wavlm_embed_dim;
     down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
     SD_CHECK(down_.w.N == cfg_.speaker_embed_dim && down_.w.Cin == cin && down_.w.kw == 5, kErrParam,
@@ -329,6 +346,7 @@ void TsvadModel::alloc_workspace() {
     }
   }
   else if (w2v_) w2v_->alloc(arena_);
+  else if (whisper_) whisper_->alloc(arena_, true);
   else cam_->alloc(arena_, cfg_.max_batch, cfg_.max_fbank_frames);
   mix_ = ws(g.mix_elems);
   mixg_ = ws(g.mix_elems);
@@ -553,6 +571,10 @@ Tens TsvadModel::trunk_forward(const float* ref, int Bh, int Tf, hipStream_t s, 
     wavlm_mix_proj_ln(acc_, rows, D, wproj_.w.w, cfg_.bf16, wproj_.beta, wln_g_, wln_b_, cfg_.speaker_embed_dim, z_, s);
     return Tens{z_, cfg_.bf16};
   }
+  if (whisper_) {
+    SD_CHECK(b0 == 0, kErrInvalid, "the Whisper trunk runs over the whole batch");
+    return whisper_->encode(ref, Bh, Tf, s);   // self.speech_encoder(ref_speech) (:1221)
+  }
   if (w2v_) {
     SD_CHECK(b0 == 0, kErrInvalid, "the w2v-BERT trunk runs over the whole batch");
     // torch.reshape(ref_speech, (B, T // 2, 160)) is the same memory (:1228-1231); hidden_states[-1] (:1232-1235)
@@ -579,6 +601,8 @@ ConvGemmArgs TsvadModel::down_gemm(Tens x, int Bh, int Tf, float* out) const {
   if (wavlm_)
     return cam_conv1d(x, Bh, WavlmTrunk::frames(Tf), cfg_.variant == 6 ? SE : cfg_.wavlm_embed_dim, down_, 2, 2, 1,
                       Tens{out, false}, SE);
+  // Whisper: the same conv over the (Bh, T', n_audio_state * n_cat) normalised concatenation
+  if (whisper_) return cam_conv1d(x, Bh, WhisperTrunk::frames(Tf), whisper_->wide(), down_, 2, 2, 1, Tens{out, false}, SE);
   // w2v-BERT: the same conv over the (Bh, T / 2, 1024) encoder output
   if (w2v_) return cam_conv1d(x, Bh, Tf / 2, W2vBertTrunk::kHidden, down_, 2, 2, 1, Tens{out, false}, SE);
   // CAM++: k5 stride-2 pad-2 conv, out_nonlinear's BN-ReLU fused as its prologue
@@ -604,7 +628,8 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
     SD_CHECK(Tf >= WavlmTrunk::kMinSamples, kErrInvalid, "n_samples must be at least 400");
     SD_CHECK(Tf <= cfg_.max_samples, kErrInvalid, "n_samples exceeds max_samples");
     SD_CHECK(Tf % 4 == 0, kErrInvalid, "n_samples must be a multiple of 4 (16-byte window rows)");
-    SD_CHECK(!gemm_x3(), kErrInvalid, "the WavLM speech encoders (variants 5 / 6) do not build bf16x3");
+    SD_CHECK(!gemm_x3(), kErrInvalid,
+             "the waveform speech encoders (WavLM, variants 5 / 6; whisper, variant 8) do not build bf16x3");
   } else {
     SD_CHECK(Tf >= (cfg_.variant >= 3 ? 1 : 8) && Tf <= cfg_.max_fbank_frames, kErrInvalid,
              "fbank frames exceed max_fbank_frames");
@@ -625,7 +650,7 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
   // Under the libsdiar kernel timer (bench.py's extra profiled step) the forward stays on one stream, so
   // each kernel's HIP-event time is its own and not shared with the other slice's kernels.
   static const bool one_stream_env = getenv("SDIAR_CAM_ONE_STREAM") != nullptr;
-  const bool two = !(one_stream_env || prof_enabled()) && B >= 384 && !redim_ && !wavlm_ && !w2v_;   // these trunks take no window slice
+  const bool two = !(one_stream_env || prof_enabled()) && B >= 384 && !redim_ && !wavlm_ && !w2v_ && !whisper_;   // these trunks take no window slice
   // ---------------- BatchNorm1D's NaN bypass: which windows hold a non-finite input, which reference forwards
   // (groups of forward_batch windows) therefore skip the BatchNorm (from the inputs alone, so first: the window
   // slices below then need nothing from each other until the LSTM)

@@ -10,6 +10,7 @@
 #include "resnet.h"
 #include "wavlm.h"
 #include "w2vbert.h"
+#include "whisper.h"
 
 namespace sd {
 
@@ -26,6 +27,9 @@ struct TsvadConfig {
                               // 7: w2v-bert2 on 80-bin fbank paired to (B, T / 2, 160): the first w2vbert_layers Conformer
                               //    layers of w2v-BERT 2.0, hidden_states[-1] + conv k5 stride 2 + transformer (:805-840,
                               //    1225-1237)
+                              // 8: whisper on the raw waveform: the Whisper-PMFA encoder (whisper.h; `whisper` below),
+                              //    ln_post2 over the concatenated blocks + conv k5 stride 2 + transformer (:928-955,
+                              //    1216-1223)
   int max_num_speaker = 4;
   int rs_len = 4;
   int max_batch = 64;
@@ -55,6 +59,8 @@ struct TsvadConfig {
   bool wavlm_pre_ln = false;          // layer_norm_first
   int max_samples = 0;
   int w2vbert_layers = 0;             // variant 7: encoder layers that run (and that the state_dict holds)
+  // variant 8: the trunk's own geometry (sd_tsvad_create_whisper); its max_batch / max_samples / bf16 follow the above
+  WhisperConfig whisper;
 };
 
 class TsvadModel : public ModelCore {
@@ -125,14 +131,16 @@ class TsvadModel : public ModelCore {
   std::unique_ptr<RedimTrunk> redim_;   // ReDimNetB2, variant 4
   std::unique_ptr<WavlmTrunk> wavlm_;   // WavLM on the waveform, variants 5 and 6
   std::unique_ptr<W2vBertTrunk> w2v_;   // w2v-BERT 2.0 on paired fbank frames, variant 7
+  std::unique_ptr<WhisperTrunk> whisper_;   // Whisper-PMFA on the waveform, variant 8
   // values per frame of ref_speech: mel bins, or 1 for the waveform variants
-  int feat_dim() const { return wavlm_ ? 1 : cfg_.variant == 4 ? RedimTrunk::kF : 80; }
-  bool waveform() const { return cfg_.variant == 5 || cfg_.variant == 6; }
+  int feat_dim() const { return waveform() ? 1 : cfg_.variant == 4 ? RedimTrunk::kF : 80; }
+  bool waveform() const { return cfg_.variant == 5 || cfg_.variant == 6 || cfg_.variant == 8; }
   // the longest ref_speech time axis: fbank frames, or samples
   int max_input() const { return waveform() ? cfg_.max_samples : cfg_.max_fbank_frames; }
   // frames of the speech_down_or_up output for T_fb fbank frames (the conv's stride 2, the upsampler's 2 T', or
   // ECAPA's and ReDimNetB2's stride 4 on the unsubsampled time axis)
   int mix_frames(int Tf) const {
+    if (cfg_.variant == 8) return (WhisperTrunk::frames(Tf) - 1) / 2 + 1;   // Whisper's 50 frames / s likewise
     if (waveform()) return (WavlmTrunk::frames(Tf) - 1) / 2 + 1;   // WavLM's 50 frames / s through the stride-2 conv
     if (cfg_.variant == 3 || cfg_.variant == 4) return (Tf - 1) / 4 + 1;
     if (cfg_.variant == 7) return (Tf / 2 - 1) / 2 + 1;   // w2v-BERT's 50 frames / s through the stride-2 conv

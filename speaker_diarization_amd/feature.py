@@ -66,6 +66,15 @@ def slaney_mel(sample_rate: int, n_fft: int, n_mels: int = 23) -> np.ndarray:
     return w
 
 
+def whisper_mel_filters(n_mels: int = 80) -> np.ndarray:
+    """The mel matrix of whisper.log_mel_spectrogram, (n_mels, 201) float32: librosa.filters.mel(sr=16000, n_fft=400,
+    n_mels) (whisper/audio.py's mel_filters.npz), equal to transformers' WhisperFeatureExtractor(feature_size=
+    n_mels).mel_filters.T within 1e-7 (tests/test_whisper_host.py).  The Whisper encoder takes it as `mel_filters`."""
+    if n_mels not in (80, 128):
+        raise ValueError(f"n_mels must be 80 or 128, got {n_mels}")
+    return slaney_mel(16000, 400, n_mels)
+
+
 _mel_cache: dict = {}
 
 

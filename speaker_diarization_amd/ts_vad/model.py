@@ -57,19 +57,49 @@ class TSVADModel(_lib.Handle):
             wav = dict(w2vbert_layers=c.effective_w2vbert_cfg().num_hidden_layers)
             # the reference takes any even frame count; rs_len seconds at 100 frames / s is the longest a window gives
             self.max_fbank = max(self.max_fbank, c.rs_len * 100)
-        self._create(_lib.TsvadConfig(
+        wcfg = None
+        if c.variant == 8:
+            # whisper reads the raw waveform too; the trunk's geometry travels in its own struct
+            # (sd_tsvad_create_whisper: sd_tsvad_config keeps its fields)
+            if precision == "bf16x3":
+                raise ValueError("the whisper speech encoder does not build bf16x3 (the Whisper trunk runs in fp32 or "
+                                 "bf16)")
+            w = c.effective_whisper_cfg()
+            self.max_samples = c.rs_len * c.sample_rate
+            wav = dict(max_samples=self.max_samples)
+            wcfg = _lib.WhisperConfig(
+                n_mels=w.n_mels, n_audio_ctx=w.n_audio_ctx, n_audio_state=w.n_audio_state,
+                n_audio_head=w.n_audio_head, n_audio_layer=w.n_audio_layer, layer_st=w.layer_st, layer_ed=w.layer_ed,
+                precision=_lib.PRECISION[precision], max_batch=self.max_batch, max_samples=self.max_samples)
+        conf = _lib.TsvadConfig(
             variant=c.variant, max_num_speaker=c.max_num_speaker, rs_len=c.rs_len, max_batch=self.max_batch,
             max_fbank_frames=self.max_fbank, precision=_lib.PRECISION[precision],
             num_transformer_layer=c.num_transformer_layer, num_attention_head=c.num_attention_head,
             transformer_embed_dim=c.transformer_embed_dim,
             transformer_ffn_embed_dim=c.transformer_ffn_embed_dim, speaker_embed_dim=c.speaker_embed_dim,
-            backend=c.backend, d_state=c.d_state if c.backend else 0, expand=c.expand if c.backend else 0, **wav))
+            backend=c.backend, d_state=c.d_state if c.backend else 0, expand=c.expand if c.backend else 0, **wav)
+        if wcfg is None:
+            self._create(conf)
+        else:
+            import ctypes
+            h = ctypes.c_void_p()
+            _lib.call("sd_tsvad_create_whisper", ctypes.byref(conf), ctypes.byref(wcfg), ctypes.byref(h))
+            self._h = h
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Strict load (missing/unexpected keys raise RuntimeError like torch)."""
         if not strict:
             raise ValueError("the MI355X backend only supports strict=True loading")
-        self._load(unwrap_checkpoint(state_dict))
+        state = unwrap_checkpoint(state_dict)
+        if self.cfg.variant == 8:
+            # the Whisper front end's mel matrix: a constant computed on the host, not a reference key
+            from ..feature import whisper_mel_filters
+            state = dict(state)
+            if "speech_encoder.mel_filters" in state:
+                raise RuntimeError('Error(s) in loading state_dict: Unexpected key(s) in state_dict: '
+                                   '"speech_encoder.mel_filters"')
+            state["speech_encoder.mel_filters"] = whisper_mel_filters(self.cfg.whisper_n_mels)
+        self._load(state)
         return self
 
     def eval(self):
@@ -110,6 +140,9 @@ class TSVADModel(_lib.Handle):
                 raise ValueError(f"{self.cfg.speech_encoder_type} expects the raw waveform (B, n_samples), got "
                                  f"{tuple(ref_speech.shape)}")
             B, T_fb = ref_speech.shape
+            if self.cfg.variant == 8:
+                from ..ssl.whisper import check_samples
+                check_samples(self.cfg.effective_whisper_cfg(), T_fb)
         else:
             B, T_fb, F = ref_speech.shape
             assert F == self.cfg.n_mels, f"{self.cfg.speech_encoder_type} expects {self.cfg.n_mels}-dim fbank"

@@ -61,11 +61,35 @@ class TSVADConfig:
     # cfg.speech_encoder_config, a W2vBertConfig of speaker_diarization_amd.ssl.w2vbert; None: the published geometry.
     # select_encoder_layer_nums overrides its depth (model.py:816).
     w2vbert_cfg: Optional[Any] = None
+    # "whisper" (egs/magicdata-ramc/ts_vad2/model.py:928-955): whisper_cfg is a WhisperConfig of
+    # speaker_diarization_amd.ssl.whisper; None: the published ModelDimensions() with n_mels = whisper_n_mels, the only
+    # geometry the reference can build (its ModelDimensions() takes no argument there).
+    whisper_n_mels: int = 80
+    whisper_cfg: Optional[Any] = None
 
     @property
     def waveform_input(self) -> bool:
-        """ref_speech is the raw waveform (B, n_samples), not fbank: the WavLM speech encoders."""
-        return self.speech_encoder_type in ("WavLM", "WavLM_weight_sum")
+        """ref_speech is the raw waveform (B, n_samples), not fbank: the WavLM and Whisper speech encoders."""
+        return self.speech_encoder_type in ("WavLM", "WavLM_weight_sum", "whisper")
+
+    def effective_whisper_cfg(self):
+        """whisper_cfg, or the published ModelDimensions() with n_mels = whisper_n_mels."""
+        from .ssl.whisper import WhisperConfig
+        return self.whisper_cfg if self.whisper_cfg is not None else WhisperConfig(n_mels=self.whisper_n_mels)
+
+    def _whisper_variant(self) -> int:
+        se = self.speech_encoder_type
+        if self.ots_vad_style or (self.single_backend_type, self.multi_backend_type) != ("transformer", "transformer"):
+            raise ValueError(
+                f"unsupported TS-VAD configuration {se}/{self.single_backend_type}/{self.multi_backend_type}"
+                f"{' ots_vad_style ' + self.ots_vad_style if self.ots_vad_style else ''}: the whisper speech encoder "
+                "is built with the transformer single and multi back ends only (no Mamba2, no ots_vad)")
+        from .ssl.whisper import check_config
+        w = self.effective_whisper_cfg()
+        check_config(w)
+        if w.n_mels != self.whisper_n_mels:
+            raise ValueError(f"whisper_cfg.n_mels {w.n_mels} differs from whisper_n_mels {self.whisper_n_mels}")
+        return 8
 
     @property
     def wavlm_encoder_layers(self) -> int:
@@ -130,6 +154,8 @@ class TSVADConfig:
 
     @property
     def variant(self) -> int:
+        if self.speech_encoder_type == "whisper":
+            return self._whisper_variant()   # 8
         if self.waveform_input:
             return self._wavlm_variant()   # 5 "WavLM", 6 "WavLM_weight_sum" with wavlm_fuse_feat_post_norm
         if self.speech_encoder_type == "w2v-bert2":
@@ -158,7 +184,7 @@ class TSVADConfig:
                 f"{self.single_backend_type}/{self.multi_backend_type} (MI355X backend builds CAM++ "
                 "with transformer, mamba2 + transformer, mamba2 + mamba2 or conformer_ots_vad/lstm_ots_vad, "
                 "resnet34_wespeaker, ecapa_channel_1024_wespeaker and ReDimNetB2 with transformer, WavLM / "
-                "WavLM_weight_sum with transformer given wavlm_cfg, w2v-bert2 with transformer)")
+                "WavLM_weight_sum with transformer given wavlm_cfg, w2v-bert2 with transformer, whisper with transformer)")
         return 0
 
     @property
@@ -512,6 +538,14 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         k.append(("speech_down_or_up.0.weight", (se, w.output_hidden_size, 5), "conv1d"))
         k.append(("speech_down_or_up.0.bias", (se,), "small"))
         _bn(k, "speech_down_or_up.1.bn", se)
+    elif cfg.variant == 8:
+        # the Whisper-PMFA encoder + Conv1d(n_audio_state * n_cat -> D, k5, stride 2, pad 2)
+        # (egs/magicdata-ramc/ts_vad2/model.py:928-955); the back end is variant 0's
+        w = cfg.effective_whisper_cfg()
+        k = whisper_layout(w, "speech_encoder.")
+        k.append(("speech_down_or_up.0.weight", (se, w.out_dim, 5), "conv1d"))
+        k.append(("speech_down_or_up.0.bias", (se,), "small"))
+        _bn(k, "speech_down_or_up.1.bn", se)
     else:
         k = campplus_layout()
         if cfg.variant == 1:
@@ -525,7 +559,7 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         # 873-874); the reference registers it for every variant, its ots_vad forward never applies it
         k.append(("proj_layer.weight", (e, 2 * se), "linear"))
         k.append(("proj_layer.bias", (e,), "small"))
-    if cfg.variant in (0, 2, 3, 4, 5, 6, 7):
+    if cfg.variant in (0, 2, 3, 4, 5, 6, 7, 8):
         k.append(("pos_encoder.pe", (cfg.rs_len * cfg.label_rate, 1, e), "pe"))
         backend = cfg.backend
         if backend:
@@ -819,6 +853,13 @@ def tsvad_state_dict(cfg: TSVADConfig, seed: int = 777, spread: bool = False, dy
         if spread or dynamic:
             raise ValueError("no spread / dynamic calibration for the w2v-bert2 speech encoder")
         enc = w2vbert_state_dict(cfg.effective_w2vbert_cfg(), seed)
+        rest = synthetic_state_dict([e for e in layout if not e[0].startswith("speech_encoder.")], seed + 1)
+        return OrderedDict([("speech_encoder." + k, v) for k, v in enc.items()] + list(rest.items()))
+    if cfg.variant == 8:
+        # the encoder part: whisper_state_dict's sharp weights; the rest seeded as for every other variant
+        if spread or dynamic:
+            raise ValueError("no spread / dynamic calibration for the whisper speech encoder")
+        enc = whisper_state_dict(cfg.effective_whisper_cfg(), seed)
         rest = synthetic_state_dict([e for e in layout if not e[0].startswith("speech_encoder.")], seed + 1)
         return OrderedDict([("speech_encoder." + k, v) for k, v in enc.items()] + list(rest.items()))
     sd = synthetic_state_dict(layout, seed)
@@ -1166,6 +1207,71 @@ def w2vbert_state_dict(cfg, seed: int = 777):
         elif leaf == "output_dense":
             v = rng.standard_normal(shape) * (2.0 / np.sqrt(shape[1]))   # swish halves the hidden layer's scale
         else:   # projection, linear_v, linear_out, intermediate_dense, pointwise_conv2
+            v = rng.standard_normal(shape) / np.sqrt(shape[1])
+        sd[name] = np.ascontiguousarray(v, dtype=np.float32)
+    return sd
+
+
+def whisper_layout(cfg, prefix: str = "") -> list:
+    """Key layout of the reference's WhisperEncoder(cfg) (egs/magicdata-ramc/ts_vad2/whisper_encoder.py:150-191) under
+    `prefix`: (name, shape, kind) in state_dict order (parameters in registration order, the positional_embedding
+    buffer after them, as nn.Module.state_dict lists a module's own parameters before its buffers and both before its
+    children); attn.key has no bias (:66).  cfg: a WhisperConfig of speaker_diarization_amd.ssl.whisper or any object
+    with ModelDimensions' fields."""
+    D, M, L = cfg.n_audio_state, cfg.n_mels, cfg.n_audio_layer
+    W = D * (cfg.layer_ed - cfg.layer_st + 1)
+
+    def wb(p, *shape):
+        return [(p + ".weight", tuple(shape), "whisper"), (p + ".bias", (shape[0],), "whisper")]
+
+    k = [("positional_embedding", (cfg.n_audio_ctx, D), "whisper")]
+    k += wb("conv1", D, M, 3) + wb("conv2", D, D, 3)
+    for i in range(L):
+        p = f"layers.{i}."
+        k += wb(p + "attn.query", D, D)
+        k.append((p + "attn.key.weight", (D, D), "whisper"))
+        k += wb(p + "attn.value", D, D) + wb(p + "attn.out", D, D)
+        k += wb(p + "attn_ln", D)
+        k += wb(p + "mlp.0", 4 * D, D) + wb(p + "mlp.2", D, 4 * D)
+        k += wb(p + "mlp_ln", D)
+    k += wb("ln_post2", W)
+    return [(prefix + n, s, kind) for n, s, kind in k]
+
+
+def whisper_sinusoids(length: int, channels: int) -> np.ndarray:
+    """sinusoids() of whisper_encoder.py:50-58, the positional_embedding buffer the reference registers."""
+    inc = np.log(10000.0) / (channels // 2 - 1)
+    t = np.arange(length)[:, None] * np.exp(-inc * np.arange(channels // 2))[None, :]
+    return np.concatenate([np.sin(t), np.cos(t)], axis=1).astype(np.float32)
+
+
+# Seeded Whisper encoder init (whisper_layout).  query / key rows give per-head q . k / 8 a standard deviation of about 2.3
+# on LayerNorm'd rows, as for w2v-BERT above: the attention is sharp.  The positional table is the reference's sinusoids
+# PLUS 0.05 N noise: a model that recomputes the table instead of using the loaded buffer misses the goldens.
+WHISPER_QK_STD = 1.5
+
+
+def whisper_state_dict(cfg, seed: int = 888):
+    """Seeded Whisper-PMFA encoder weights under the reference class's key names; every bias and norm affine is
+    perturbed by 0.1 N, the other weights are drawn so that each sub-block's output is O(1) on the LayerNorm'd
+    stream."""
+    rng = np.random.default_rng(seed)
+    sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for name, shape, _ in whisper_layout(cfg):
+        leaf = name.rsplit(".", 2)[-2] if name.count(".") else name
+        if name == "positional_embedding":
+            v = whisper_sinusoids(*shape) + rng.standard_normal(shape) * 0.05
+        elif name.endswith(".bias"):
+            v = rng.standard_normal(shape) * 0.1
+        elif leaf in ("attn_ln", "mlp_ln", "ln_post2"):
+            v = 1.0 + rng.standard_normal(shape) * 0.1
+        elif leaf in ("conv1", "conv2"):
+            v = rng.standard_normal(shape) * (1.5 / np.sqrt(shape[1] * shape[2]))
+        elif leaf in ("query", "key"):
+            v = rng.standard_normal(shape) * (WHISPER_QK_STD / np.sqrt(shape[1]))
+        elif leaf == "2":   # mlp.2: GELU halves the hidden layer's scale
+            v = rng.standard_normal(shape) * (2.0 / np.sqrt(shape[1]))
+        else:   # value, out, mlp.0
             v = rng.standard_normal(shape) / np.sqrt(shape[1])
         sd[name] = np.ascontiguousarray(v, dtype=np.float32)
     return sd
