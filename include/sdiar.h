@@ -839,6 +839,60 @@ int sd_fseend_stream_stats(const sd_fseend_stream* s, int64_t* enc_runs, int64_t
 int sd_fseend_stream_debug_counters(const sd_fseend_stream* s, unsigned* host_out, int cap, int* n, void* stream);
 int sd_fseend_stream_destroy(sd_fseend_stream* s);
 
+/* Test-only single ops of the FS-EEND streaming kernels (csrc/stream_ops.hip).  Every pointer is a device pointer
+ * and the data is already in its io dtype (fp32, or bf16 where a *_bf16 flag says so); nothing is allocated or
+ * zeroed for the caller: workspaces, counters and cursors are the caller's.  Counters are unsigned words zeroed
+ * ONCE; every launch leaves them at 0 again, so launches that run one after another share them.
+ *
+ * sd_attn_decode_blocks: partials per (sequence, head) that a history of max_keys rows needs (n_blocks below).
+ * sd_op_attn_decode: chunked causal attention, head size 64.  Strides in elements: query i of sequence s at
+ *   q + i q_tok + s q_seq (+ 64 head), key / value j at k / v + j kv_tok + s kv_seq (+ 64 head), output at
+ *   out + i o_tok + s o_seq (+ 64 head).  Query i sits at *pos + i and sees key j iff j <= *pos + i + delay and
+ *   j < *pos + nq.  1 <= nq <= 32; k, v 16-byte aligned with strides of 16-byte multiples.  ws: nseq nh n_blocks nq
+ *   66 floats, n_blocks >= sd_attn_decode_blocks(max_keys).  cnt (optional): nseq nh counters; the last block
+ *   of each (sequence, head) merges the partials in the same launch (NULL: a separate combine launch).  wo, bo, o2,
+ *   ws2, cnt2 (optional, all or none, with cnt): o2 = out-row W_oᵀ + bo in the same launch when nq == 1 and nh <= 4,
+ *   wo (nh 64, nh 64) in the io dtype and 16-byte aligned, o2 rows laid out as out's with nh 64 values each, ws2: nseq
+ *   nh nq nh 64 floats, cnt2: nseq counters; `out` is not written then.  *ran_out_proj = 1 iff that path ran.
+ * sd_op_stream_slot_block: y = LN(ln_x + ln_t) -> ln_out (fp32); out = MHA over the C slots of each of the c frames
+ *   of y (w_in (3D, D), w_out (D, D), weights in the w dtype), rows (c C, D).  ln_t may be NULL.  ws: nh c C D
+ *   floats, cnt: 1 counter.  *ran = 0 and nothing launched unless D == 256, nh == 4, c C <= 16, C <= 8, ws and cnt
+ *   set and ln_x, ln_g, ln_b, ln_out, w_in, w_out 16-byte aligned.
+ * sd_op_stream_ffn_pair: y = LN(ln_x + ln_t) -> ln_out; out = relu(y W1ᵀ + b1) W2ᵀ + b2, w1 (F, D), w2 (D, F).
+ *   ws: 128 * 8 * D floats, cnt: 1 counter.  *ran = 0 and nothing launched unless D == 256, F == 2048,
+ *   1 <= n <= 8, ln_g / ln_b / ln_out / ws / cnt set and w1, w2, ln_x, ln_out, out, ws, b2 16-byte aligned.
+ * sd_op_kv_append: dst row (*cursor mult + r) = src row r for r < rows; rows of width_bytes at byte strides
+ *   ld_src_bytes / ld_dst_bytes, all 16-byte multiples, 16-byte aligned buffers.
+ * sd_op_gather_window: dst (rows, D) = hist rows [*cursor - pad, *cursor - pad + rows), zero outside [0, *n_valid).
+ * sd_op_cursor_advance: *cursor += by; *mirror (optional) = the new value.
+ * sd_op_stream_enc_finish: hist row (*cursor + r) = LN(x + t)[r] for r < c (t optional; D in 256/512/768/1024), then
+ *   *cursor += c and *mirror (optional) = *cursor.
+ * sd_op_stream_dec_finish: a = LN(x + t) over the c C rows, scores[r] = emb[r / C] . a[r] / |a[r]| (emb (c, D)), then
+ *   *cursor += c. */
+int sd_attn_decode_blocks(int max_keys);
+int sd_op_attn_decode(const void* q, int64_t q_tok, int64_t q_seq, const void* k, const void* v, int64_t kv_tok,
+                      int64_t kv_seq, void* out, int64_t o_tok, int64_t o_seq, int nseq, int nq, int nh, float scale,
+                      const int* pos, int delay, int max_keys, int io_bf16, float* ws, int n_blocks, unsigned* cnt,
+                      const void* wo, const float* bo, void* o2, float* ws2, unsigned* cnt2, int* ran_out_proj,
+                      void* stream);
+int sd_op_stream_slot_block(const float* ln_x, const void* ln_t, int t_bf16, const float* ln_g, const float* ln_b,
+                            float eps, float* ln_out, const void* w_in, const float* b_in, const void* w_out,
+                            const float* b_out, int w_bf16, void* out, int out_bf16, float* ws, unsigned* cnt, int c,
+                            int C, int D, int nh, float scale, int* ran, void* stream);
+int sd_op_stream_ffn_pair(const float* ln_x, const void* ln_t, int t_bf16, const float* ln_g, const float* ln_b,
+                          float eps, float* ln_out, const void* w1, const float* b1, const void* w2, const float* b2,
+                          int w_bf16, void* out, int out_bf16, float* ws, unsigned* cnt, int n, int D, int F, int* ran,
+                          void* stream);
+int sd_op_kv_append(const void* src, int64_t ld_src_bytes, int rows, int width_bytes, void* dst, int64_t ld_dst_bytes,
+                    const int* cursor, int mult, void* stream);
+int sd_op_gather_window(const float* hist, int D, const int* cursor, const int* n_valid, int pad, int rows, float* dst,
+                        void* stream);
+int sd_op_cursor_advance(int* cursor, int by, int* mirror, void* stream);
+int sd_op_stream_enc_finish(const float* x, const void* t, int t_bf16, const float* g, const float* b, float eps, int c,
+                            int D, float* hist, int* cursor, int* mirror, void* stream);
+int sd_op_stream_dec_finish(const float* x, const void* t, int t_bf16, const float* g, const float* b, float eps, int c,
+                            int C, int D, const float* emb, float* scores, int* cursor, void* stream);
+
 /* feature.stft + feature.transform('logmel23_mn' | 'logmel23') + feature.splice + [::subsampling]
  * (speaker_diarization/feature.py:155-184, 56-73, 130-152; eend_eda/infer_eda.py:94-98).
  * wav: device f32 (n_samples) (soundfile values, computed in float64 like the reference);

@@ -326,6 +326,24 @@ _SIGS = {
     "sd_fseend_stream_stats": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int), POINTER(c_int)]),
     "sd_fseend_stream_debug_counters": (c_int, [c_void_p, POINTER(ctypes.c_uint), c_int, POINTER(c_int), c_void_p]),
     "sd_fseend_stream_destroy": (c_int, [c_void_p]),
+    "sd_attn_decode_blocks": (c_int, [c_int]),
+    "sd_op_attn_decode": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+                                  c_int64, c_int, c_int, c_int, c_float, c_void_p, c_int, c_int, c_int, c_void_p,
+                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int),
+                                  c_void_p]),
+    "sd_op_stream_slot_block": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_int, c_int, c_int, c_int, c_float, POINTER(c_int), c_void_p]),
+    "sd_op_stream_ffn_pair": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                      c_int, c_int, POINTER(c_int), c_void_p]),
+    "sd_op_kv_append": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    "sd_op_gather_window": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sd_op_cursor_advance": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "sd_op_stream_enc_finish": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sd_op_stream_dec_finish": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
     "sd_eend_features": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                  c_void_p, c_void_p, c_int, c_void_p]),
     "sd_fbank_kaldi": (c_int, [c_void_p, c_int64, c_float, c_int, c_void_p, c_int, c_void_p, c_void_p]),

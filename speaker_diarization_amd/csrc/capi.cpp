@@ -507,6 +507,113 @@ int64_t sd_fseend_stream_device_bytes(const sd_fseend_stream* h) { return device
 
 int sd_fseend_stream_destroy(sd_fseend_stream* h) { return destroy(h); }
 
+// Test-only single ops of the streaming kernels (stream_ops.hip): raw device pointers, the caller's own
+// workspaces, counters and cursors, data already in the io dtype.
+int sd_attn_decode_blocks(int max_keys) { return max_keys < 1 ? 0 : sd::attn_decode_blocks(max_keys); }
+
+int sd_op_attn_decode(const void* q, int64_t q_tok, int64_t q_seq, const void* k, const void* v, int64_t kv_tok,
+                      int64_t kv_seq, void* out, int64_t o_tok, int64_t o_seq, int nseq, int nq, int nh, float scale,
+                      const int* pos, int delay, int max_keys, int io_bf16, float* ws, int n_blocks, unsigned* cnt,
+                      const void* wo, const float* bo, void* o2, float* ws2, unsigned* cnt2, int* ran_out_proj,
+                      void* stream) {
+  return guard([&] {
+    SD_CHECK(q && k && v && out && pos && ws && ran_out_proj, sd::kErrInvalid, "attn_decode: null argument");
+    SD_CHECK(nseq >= 1 && nh >= 1 && max_keys >= 1 && delay >= 0, sd::kErrInvalid, "attn_decode: bad argument");
+    SD_CHECK(io_bf16 == 0 || io_bf16 == 1, sd::kErrInvalid, "attn_decode: io_bf16 must be 0 or 1");
+    // K rows are read as 16-byte vectors
+    const int64_t v16 = io_bf16 ? 8 : 4;
+    SD_CHECK(((uintptr_t)k | (uintptr_t)v) % 16 == 0 && kv_tok % v16 == 0 && kv_seq % v16 == 0, sd::kErrInvalid,
+             "attn_decode: k / v must be 16-byte aligned, their strides 16-byte multiples");
+    SD_CHECK(!(wo || bo || o2 || ws2 || cnt2) || (cnt && wo && bo && o2 && ws2 && cnt2), sd::kErrInvalid,
+             "attn_decode: the out-projection needs cnt, wo, bo, o2, ws2 and cnt2 together");
+    sd::DecodeAttnArgs a;
+    a.q = q; a.q_tok = q_tok; a.q_seq = q_seq;
+    a.k = k; a.v = v; a.kv_tok = kv_tok; a.kv_seq = kv_seq;
+    a.out = out; a.o_tok = o_tok; a.o_seq = o_seq;
+    a.nseq = nseq; a.nq = nq; a.nh = nh; a.hd = 64; a.scale = scale;
+    a.pos = pos; a.delay = delay; a.max_keys = max_keys; a.n_blocks = n_blocks; a.ws = ws; a.io_bf16 = io_bf16 != 0;
+    a.cnt = cnt; a.wo = wo; a.bo = bo; a.o2 = o2; a.ws2 = ws2; a.cnt2 = cnt2;
+    *ran_out_proj = 0;
+    *ran_out_proj = sd::attn_decode(a, S(stream)) ? 1 : 0;
+  });
+}
+
+int sd_op_stream_slot_block(const float* ln_x, const void* ln_t, int t_bf16, const float* ln_g, const float* ln_b,
+                            float eps, float* ln_out, const void* w_in, const float* b_in, const void* w_out,
+                            const float* b_out, int w_bf16, void* out, int out_bf16, float* ws, unsigned* cnt, int c,
+                            int C, int D, int nh, float scale, int* ran, void* stream) {
+  return guard([&] {
+    SD_CHECK(ln_x && ln_g && ln_b && ln_out && w_in && b_in && w_out && b_out && out && ran, sd::kErrInvalid,
+             "stream_slot_block: null argument");
+    sd::SlotBlockArgs a;
+    a.ln_x = ln_x; a.ln_t = ln_t; a.t_bf16 = t_bf16 != 0; a.ln_g = ln_g; a.ln_b = ln_b; a.eps = eps; a.ln_out = ln_out;
+    a.w_in = w_in; a.b_in = b_in; a.w_out = w_out; a.b_out = b_out; a.w_bf16 = w_bf16 != 0;
+    a.out = out; a.out_bf16 = out_bf16 != 0; a.ws = ws; a.cnt = cnt;
+    a.c = c; a.C = C; a.D = D; a.nh = nh; a.scale = scale;
+    *ran = 0;
+    *ran = sd::stream_slot_block(a, S(stream)) ? 1 : 0;
+  });
+}
+
+int sd_op_stream_ffn_pair(const float* ln_x, const void* ln_t, int t_bf16, const float* ln_g, const float* ln_b,
+                          float eps, float* ln_out, const void* w1, const float* b1, const void* w2, const float* b2,
+                          int w_bf16, void* out, int out_bf16, float* ws, unsigned* cnt, int n, int D, int F, int* ran,
+                          void* stream) {
+  return guard([&] {
+    SD_CHECK(ln_x && w1 && b1 && w2 && b2 && out && ran, sd::kErrInvalid, "stream_ffn_pair: null argument");
+    sd::FfnPairArgs a;
+    a.ln_x = ln_x; a.ln_t = ln_t; a.t_bf16 = t_bf16 != 0; a.ln_g = ln_g; a.ln_b = ln_b; a.eps = eps; a.ln_out = ln_out;
+    a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w_bf16 = w_bf16 != 0;
+    a.out = out; a.out_bf16 = out_bf16 != 0; a.ws = ws; a.cnt = cnt; a.n = n; a.D = D; a.F = F;
+    *ran = 0;
+    *ran = sd::stream_ffn_pair(a, S(stream)) ? 1 : 0;
+  });
+}
+
+int sd_op_kv_append(const void* src, int64_t ld_src_bytes, int rows, int width_bytes, void* dst, int64_t ld_dst_bytes,
+                    const int* cursor, int mult, void* stream) {
+  return guard([&] {
+    SD_CHECK(src && dst && cursor, sd::kErrInvalid, "kv_append: null argument");
+    SD_CHECK(rows >= 0 && width_bytes >= 16 && mult >= 1 && ld_src_bytes >= width_bytes && ld_dst_bytes >= width_bytes,
+             sd::kErrInvalid, "kv_append: bad argument");
+    sd::kv_append(src, ld_src_bytes, rows, width_bytes, dst, ld_dst_bytes, cursor, mult, S(stream));
+  });
+}
+
+int sd_op_gather_window(const float* hist, int D, const int* cursor, const int* n_valid, int pad, int rows, float* dst,
+                        void* stream) {
+  return guard([&] {
+    SD_CHECK(hist && cursor && n_valid && dst, sd::kErrInvalid, "gather_window: null argument");
+    SD_CHECK(D >= 1 && rows >= 1 && pad >= 0, sd::kErrInvalid, "gather_window: bad argument");
+    sd::gather_window(hist, D, cursor, n_valid, pad, rows, dst, S(stream));
+  });
+}
+
+int sd_op_cursor_advance(int* cursor, int by, int* mirror, void* stream) {
+  return guard([&] {
+    SD_CHECK(cursor, sd::kErrInvalid, "cursor_advance: null argument");
+    sd::cursor_advance(cursor, by, mirror, S(stream));
+  });
+}
+
+int sd_op_stream_enc_finish(const float* x, const void* t, int t_bf16, const float* g, const float* b, float eps, int c,
+                            int D, float* hist, int* cursor, int* mirror, void* stream) {
+  return guard([&] {
+    SD_CHECK(x && g && b && hist && cursor, sd::kErrInvalid, "stream_enc_finish: null argument");
+    SD_CHECK(c >= 1 && D >= 256, sd::kErrInvalid, "stream_enc_finish: D must be 256/512/768/1024, c >= 1");
+    sd::stream_enc_finish(x, t, t_bf16 != 0, g, b, eps, c, D, hist, cursor, mirror, S(stream));
+  });
+}
+
+int sd_op_stream_dec_finish(const float* x, const void* t, int t_bf16, const float* g, const float* b, float eps, int c,
+                            int C, int D, const float* emb, float* scores, int* cursor, void* stream) {
+  return guard([&] {
+    SD_CHECK(x && g && b && emb && scores && cursor, sd::kErrInvalid, "stream_dec_finish: null argument");
+    SD_CHECK(c >= 1 && C >= 1 && D >= 256, sd::kErrInvalid, "stream_dec_finish: D must be 256/512/768/1024, c and C >= 1");
+    sd::stream_dec_finish(x, t, t_bf16 != 0, g, b, eps, c, C, D, emb, scores, cursor, S(stream));
+  });
+}
+
 int sd_eend_features(const float* wav, int64_t n_samples, int frame_size, int frame_shift, int n_frames,
                      const float* mel_fb, int n_mels, int mean_norm, int context_size, int subsampling,
                      double* work, float* out, int ld_out, void* stream) {

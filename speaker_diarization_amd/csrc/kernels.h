@@ -827,8 +827,8 @@ int attn_decode_blocks(int max_keys);
 // ONE launch of nh workgroups (one per head): a head's q/k/v and attention stay in LDS, its out-projection
 // partial (the head's 64 input features) is published write-through and the last workgroup to count itself
 // sums the nh partials in head order (MI355X guide hand-off row 1; cnt monotonic, zeroed once).
-// Supported: D == 256, D / nh == 64, c * C <= 16, C <= 8; returns false otherwise (caller runs the three-launch
-// path).
+// Supported: D == 256, D / nh == 64, c * C <= 16, C <= 8, 16-B aligned ln_x / ln_g / ln_b / ln_out / w_in / w_out
+// (ln_t: 8 B when bf16); returns false otherwise (caller runs the three-launch path).
 struct SlotBlockArgs {
   const float* ln_x = nullptr;
   const void* ln_t = nullptr;

@@ -340,7 +340,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(DecodeAttnArgs a) {
 }
 
 // grid (nseq*nh, cdiv(nq, 4)), 256 threads: wave -> query, lane -> head dim; merges the
-// nblk (<= 64) block partials (lane-parallel max / weights, shuffled weights for o).
+// nblk (<= kMaxBlk = 32) block partials (lane-parallel max / weights, shuffled weights for o).
 template <bool IOBF>
 __global__ __launch_bounds__(256) void attn_combine_kernel(DecodeAttnArgs a, int nblk) {
   const int qi = blockIdx.y * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -924,6 +924,9 @@ bool stream_slot_block(const SlotBlockArgs& a, hipStream_t st) {
   const int n = a.c * a.C;
   if (a.D != kSlotD || a.nh * kHD != a.D || a.nh > 8 || n < 1 || n > kSlotRows || a.C > 8 || !a.ws || !a.cnt)
     return false;
+  auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  if (!al(a.ln_x) || !al(a.ln_g) || !al(a.ln_b) || !al(a.ln_out) || !al(a.w_in) || !al(a.w_out)) return false;
+  if (a.ln_t && reinterpret_cast<uintptr_t>(a.ln_t) % (a.t_bf16 ? 8 : 16) != 0) return false;
   ProfScope prof("slot_block", 2.0 * n * a.D * 4.0 * a.D + 4.0 * n * a.C * a.D, (a.w_bf16 ? 2.0 : 4.0) * 4 * a.D * a.D, st);
   if (n <= 2) launch_slot_block<2>(a, st);
   else if (n <= 4) launch_slot_block<4>(a, st);
