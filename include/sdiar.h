@@ -135,7 +135,24 @@ typedef struct {
                                      for sd_tsvad_forward), in order, and never cross groups, so logits depend on
                                      which windows share a group; `force` (a slice of a reference batch) is refused.
                                      mamba_ssm is CUDA-only: the arithmetic restates its published Mamba2 module and
-                                     no reference-run golden pins it (parity unpinned, like the Conformer) */
+                                     no reference-run golden pins it (parity unpinned, like the Conformer)
+                                     4: single_backend_type "conformer", multi_backend_type "transformer"
+                                     5: "conformer" for both
+                                     (egs/magicdata-ramc/ts_vad2/model.py:290-313, 451-463, 1340-1351, 1382-1390; the
+                                     recipes pair them with CAM++, 2 layers, rs_len 4 / 6 / 8, e.g.
+                                     egs/magicdata-ramc/run_ts_vad2_hltsz.sh:2571-2700).  variant 0 only, SD_ERR_INVALID
+                                     otherwise; d_state / expand are not read.  Each back end is
+                                     torchaudio.models.Conformer(E, num_attention_head, transformer_ffn_embed_dim,
+                                     num_transformer_layer, depthwise_conv_kernel_size 31): use_group_norm False, so the
+                                     conv module carries an eval BatchNorm1d (keys {single,multi}_backend.
+                                     conformer_layers.{i}.*, conv_module.sequential.3.{weight, bias, running_mean,
+                                     running_var}; num_batches_tracked accepted and ignored).  The sequence axis is TIME
+                                     (batch-first calls, lengths all T, no padding mask): windows stay independent and
+                                     forward_batch only scopes the BatchNorm1D bypass, as for backend 0; backend_down.0
+                                     reads E * max_num_speaker channels.  The Conformer arithmetic restates torchaudio
+                                     2.5.1 (parity unpinned); everything around it is pinned by reference runs
+                                     (tests/golden/tsvad_conf_*.npz).
+                                     3 is not a back end: SD_ERR_INVALID */
   int d_state;                    /* backend 1 / 2: TSVADConfig.d_state (reference default 64, the recipe 128): a
                                      multiple of 16 up to 256 */
   int expand;                     /* backend 1 / 2: TSVADConfig.expand (4): expand * transformer_embed_dim must be a
@@ -1093,7 +1110,7 @@ int sd_op_glu_dwconv(const void* x, int S, int T, int C, const float* w, const f
  *         gn_partial, A is first replaced by silu(GroupNorm(A) * gn_g + gn_b), one group per gn_T rows, statistics
  *         from gn_partial (M / gn_T, gn_nblk, 2) = (sum, sum of squares) partial sums;
  *   per FFN i < n_ffn: acc += w2 silu(w1 LN(acc; ln_g, ln_b) + b1) + b2, then acc = LN(acc; post_g, post_b) when post_g
- *         is set; w1 (hidden, 384), w2 (384, hidden) fp32, hidden % 32 == 0, <= 1024.  Nothing is scaled here: a caller
+ *         is set; w1 (hidden, 384), w2 (384, hidden) fp32, hidden % 32 == 0, <= 1536.  Nothing is scaled here: a caller
  *         that wants the module's 1/2 passes w2 / b2 halved;
  *   Xo = acc (fp32, nullable, may equal X); y = LN(acc; y_g, y_b) as bf16 bits (nullable); yt (nullable) = bf16(acc) in
  *         the speakers-to-channels layout (M / (yt_NS T_seq), T_seq, yt_NS * 384).
@@ -1135,6 +1152,11 @@ int sd_op_rowprog(const sd_rowprog_op* op, void* stream);
  * non-NULL, x NULL, precision 1, use_generic 0): the input rows of sequence s = b * NS + spk are [ts[s] | mix[b][t]]
  * (ts (S, 192), mix (S / NS, Tmix, ldmix) fp32, zeros for t >= Tmix) and out is bf16 (S / NS, T, NS * 384).
  * Synchronises `stream`. */
+/* Measurement and tests only (tools/conformer_backend_probe.py): which bf16 path serves a TS-VAD conformer back end
+ * (backend 4 / 5) whose FFN hidden size is past 1024.  0: the shipped rule, run_conformer per layer (the fused stack
+ * measured no faster there); 1: the row programs, the single stack's last one writing the speakers-to-channels layout.
+ * Process-wide; read by each forward. */
+int sd_debug_conformer_wide_route(int route);
 int sd_op_conformer_stack(const float* x, int S, int T, const float* weights, int64_t n_weights, int n_layers,
                           int ffn_dim, int nh, int kernel, int group_norm, const int* key_len, int precision,
                           int use_generic, const float* ts, const float* mix, int ldmix, int Tmix, int NS, void* out,

@@ -37,7 +37,8 @@ class TsvadConfig(ctypes.Structure):
         ("transformer_embed_dim", c_int),
         ("transformer_ffn_embed_dim", c_int),
         ("speaker_embed_dim", c_int),
-        ("backend", c_int),    # 0 the variant's own; 1 mamba2 + transformer; 2 mamba2 + mamba2 (variant 0 only)
+        ("backend", c_int),    # 0 the variant's own; 1 mamba2 + transformer; 2 mamba2 + mamba2; 4 conformer + transformer;
+                               # 5 conformer + conformer (1, 2, 4, 5: variant 0 only)
         ("d_state", c_int),
         ("expand", c_int),
         # variants 5 / 6 (WavLM / WavLM_weight_sum on the raw waveform); all zero otherwise
@@ -368,6 +369,7 @@ _SIGS = {
     "sd_op_glu_dwconv": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sd_op_rowprog": (c_int, [POINTER(RowprogOp), c_void_p]),
+    "sd_debug_conformer_wide_route": (c_int, [c_int]),
     "sd_op_conformer_stack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                       c_void_p]),

@@ -2099,6 +2099,13 @@ int sd_op_rowprog(const sd_rowprog_op* op, void* stream) {
   });
 }
 
+int sd_debug_conformer_wide_route(int route) {
+  return guard([&] {
+    SD_CHECK(route == 0 || route == 1, sd::kErrInvalid, "conformer wide route must be 0 or 1");
+    sd::conformer_wide_route_debug(route);
+  });
+}
+
 int sd_op_conformer_stack(const float* x, int nseq, int T, const float* weights, int64_t n_weights, int n_layers,
                           int ffn_dim, int nh, int kernel, int group_norm, const int* key_len, int precision,
                           int use_generic, const float* ts, const float* mix, int ldmix, int Tmix, int NS, void* out,
@@ -2198,7 +2205,7 @@ int sd_op_conformer_stack(const float* x, int nseq, int T, const float* weights,
         for (const sd::ConformerL& L : Ls) sd::run_conformer(L, X, nseq, T, E, nh, kernel, key_len, w, st);
       } else {
         SD_CHECK(sd::conformer_stack_fused(Ls, E, bf), sd::kErrInvalid,
-                 "conformer_stack: use_generic 0 needs the row programs (precision 1, ffn_dim % 32 == 0, <= 1024)");
+                 "conformer_stack: use_generic 0 needs the row programs (precision 1, ffn_dim % 32 == 0, <= 1536)");
         sd::run_conformer_stack(Ls, X, nseq, T, E, nh, kernel, key_len, w, st);
       }
     }

@@ -245,6 +245,16 @@ bool conformer_stack_fused(const std::vector<ConformerL>& Ls, int E, bool bf16) 
   return fused;
 }
 
+static int g_wide_route = 0;
+void conformer_wide_route_debug(int route) { g_wide_route = route; }
+
+bool conformer_stack_default_fused(const std::vector<ConformerL>& Ls, int E, bool bf16) {
+  if (!conformer_stack_fused(Ls, E, bf16)) return false;
+  for (const ConformerL& L : Ls)
+    if (L.rp_hidden > 1024 && g_wide_route == 0) return false;
+  return true;
+}
+
 void run_conformer_stack(const std::vector<ConformerL>& Ls, float* X, int S, int T, int E, int nh, int kernel,
                          const int* key_len, const EncoderWork& w, hipStream_t st, const SpeakerStreams* io) {
   const bool fused = conformer_stack_fused(Ls, E, w.bf16);
@@ -276,7 +286,7 @@ void run_conformer_stack(const std::vector<ConformerL>& Ls, float* X, int S, int
   {
     RowProgArgs r;
     r.X = X; r.Xo = X; r.M = rows;
-    if (io) {
+    if (io && io->ts) {
       r.X = nullptr; r.x_ts = io->ts; r.x_mix = io->mix; r.x_ldmix = io->ldmix; r.x_Tmix = io->Tmix;
       r.x_NS = io->NS; r.T_seq = T;
     }
@@ -342,7 +352,7 @@ void run_conformer_stack(const std::vector<ConformerL>& Ls, float* X, int S, int
         r.y = y.p; r.y_g = Ln.at_lng; r.y_b = Ln.at_lnb;
         r.xo_tiled = tiled;
         r.y_tiled = tiled_y;
-      } else if (io) {
+      } else if (io && io->out) {
         r.Xo = nullptr; r.yt = io->out; r.yt_NS = io->NS; r.T_seq = T;
       }   // else: the stack's output X, row-major (in place over the tiled input: a tile is read whole first)
       rowprog(r, "rowprog_pw2_ffn", st);

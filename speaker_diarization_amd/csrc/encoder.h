@@ -94,14 +94,22 @@ void run_conformer(const ConformerL& L, float* X, int S, int T, int E, int nh, i
 // TS-VAD speaker streams around a fused (row-program) conformer stack: the first program builds its input
 // rows [ts | mix] on load (no build_speaker_input pass) and the last writes bf16 rows straight into the
 // speakers-to-channels layout (no speakers_to_channels pass, no fp32 output).  Only with
-// conformer_stack_fused() true.
+// conformer_stack_fused() true.  The two ends are independent: ts == nullptr keeps the plain X input (TS-VAD's
+// "conformer" single back end, whose rows carry proj_layer and the positional encoding), out == nullptr the X output.
 struct SpeakerStreams {
-  const float* ts = nullptr;    // (B*NS, 192)
+  const float* ts = nullptr;    // (B*NS, 192); nullptr: the stack reads X
   const float* mix = nullptr;   // (B, Tmix, ldmix), columns 0..191
   int ldmix = 0, Tmix = 0, NS = 0;
-  void* out = nullptr;          // bf16 (B, T, NS*E)
+  void* out = nullptr;          // bf16 (B, T, NS*E); nullptr: the stack writes X
 };
 bool conformer_stack_fused(const std::vector<ConformerL>& Ls, int E, bool bf16);
+// The shipped choice for a stack that could run fused.  Up to FFN hidden 1024 (ots_vad v1, SSND): the fused stack.  Past
+// it (TS-VAD's conformer back ends, hidden 1536, 4 heads: the in-projection GEMM + attention() between the programs, no
+// mha_block) the fused stack measured no faster than run_conformer per layer (4.107 against 4.109 ms per
+// 64-window forward, spread 0.05 ms), so those stacks run per layer.  conformer_wide_route_debug(1) (measurement and
+// tests: sd_debug_conformer_wide_route) sends them to the fused stack; 0 restores the shipped rule.
+bool conformer_stack_default_fused(const std::vector<ConformerL>& Ls, int E, bool bf16);
+void conformer_wide_route_debug(int route);
 void run_conformer_stack(const std::vector<ConformerL>& Ls, float* X, int S, int T, int E, int nh, int kernel,
                          const int* key_len, const EncoderWork& w, hipStream_t st,
                          const SpeakerStreams* io = nullptr);

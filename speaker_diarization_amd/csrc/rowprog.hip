@@ -53,7 +53,7 @@ constexpr int kFrag = 512;            // bf16 per fragment (64 lanes x 8)
 constexpr int kPieceFrags = 24;
 constexpr int kPiece = kPieceFrags * kFrag;   // 12288 bf16 = 24 KiB
 constexpr int kNSlot = 5;
-constexpr int kMaxHidden = 1024;
+constexpr int kMaxHidden = 1536;          // TS-VAD's conformer back ends: transformer_ffn_embed_dim 1536
 constexpr int kPD = 3;                // fragment reads in flight ahead of the MFMA that uses them
 constexpr int kRefillAt = 8;          // the DMA refill is issued after this many MFMAs of a piece (round 6 sweep 0 / 3 / 8 / 16 / 22: 8)
 // LDS parameter block (floats): b0 | per FFN: post_g post_b b2 (D each) b1 (kMaxHidden) | y_g y_b
@@ -63,6 +63,7 @@ constexpr int kPrmGn = kPrmY + 2 * kD;   // GroupNorm gamma | beta of the pre-GE
 constexpr int kPrmFloats = (kPrmGn + 2 * kD + 255) / 256 * 256;   // padded to whole KiB
 constexpr size_t kSmemBytes = sizeof(uint16_t) * (size_t)kNSlot * kPiece + sizeof(float) * kPrmFloats;
 static_assert((kPrmFloats * 4) % 1024 == 0, "ring slots stay 1-KiB aligned");
+// 5 slots x 24 KiB + 29 KiB of parameters (7424 floats: 384 + 2 x 2688 + 768 + 768, padded) = 149 KiB
 static_assert(kSmemBytes <= 160 * 1024, "LDS budget");
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 

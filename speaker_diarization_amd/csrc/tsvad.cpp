@@ -28,6 +28,8 @@
 //          backend 1 / 2 (variant 0; egs/magicdata-ramc/ts_vad2/model.py:377-403, 488-504, 1337-1399): the per-speaker
 //          encoder, and with 2 the multi-speaker one (+ multi_backend_proj), is a bidirectional Mamba2BlockV2 (mamba2.h)
 //          that scans along the WINDOWS of a reference forward call; backend_down reads 2 E NS channels
+//          backend 4 / 5 (variant 0; magicdata model.py:290-313, 451-463, 1340-1351, 1382-1390): the per-speaker encoder,
+//          and with 5 the multi-speaker one, is a torchaudio Conformer (BatchNorm conv module, kernel 31) along time
 //        ots_vad_backend, variant 1 (forward_common_ots_vad, model.py:669-756):
 //          GSP + gsp_fc -> [ts_embed | mix] -> 6-layer Conformer per speaker (conformer_slice: the fused stack,
 //          which runs inside each window slice) -> BiLSTM(1536 -> 2x256) -> fc
@@ -47,12 +49,15 @@ ConvL TsvadModel::conv_bn(const std::string& wname, const std::string& bn, const
 }
 
 void TsvadModel::validate(const TsvadConfig& c) {
-  SD_CHECK(c.backend >= 0 && c.backend <= 2, kErrInvalid, "backend must be 0, 1 or 2");
-  if (c.backend != 0) {
+  SD_CHECK(c.backend >= 0 && c.backend <= 5 && c.backend != 3, kErrInvalid, "backend must be 0, 1, 2, 4 or 5");
+  if (c.backend == 1 || c.backend == 2) {
     SD_CHECK(c.variant == 0, kErrInvalid,
              "backend 1 / 2 (Mamba2 back ends) is built for variant 0 (speech_encoder_type CAM++) only");
     Mamba2Stack::validate(c.embed_dim, c.d_state, c.expand);
   }
+  if (c.backend == 4 || c.backend == 5)   // d_state / expand are not read
+    SD_CHECK(c.variant == 0, kErrInvalid,
+             "backend 4 / 5 (conformer back ends) is built for variant 0 (speech_encoder_type CAM++) only");
   if (c.variant == 5 || c.variant == 6) {
     SD_CHECK(c.backend == 0, kErrInvalid,
              "the WavLM speech encoders (variants 5 / 6) are built with the transformer back end only (backend 0)");
@@ -93,6 +98,22 @@ void TsvadModel::validate(const TsvadConfig& c) {
            "wide input): not supported for ots_vad_style v1");
   SD_CHECK(speaker_input_proj_supported(c.speaker_embed_dim, c.embed_dim), kErrInvalid,
            "proj_layer: speaker_embed_dim and transformer_embed_dim must be multiples of 8");
+}
+
+// One layer of a backend 4 / 5 Conformer, its shapes held to the configuration the workspace was sized for.
+ConformerL TsvadModel::conformer_layer(const std::string& p) {
+  const int E = cfg_.embed_dim, F = cfg_.ffn_dim;
+  const ConformerL L = loader().conformer(p, false);
+  const HostTensor& dw = ps_.get(p + ".conv_module.sequential.2.weight");
+  SD_CHECK(dw.shape[0] == E && dw.shape[2] == kConformerKernel, kErrParam,
+           p + ".conv_module.sequential.2.weight must be (transformer_embed_dim, 1, 31)");
+  SD_CHECK(L.f1_w1.N == F && L.f1_w1.K == E && L.f2_w1.N == F && L.f2_w1.K == E && L.f1_w2.N == E && L.f1_w2.K == F &&
+               L.f2_w2.N == E && L.f2_w2.K == F,
+           kErrParam, p + ".ffn1 / ffn2 must be Linear(transformer_embed_dim, transformer_ffn_embed_dim) and back");
+  SD_CHECK(L.in_proj.N == 3 * E && L.in_proj.K == E && L.out_proj.N == E && L.out_proj.K == E && L.pw1.N == 2 * E &&
+               L.pw1.K == E && L.pw2.N == E && L.pw2.K == E,
+           kErrParam, p + ": self_attn / conv_module weights must be transformer_embed_dim wide");
+  return L;
 }
 
 void TsvadModel::build() {
@@ -261,7 +282,7 @@ void TsvadModel::build() {
       proj_mix_ = upload_packed(arena_, wm, E, SE, 1, 1, cfg_.bf16);
       proj_b_ = arena_.upload(b.data);
     }
-    if (cfg_.backend != 0) {
+    if (mamba2_backend()) {
       // Mamba2BlockV2(E, n_layer=num_transformer_layer, d_state, d_conv=4, expand, bidirectional=True)
       // (magicdata model.py:377-403)
       single_m_ = std::make_unique<Mamba2Stack>();
@@ -278,12 +299,19 @@ void TsvadModel::build() {
                "multi_backend_proj.weight must be (transformer_embed_dim, 2 * transformer_embed_dim)");
       SD_CHECK(ps_.get("multi_backend_proj.bias").numel() == cfg_.embed_dim, kErrParam, "multi_backend_proj.bias size");
     }
+    // backend 4 / 5: torchaudio.models.Conformer(E, num_attention_head, transformer_ffn_embed_dim, num_transformer_layer,
+    // depthwise_conv_kernel_size=31), use_group_norm False: eval BatchNorm1d folded into the depthwise conv
+    // (egs/magicdata-ramc/ts_vad2/model.py:290-313, 451-463)
     for (int i = 0; i < cfg_.num_transformer_layer; ++i) {
-      if (cfg_.backend == 0) single_.push_back(loader().transformer("single_backend.layers." + std::to_string(i)));
-      if (cfg_.backend != 2) multi_.push_back(loader().transformer("multi_backend.layers." + std::to_string(i)));
+      const std::string n = std::to_string(i);
+      if (cfg_.backend == 0) single_.push_back(loader().transformer("single_backend.layers." + n));
+      // (num_batches_tracked is accepted and ignored: require_all_used skips it)
+      if (conformer_backend()) single_c_.push_back(conformer_layer("single_backend.conformer_layers." + n));
+      if (cfg_.backend == 5) multi_c_.push_back(conformer_layer("multi_backend.conformer_layers." + n));
+      else if (cfg_.backend != 2) multi_.push_back(loader().transformer("multi_backend.layers." + n));
     }
     backend_down_ = conv_bn("backend_down.0.weight", "", "backend_down.0.bias");
-    if (cfg_.backend != 0)   // the two directions are concatenated: Conv1d(2 E NS -> E, k5, pad 2)
+    if (mamba2_backend())   // the two directions are concatenated: Conv1d(2 E NS -> E, k5, pad 2)
       SD_CHECK(backend_down_.w.N == cfg_.embed_dim && backend_down_.w.kw == 5 &&
                    backend_down_.w.Cin == 2 * cfg_.embed_dim * cfg_.max_num_speaker,
                kErrParam, "backend_down.0.weight must be (transformer_embed_dim, 2 * transformer_embed_dim * "
@@ -441,7 +469,7 @@ void TsvadModel::transformer_backend(const float* ts, int T3, int B, int Tl, flo
     build_speaker_input(ts, mix_, SE, T3, B, NS, Tl, SE, pe_, X_, st, sd_bn);
     // bf16(X) for the first layer's in-projection too (every later layer gets it from the LayerNorms): an
     // fp32 A operand would send that GEMM to the register-staged kernel (C4: 1.5 ms per 640 windows vs 0.3)
-    if (bf && !single_m_) f32_to_bf16(X_, (int64_t)S * Tl * E, enc_work().AO, st);
+    if (bf && !single_m_ && single_c_.empty()) f32_to_bf16(X_, (int64_t)S * Tl * E, enc_work().AO, st);
   }
   // Mamba2 back ends: the reference hands the seq-first (T, B, E) tensor to a batch-first module (magicdata
   // model.py:1366-1367, 1393), so each (speaker, frame) is a sequence over the windows of one reference forward call:
@@ -452,6 +480,19 @@ void TsvadModel::transformer_backend(const float* ts, int T3, int B, int Tl, flo
     // both directions of every speaker straight into the speakers-to-channels layout (B, Tl, NS * 2 E)
     single_m_->forward(X_, B, G, NS * Tl, X2_, bf, NS, Tl, st);
     ch = NS * 2 * E;
+  } else if (!single_c_.empty()) {
+    // the sequence axis is time: every (window, speaker) is one sequence of Tl frames, all of full length (:1340-1351)
+    if (conformer_stack_default_fused(single_c_, E, bf)) {
+      // (not the shipped route at hidden 1536: encoder.h) the row programs, the last one writing bf16 rows straight
+      // into the speakers-to-channels layout
+      SpeakerStreams io;
+      io.NS = NS; io.out = X2_;
+      run_conformer_stack(single_c_, X_, S, Tl, E, cfg_.num_attention_head, kConformerKernel, nullptr, enc_work(), st, &io);
+    } else {
+      for (const ConformerL& L : single_c_)
+        run_conformer(L, X_, S, Tl, E, cfg_.num_attention_head, kConformerKernel, nullptr, enc_work(), st);
+      speakers_to_channels(X_, B, NS, Tl, E, X2_, bf, st);
+    }
   } else {
     for (size_t i = 0; i < single_.size(); ++i)
       run_transformer(single_[i], X_, S, Tl, E, cfg_.num_attention_head, nullptr, enc_work(), st, 0, 0, bf || i > 0);
@@ -463,6 +504,12 @@ void TsvadModel::transformer_backend(const float* ts, int T3, int B, int Tl, flo
   if (multi_m_) {
     multi_m_->forward(X_, B, G, Tl, X2_, bf, 1, Tl, st);
     conv_gemm(lin(Tens{X2_, bf}, B * Tl, 2 * E, multi_proj_.w, multi_proj_.beta, Tens{X_, false}, E), bf, st);
+  } else if (!multi_c_.empty()) {
+    if (conformer_stack_default_fused(multi_c_, E, bf))   // :1382-1390
+      run_conformer_stack(multi_c_, X_, B, Tl, E, cfg_.num_attention_head, kConformerKernel, nullptr, enc_work(), st);
+    else
+      for (const ConformerL& L : multi_c_)
+        run_conformer(L, X_, B, Tl, E, cfg_.num_attention_head, kConformerKernel, nullptr, enc_work(), st);
   } else {
     if (bf) f32_to_bf16(X_, (int64_t)B * Tl * E, enc_work().AO, st);
     for (size_t i = 0; i < multi_.size(); ++i)

@@ -45,6 +45,9 @@ struct TsvadConfig {
   int conformer_ffn = 512;
   int conformer_kernel = 31;
   int lstm_hidden = 256;
+  // 4: single_backend "conformer" + multi_backend "transformer"; 5: "conformer" for both (torchaudio Conformer(E,
+  // num_attention_head, ffn_dim, num_transformer_layer, kernel 31), BatchNorm conv module, along TIME; magicdata
+  // model.py:290-313, 451-463, 1340-1351, 1382-1390; variant 0 only; d_state / expand unread).  3 is not a back end.
   // 0: the variant's own back end; 1: single_backend "mamba2" + multi_backend "transformer"; 2: "mamba2" for both
   // (egs/magicdata-ramc/ts_vad2/model.py:377-403, 488-504, 1337-1399; variant 0 only).  The Mamba2BlockV2 stacks scan
   // ALONG THE WINDOWS of a reference forward call (forward's forward_batch groups), as the reference's seq-first call
@@ -96,6 +99,7 @@ class TsvadModel : public ModelCore {
   void build() override;
   ConvL conv_bn(const std::string& wname, const std::string& bn, const std::string& bias = "");
   LayerLoader loader() { return LayerLoader{ps_, arena_, cfg_.bf16}; }
+  ConformerL conformer_layer(const std::string& prefix);
   EncoderWork enc_work() const { return EncoderWork{Y_, QKV_, AO_, H_, partial_, cfg_.bf16}; }
   // Workspace sizes at max_batch windows of max_fbank_frames: frames of a mix row block, label frames of a token
   // row block, token rows, and the elements of the mix (B, T3, SE) and token (rows, E) buffers.
@@ -148,6 +152,9 @@ class TsvadModel : public ModelCore {
   }
   // the back end of forward_common (variant 0's; also behind the ResNet34 and ECAPA encoders)
   bool transformer_variant() const { return cfg_.variant != 1; }
+  bool mamba2_backend() const { return cfg_.backend == 1 || cfg_.backend == 2; }
+  bool conformer_backend() const { return cfg_.backend == 4 || cfg_.backend == 5; }
+  static constexpr int kConformerKernel = 31;   // depthwise_conv_kernel_size of backend 4 / 5 (magicdata model.py:290-313)
   // speech_down_or_up conv: epilogue = + bias only (its BatchNorm1D is down_bn_).  Variant 2: the transposed conv
   // ConvTranspose1d(2560 -> D, k5, stride 2, pad 2, output_padding 1) as ONE k-3 pad-1 conv with 2 D outputs per
   // input frame j, [even phase y[2j] | odd phase y[2j+1]] = two consecutive rows of the (B, 2 T', D) output.
@@ -171,6 +178,8 @@ class TsvadModel : public ModelCore {
   std::vector<TransformerL> single_, multi_;
   // backend 1 / 2: single_backend (and, 2, multi_backend + multi_backend_proj) as Mamba2BlockV2 stacks
   std::unique_ptr<Mamba2Stack> single_m_, multi_m_;
+  // backend 4 / 5: single_backend (and, 5, multi_backend) as torchaudio Conformers with a BatchNorm conv module
+  std::vector<ConformerL> single_c_, multi_c_;
   ConvL multi_proj_;
   ConvL backend_down_;
   std::vector<ConformerL> conf_;

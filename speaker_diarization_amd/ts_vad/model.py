@@ -77,7 +77,8 @@ class TSVADModel(_lib.Handle):
             num_transformer_layer=c.num_transformer_layer, num_attention_head=c.num_attention_head,
             transformer_embed_dim=c.transformer_embed_dim,
             transformer_ffn_embed_dim=c.transformer_ffn_embed_dim, speaker_embed_dim=c.speaker_embed_dim,
-            backend=c.backend, d_state=c.d_state if c.backend else 0, expand=c.expand if c.backend else 0, **wav)
+            backend=c.backend, d_state=c.d_state if c.mamba2_backend else 0,
+            expand=c.expand if c.mamba2_backend else 0, **wav)
         if wcfg is None:
             self._create(conf)
         else:
@@ -163,7 +164,7 @@ class TSVADModel(_lib.Handle):
                 for s in range(0, B, step):
                     e = min(B, s + step)
                     self.forward(ref[s:e], ts[s:e], T_lab, out=out[s:e], check=False, forward_batch=G)
-            elif self.cfg.backend:
+            elif self.cfg.mamba2_backend:
                 raise ValueError(f"a Mamba2 back end scans over the {G} windows of a reference forward call: "
                                  f"create the model with max_batch >= {G} (it is {self.max_batch})")
             else:                        # a reference batch spans device forwards: its non-finite flags up front

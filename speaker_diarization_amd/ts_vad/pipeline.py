@@ -55,7 +55,8 @@ class TSVADPipeline:
         self.segment_shift = segment_shift
         # a model that fixes the reference batch (the streaming decoder: batch 1) overrides it
         batch_size = getattr(model, "reference_batch_size", batch_size)
-        if getattr(self.cfg, "backend", 0) and batch_size > model.max_batch:
+        # (the conformer back ends, backend 4 / 5, run along time: no coupling to the batch size)
+        if getattr(self.cfg, "backend", 0) in (1, 2) and batch_size > model.max_batch:
             raise ValueError(f"a Mamba2 back end scans over the {batch_size} windows of a reference batch: create the "
                              f"model with max_batch >= {batch_size} (it is {model.max_batch})")
         self.batch_size = min(batch_size, model.max_batch)

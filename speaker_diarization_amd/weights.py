@@ -24,6 +24,11 @@ Shape = Tuple[int, ...]
 # Mamba v1 ("mamba", "mamba_v2"), "mamba2_unidirectional" and mamba2 behind another speech encoder are not built.
 _MAMBA2_BACKENDS = {("CAM++", "mamba2", "transformer"): 1, ("CAM++", "mamba2", "mamba2"): 2}
 MAMBA2_HEADDIM = 64   # mamba_ssm Mamba2's headdim default
+# The conformer back ends (egs/magicdata-ramc/ts_vad2/model.py:290-313, 451-463): torchaudio.models.Conformer with a
+# BatchNorm conv module, along time.  The reference's recipes pair them with CAM++ only and never run a transformer
+# single back end in front of a conformer multi one.
+_CONFORMER_BACKENDS = {("CAM++", "conformer", "transformer"): 4, ("CAM++", "conformer", "conformer"): 5}
+CONFORMER_BACKEND_KERNEL = 31   # depthwise_conv_kernel_size the reference passes
 
 
 @dataclass
@@ -177,12 +182,16 @@ class TSVADConfig:
         if not self.ots_vad_style and (self.speech_encoder_type, self.single_backend_type,
                                        self.multi_backend_type) in _MAMBA2_BACKENDS:
             return 0   # CAM++ with Mamba2 back ends: variant 0 plus `backend`
+        if not self.ots_vad_style and (self.speech_encoder_type, self.single_backend_type,
+                                       self.multi_backend_type) in _CONFORMER_BACKENDS:
+            return 0   # CAM++ with conformer back ends: variant 0 plus `backend`
         if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) != (
                 "CAM++", "transformer", "transformer"):
             raise ValueError(
                 f"unsupported TS-VAD configuration {self.speech_encoder_type}/"
                 f"{self.single_backend_type}/{self.multi_backend_type} (MI355X backend builds CAM++ "
-                "with transformer, mamba2 + transformer, mamba2 + mamba2 or conformer_ots_vad/lstm_ots_vad, "
+"with transformer, mamba2 + transformer, mamba2 + mamba2, conformer + transformer, conformer + conformer or "
+                "conformer_ots_vad/lstm_ots_vad, "
                 "resnet34_wespeaker, ecapa_channel_1024_wespeaker and ReDimNetB2 with transformer, WavLM / "
                 "WavLM_weight_sum with transformer given wavlm_cfg, w2v-bert2 with transformer, whisper with transformer)")
         return 0
@@ -190,9 +199,17 @@ class TSVADConfig:
     @property
     def backend(self) -> int:
         """sd_tsvad_config.backend: 0 the variant's own back end, 1 single_backend "mamba2" + multi_backend
-        "transformer", 2 "mamba2" for both (bidirectional Mamba2BlockV2 stacks, CAM++ only).  Raises like `variant`."""
+        "transformer", 2 "mamba2" for both (bidirectional Mamba2BlockV2 stacks, CAM++ only), 4 single_backend
+        "conformer" + multi_backend "transformer", 5 "conformer" for both (torchaudio Conformers, CAM++ only).  Raises
+        like `variant`."""
         self.variant
-        return _MAMBA2_BACKENDS.get((self.speech_encoder_type, self.single_backend_type, self.multi_backend_type), 0)
+        key = (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type)
+        return _MAMBA2_BACKENDS.get(key, _CONFORMER_BACKENDS.get(key, 0))
+
+    @property
+    def mamba2_backend(self) -> bool:
+        """A Mamba2 back end: the scan runs along the windows of a reference forward call."""
+        return self.backend in (1, 2)
 
     @staticmethod
     def ots_vad_v1(**kw) -> "TSVADConfig":
@@ -562,23 +579,35 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
     if cfg.variant in (0, 2, 3, 4, 5, 6, 7, 8):
         k.append(("pos_encoder.pe", (cfg.rs_len * cfg.label_rate, 1, e), "pe"))
         backend = cfg.backend
-        if backend:
+        m2 = cfg.mamba2_backend
+        ffn = cfg.transformer_ffn_embed_dim
+        if m2:
             # Mamba2BlockV2(e, n_layer, d_state, d_conv=4, expand, bidirectional=True): the two directions are
             # concatenated, so backend_down reads 2 e ns channels (magicdata model.py:377-403)
             mamba2_block_v2_layout(k, "single_backend.", e, cfg.num_transformer_layer, cfg.d_state, cfg.expand)
+        elif backend in (4, 5):
+            # torchaudio.models.Conformer(e, num_attention_head, ffn, num_transformer_layer, 31): use_group_norm False,
+            # so conv_module.sequential.3 is a BatchNorm1d (magicdata model.py:290-313)
+            for i in range(cfg.num_transformer_layer):
+                _conformer_layer(k, f"single_backend.conformer_layers.{i}.", e, ffn, CONFORMER_BACKEND_KERNEL,
+                                 group_norm=False)
         else:
             for i in range(cfg.num_transformer_layer):
-                _tfm(k, f"single_backend.layers.{i}.", e, cfg.transformer_ffn_embed_dim)
-        k.append(("backend_down.0.weight", (e, (2 if backend else 1) * e * ns, 5), "conv1d"))
+                _tfm(k, f"single_backend.layers.{i}.", e, ffn)
+        k.append(("backend_down.0.weight", (e, (2 if m2 else 1) * e * ns, 5), "conv1d"))
         k.append(("backend_down.0.bias", (e,), "small"))
         _bn(k, "backend_down.1.bn", e)
         if backend == 2:
             mamba2_block_v2_layout(k, "multi_backend.", e, cfg.num_transformer_layer, cfg.d_state, cfg.expand)
             k.append(("multi_backend_proj.weight", (e, 2 * e), "linear"))   # magicdata model.py:488-504
             k.append(("multi_backend_proj.bias", (e,), "small"))
+        elif backend == 5:
+            for i in range(cfg.num_transformer_layer):   # magicdata model.py:451-463
+                _conformer_layer(k, f"multi_backend.conformer_layers.{i}.", e, ffn, CONFORMER_BACKEND_KERNEL,
+                                 group_norm=False)
         else:
             for i in range(cfg.num_transformer_layer):
-                _tfm(k, f"multi_backend.layers.{i}.", e, cfg.transformer_ffn_embed_dim)
+                _tfm(k, f"multi_backend.layers.{i}.", e, ffn)
         k.append(("fc.weight", (ns, e), "linear"))
         k.append(("fc.bias", (ns,), "small"))
     else:
