@@ -168,6 +168,26 @@ typedef struct {
 } sd_tsvad_config;
 
 int sd_tsvad_create(const sd_tsvad_config* cfg, sd_tsvad** out);
+
+/* sd_tsvad_config followed by the fields added since; sd_tsvad_create(cfg) is sd_tsvad_create_ex of cfg zero-extended,
+ * today's model.  Later fields go after frame_level_gsp. */
+typedef struct {
+  sd_tsvad_config base;
+  int frame_level_gsp;            /* 1: speech_encoder_type "CAM++_frame_level_gsp_fc" (egs/magicdata-ramc/ts_vad2/
+                                     model.py:543-563 construction, 1275-1287 forward; egs/magicdata-ramc/
+                                     run_ts_vad2.sh:8333-8440 and the same stages of run_ts_vad2_aistation.sh, with
+                                     single_backend_type "mamba2", d_state 128, rs_len 6).  The CAM++ time output
+                                     (B, 512, T') is reduced per frame to its mean and unbiased std over the 512
+                                     channels, gsp_fc = Linear(2, 256) maps the pair to 256 features and
+                                     speech_down_or_up = Conv1d(256 -> speaker_embed_dim, k5, stride 2, pad 2) +
+                                     BatchNorm1D + ReLU follows; everything after is forward_common.  Keys: variant 0's,
+                                     plus gsp_fc.weight (256, 2), gsp_fc.bias (256), and speech_down_or_up.0.weight is
+                                     (speaker_embed_dim, 256, 5).  base.variant must be 0 (SD_ERR_INVALID otherwise) with
+                                     any of its back ends (base.backend 0, 1, 2, 4, 5); speaker_embed_dim a multiple of 32.
+                                     gsp_fc and the conv run folded in one kernel (sd_op_gsp_down below); the statistics
+                                     and its outputs are fp32 at every precision.  0: base alone */
+} sd_tsvad_config_ex;
+int sd_tsvad_create_ex(const sd_tsvad_config_ex* cfg, sd_tsvad** out);
 /* One state_dict entry by its reference key name (fp32 host data, torch shape). */
 int sd_tsvad_set_param(sd_tsvad* h, const char* name, const float* host_data, const int64_t* shape,
                        int ndim);
@@ -1243,6 +1263,20 @@ int sd_op_speaker_input_proj(const float* ts, const float* mix, int B, int NS, i
  * mixer.conv1d.bias, mixer.dt_bias (H), mixer.A_log (H), mixer.D (H), mixer.norm.weight (d_inner),
  * mixer.out_proj.weight (E, d_inner); d_inner = expand * E, H = d_inner / 64.  precision 0 fp32, 1 bf16 (bf16 GEMM
  * operands, zxbcdt / g and the output stored as bf16; the scan itself is fp32), 2 bf16x3.  Synchronises `stream`. */
+/* The "CAM++_frame_level_gsp_fc" stage between the CAM++ trunk and the mix embeddings (sd_tsvad_config_ex.
+ * frame_level_gsp; egs/magicdata-ramc/ts_vad2/model.py:1275-1287) as the model runs it, all pointers on the device:
+ * x (B, T2, 512) the trunk's transit3 map, fp32 or (x_bf16) bf16 bits, before out_nonlinear; s / h (512) that BatchNorm
+ * folded to scale / shift (the ReLU follows); gw (256, 2) / gb (256) gsp_fc; w (SE, 256, 5) / cb (SE) speech_down_or_up.0,
+ * UNFOLDED: the call folds them on the host as the model does at finalize (float64:
+ * A[o,k] = sum_c w[o,c,k] gw[c,0], S with gw[c,1], C with gb[c]).  Per frame mean and unbiased std over the channels of
+ * relu(s x + h), then y[b,j,o] = cb[o] + sum over taps k = 0..4 with 0 <= t = 2 j + k - 2 < T2 of
+ * (A[o,k] mean[t] + S[o,k] std[t] + C[o,k]): the reference zero-pads gsp_fc's output, so a padded tap contributes nothing.
+ * y (B, (T2 - 1) / 2 + 1, SE) fp32 = conv + bias, before speech_down_or_up.1.  SE a multiple of 32 and T2 >= 1
+ * (SD_ERR_INVALID otherwise).  Synchronises `stream`.  sd_gsp_down_frame_tile: the input frames one workgroup's tile
+ * covers (a 2-frame halo on each side comes on top), for tests that cross a tile boundary. */
+int sd_op_gsp_down(const void* x, int x_bf16, const float* s, const float* h, const float* gw, const float* gb,
+                   const float* w, const float* cb, int B, int T2, int SE, float* y, void* stream);
+int sd_gsp_down_frame_tile(void);
 int sd_op_mamba2_stack(const float* x, int R, int L, int E, const float* weights, int64_t n_weights, int n_layer,
                        int d_state, int expand, int precision, float* out, void* stream);
 /* Attention core on packed qkv (S*T, 3D) -> out (S*T, D). */

@@ -52,6 +52,14 @@ class TsvadConfig(ctypes.Structure):
     ]
 
 
+class TsvadConfigEx(TsvadConfig):
+    """sd_tsvad_config_ex: sd_tsvad_config followed by the fields added since (ctypes lays a subclass's fields out after
+    its base's).  sd_tsvad_create_ex takes it; all new fields zero is sd_tsvad_create."""
+    _fields_ = [
+        ("frame_level_gsp", c_int),   # 1: speech_encoder_type "CAM++_frame_level_gsp_fc" (variant 0 only)
+    ]
+
+
 class EdaConfig(ctypes.Structure):
     _fields_ = [
         ("variant", c_int),
@@ -294,6 +302,7 @@ _SIGS = {
     "sd_whisper_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sd_whisper_frames": (c_int, [c_int]),
     "sd_tsvad_create_whisper": (c_int, [POINTER(TsvadConfig), POINTER(WhisperConfig), POINTER(c_void_p)]),
+    "sd_tsvad_create_ex": (c_int, [POINTER(TsvadConfigEx), POINTER(c_void_p)]),
     "sd_op_whisper_logmel": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "sd_op_whisper_stem": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_int, c_void_p]),
@@ -402,6 +411,9 @@ _SIGS = {
     "sd_op_speaker_input_proj": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                          c_int, c_void_p]),
+    "sd_op_gsp_down": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                               c_int, c_void_p, c_void_p]),
+    "sd_gsp_down_frame_tile": (c_int, []),
     "sd_op_mamba2_stack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                                    c_void_p, c_void_p]),
     "sd_op_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,

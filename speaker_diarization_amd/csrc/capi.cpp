@@ -226,9 +226,11 @@ static sd::WhisperConfig whisper_geometry(const sd_whisper_config* c) {
   return t;
 }
 
-static int tsvad_create(const sd_tsvad_config* c, const sd_whisper_config* wc, sd_tsvad** out) {
+static int tsvad_create(const sd_tsvad_config* c, const sd_whisper_config* wc, sd_tsvad** out,
+                        int frame_level_gsp = 0) {
   return guard([&] {
     SD_CHECK(c && out, sd::kErrInvalid, "null argument");
+    SD_CHECK(frame_level_gsp == 0 || frame_level_gsp == 1, sd::kErrInvalid, "frame_level_gsp must be 0 or 1");
     SD_CHECK(c->variant >= 0 && c->variant <= 8, sd::kErrInvalid, "unknown TS-VAD variant");
     SD_CHECK(c->variant != 8 || wc, sd::kErrInvalid,
              "variant 8 (whisper) takes the trunk's own geometry: create it with sd_tsvad_create_whisper");
@@ -267,6 +269,7 @@ static int tsvad_create(const sd_tsvad_config* c, const sd_whisper_config* wc, s
     t.wavlm_pre_ln = c->wavlm_pre_ln != 0;
     t.max_samples = c->max_samples;
     t.w2vbert_layers = c->w2vbert_layers;
+    t.frame_level_gsp = frame_level_gsp != 0;
     if (wc) {
       check_whisper_geometry(wc);
       check_whisper_workspace(wc, c->max_batch, c->max_samples);
@@ -279,6 +282,11 @@ static int tsvad_create(const sd_tsvad_config* c, const sd_whisper_config* wc, s
 }
 
 int sd_tsvad_create(const sd_tsvad_config* c, sd_tsvad** out) { return tsvad_create(c, nullptr, out); }
+
+int sd_tsvad_create_ex(const sd_tsvad_config_ex* c, sd_tsvad** out) {
+  if (!c) return guard([] { SD_CHECK(false, sd::kErrInvalid, "null argument"); });
+  return tsvad_create(&c->base, nullptr, out, c->frame_level_gsp);
+}
 
 int sd_tsvad_create_whisper(const sd_tsvad_config* c, const sd_whisper_config* wc, sd_tsvad** out) {
   if (!wc) return guard([] { SD_CHECK(false, sd::kErrInvalid, "null argument"); });
@@ -1821,6 +1829,31 @@ int sd_op_speaker_input_proj(const float* ts, const float* mix, int B, int NS, i
     sd::speaker_input_proj(a, bf, st);
   });
 }
+
+int sd_op_gsp_down(const void* x, int x_bf16, const float* s, const float* h, const float* gw, const float* gb,
+                   const float* w, const float* cb, int B, int T2, int SE, float* y, void* stream) {
+  return guard([&] {
+    hipStream_t st = S(stream);
+    SD_CHECK(x && s && h && gw && gb && w && cb && y, sd::kErrInvalid, "gsp_down: null argument");
+    SD_CHECK(SE >= 32 && SE % 32 == 0, sd::kErrInvalid, "gsp_down: SE must be a multiple of 32");
+    SD_CHECK(B >= 1 && T2 >= 1, sd::kErrInvalid, "gsp_down: B and T2 must be at least 1");
+    // the runtime's fold (TsvadModel::build): gsp_fc and the conv weight come back to the host, the 15 coefficients
+    // per channel go up again
+    constexpr int F = sd::kGspFcDim;
+    std::vector<float> hgw((size_t)F * 2), hgb(F), hw((size_t)SE * F * 5), coef;
+    SD_HIP(hipStreamSynchronize(st));
+    SD_HIP(hipMemcpy(hgw.data(), gw, hgw.size() * sizeof(float), hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(hgb.data(), gb, hgb.size() * sizeof(float), hipMemcpyDeviceToHost));
+    SD_HIP(hipMemcpy(hw.data(), w, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
+    sd::gsp_down_fold(hgw.data(), hgb.data(), hw.data(), SE, coef);
+    Scratch dc(coef.size() * sizeof(float), st);
+    SD_HIP(hipMemcpyAsync(dc.p, coef.data(), coef.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    sd::gsp_down(x, x_bf16 != 0, B, T2, s, h, static_cast<const float*>(dc.p), cb, SE, y, st);
+    SD_HIP(hipStreamSynchronize(st));   // coef (host) and dc live until the kernel is done
+  });
+}
+
+int sd_gsp_down_frame_tile(void) { return sd::gsp_down_frame_tile(); }
 
 int sd_op_mamba2_stack(const float* x, int R, int L, int E, const float* weights, int64_t n_weights, int n_layer,
                        int d_state, int expand, int precision, float* out, void* stream) {

@@ -660,6 +660,21 @@ void gsp_fc(const float* x, int rows, int C, int ldx, const float* w /*E x 2*/,
             const float* bias, int E, float* out, int ldo, hipStream_t st, const BnRelu& bn = BnRelu(),
             int rows_per_window = 1);
 
+// Frame-level GSP + gsp_fc + the speech_down_or_up conv of speech_encoder_type "CAM++_frame_level_gsp_fc"
+// (egs/magicdata-ramc/ts_vad2/model.py:543-563, 1275-1287) in one launch: x (B, T2, 512) the CAM++ transit3 map (fp32 or
+// bf16) before out_nonlinear, s / h (512) that BatchNorm folded (the ReLU follows); per frame mean and unbiased std over
+// the channels, then the folded Linear(2, 256) + Conv1d(256 -> SE, k5, stride 2, pad 2):
+//   y[b, j, o] = cb[o] + sum over k = 0..4 with 0 <= t = 2 j + k - 2 < T2 of (A[o,k] mean[t] + S[o,k] std[t] + C[o,k])
+// (the reference zero-pads gsp_fc's output, so a padded tap drops its C term too).  y (B, (T2 - 1) / 2 + 1, SE) fp32 =
+// conv + bias, before speech_down_or_up.1's BatchNorm1D + ReLU.  SE a multiple of 32.  coef (5, 3, SE) = [k][A | S | C][o]
+// from gsp_down_fold (float64 sums over the 256 gsp_fc features): gw (256, 2), gb (256), w (SE, 256, 5), all host.
+constexpr int kGspChannels = 512;   // CamTrunk::kChannels
+constexpr int kGspFcDim = 256;      // gsp_fc = nn.Linear(2, 256)
+void gsp_down_fold(const float* gw, const float* gb, const float* w, int SE, std::vector<float>& coef);
+void gsp_down(const void* x, bool x_bf16, int B, int T2, const float* s, const float* h, const float* coef,
+              const float* cb, int SE, float* y, hipStream_t st);
+int gsp_down_frame_tile();   // input frames per workgroup tile (without the 2-frame halos), for tests
+
 // (B*NS, T, E) speaker-major rows -> (B, T, NS*E) channel-concatenated rows.
 void speakers_to_channels(const float* x, int B, int NS, int T, int E, void* out, bool out_bf16,
                           hipStream_t st);

@@ -801,6 +801,131 @@ void gsp_fc(const float* x, int rows, int C, int ldx, const float* w, const floa
   SD_LAUNCH_CHECK();
 }
 
+// ------------------------------------------------------------------ frame-level GSP + gsp_fc + speech_down_or_up conv
+// speech_encoder_type "CAM++_frame_level_gsp_fc" (egs/magicdata-ramc/ts_vad2/model.py:543-563, 1275-1287): per frame
+// the mean and the unbiased std over the 512 channels of relu(bn(x)), gsp_fc = Linear(2, 256), then Conv1d(256 -> SE,
+// k5, stride 2, pad 2).  gsp_fc's output has rank 2 in (mean, std), so the conv collapses to 5 taps of
+//   A[o,k] mean[t] + S[o,k] std[t] + C[o,k],  t = 2 j + k - 2,
+// with A / S / C = the conv weight contracted with gsp_fc's two columns and its bias (gsp_down_fold, float64 on the
+// host).  The reference zero-pads gsp_fc's OUTPUT: a tap outside [0, T2) contributes nothing, its C term included.
+//
+// One workgroup per (window, tile of kGspOutTile output frames): each wave takes every fourth frame of the tile's
+// 2 kGspOutTile + 3 input frames (the tile plus a 2-frame halo on each side), 8 channels per lane from one 16-B (bf16)
+// or two 16-B (fp32) loads, two passes in registers so the sum of squares is never negative, warp_sum (a fixed
+// butterfly: runs are bit-identical), stats to LDS; then thread o keeps its 15 coefficients in registers and
+// writes the tile's outputs of channel o, coalesced over o.
+constexpr int kGspOutTile = 16;                       // output frames per workgroup
+constexpr int kGspStatFrames = 2 * kGspOutTile + 3;   // input frames whose stats a workgroup needs
+
+template <bool BF>
+__global__ __launch_bounds__(256) void gsp_down_kernel(const act_t<BF>* __restrict__ x, int T2, int T3, int tiles,
+                                                       BnRelu bn, const float* __restrict__ coef,
+                                                       const float* __restrict__ cb, int SE, float* __restrict__ y) {
+  constexpr int C = kGspChannels;
+  __shared__ float s_mean[kGspStatFrames], s_std[kGspStatFrames];
+  const int b = blockIdx.x / tiles, j0 = (blockIdx.x % tiles) * kGspOutTile;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int t0 = 2 * j0 - 2;   // input frame of stats slot 0
+  for (int f = wave; f < kGspStatFrames; f += 4) {
+    const int t = t0 + f;
+    if (t < 0 || t >= T2) continue;   // a padded tap: never read below
+    const act_t<BF>* xr = x + ((int64_t)b * T2 + t) * C + lane * 8;
+    float v[8];
+    if constexpr (BF) {
+      const uint4 q = *reinterpret_cast<const uint4*>(xr);
+      const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        v[2 * u] = __uint_as_float(w[u] << 16);
+        v[2 * u + 1] = __uint_as_float(w[u] & 0xffff0000u);
+      }
+    } else {
+      const float4 p = *reinterpret_cast<const float4*>(xr);
+      const float4 q = *reinterpret_cast<const float4*>(xr + 4);
+      v[0] = p.x; v[1] = p.y; v[2] = p.z; v[3] = p.w; v[4] = q.x; v[5] = q.y; v[6] = q.z; v[7] = q.w;
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      v[u] = bn_relu(bn, b, lane * 8 + u, v[u]);
+      s += v[u];
+    }
+    const float mean = warp_sum(s) / (float)C;
+    float q = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { const float d = v[u] - mean; q = fmaf(d, d, q); }
+    q = warp_sum(q);
+    if (lane == 0) {
+      s_mean[f] = mean;
+      s_std[f] = sqrtf(q / (float)(C - 1));   // torch.std default: unbiased
+    }
+  }
+  __syncthreads();
+  const int nj = min(kGspOutTile, T3 - j0);
+  for (int o = threadIdx.x; o < SE; o += blockDim.x) {
+    float a[5], sg[5], c[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      a[k] = coef[(k * 3 + 0) * SE + o];
+      sg[k] = coef[(k * 3 + 1) * SE + o];
+      c[k] = coef[(k * 3 + 2) * SE + o];
+    }
+    const float bias = cb[o];
+    for (int j = 0; j < nj; ++j) {
+      float acc = bias;
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        const int f = 2 * j + k, t = t0 + f;
+        if (t >= 0 && t < T2) acc += fmaf(a[k], s_mean[f], fmaf(sg[k], s_std[f], c[k]));
+      }
+      y[((int64_t)b * T3 + j0 + j) * SE + o] = acc;
+    }
+  }
+}
+
+void gsp_down_fold(const float* gw, const float* gb, const float* w, int SE, std::vector<float>& coef) {
+  constexpr int F = kGspFcDim;
+  coef.assign((size_t)15 * SE, 0.f);
+  for (int o = 0; o < SE; ++o)
+    for (int k = 0; k < 5; ++k) {
+      double a = 0.0, s = 0.0, c = 0.0;
+      for (int f = 0; f < F; ++f) {
+        const double wk = w[((size_t)o * F + f) * 5 + k];
+        a += wk * gw[2 * f];
+        s += wk * gw[2 * f + 1];
+        c += wk * gb[f];
+      }
+      coef[(size_t)(k * 3 + 0) * SE + o] = (float)a;
+      coef[(size_t)(k * 3 + 1) * SE + o] = (float)s;
+      coef[(size_t)(k * 3 + 2) * SE + o] = (float)c;
+    }
+}
+
+int gsp_down_frame_tile() { return 2 * kGspOutTile; }
+
+void gsp_down(const void* x, bool x_bf16, int B, int T2, const float* s, const float* h, const float* coef,
+              const float* cb, int SE, float* y, hipStream_t st) {
+  SD_CHECK(SE >= 32 && SE % 32 == 0, kErrInvalid, "gsp_down: speaker_embed_dim must be a multiple of 32");
+  SD_CHECK(B >= 1 && T2 >= 1, kErrInvalid, "gsp_down: needs at least one window of at least one frame");
+  SD_CHECK(x && s && h && coef && cb && y && (reinterpret_cast<uintptr_t>(x) & 15) == 0, kErrInvalid,
+           "gsp_down: null or misaligned argument");
+  const int T3 = (T2 - 1) / 2 + 1, tiles = cdiv(T3, kGspOutTile);
+  SD_CHECK((int64_t)B * tiles < (1ll << 31), kErrInvalid, "gsp_down: too many tiles");
+  BnRelu bn;   // out_nonlinear's folded BatchNorm + ReLU: no bypass groups
+  bn.a = s;
+  bn.b = h;
+  const double frames = (double)B * T2, outs = (double)B * T3 * SE;
+  ProfScope prof("gsp_down", frames * kGspChannels * 6.0 + outs * 25.0,
+                 frames * kGspChannels * (x_bf16 ? 2.0 : 4.0) + outs * 4.0, st);
+  if (x_bf16)
+    hipLaunchKernelGGL(gsp_down_kernel<true>, dim3(B * tiles), dim3(256), 0, st, static_cast<const uint16_t*>(x), T2, T3,
+                       tiles, bn, coef, cb, SE, y);
+  else
+    hipLaunchKernelGGL(gsp_down_kernel<false>, dim3(B * tiles), dim3(256), 0, st, static_cast<const float*>(x), T2, T3,
+                       tiles, bn, coef, cb, SE, y);
+  SD_LAUNCH_CHECK();
+}
+
 template <bool OBF>
 __global__ void speakers_to_channels_kernel(const float* __restrict__ x, int B, int NS, int T, int E,
                                             act_t<OBF>* __restrict__ out) {

@@ -16,6 +16,8 @@
 //          variant 7 (w2v-bert2, magicdata model.py:805-840, 1225-1237): ref_speech (B, T, 80) read as (B, T / 2, 160)
 //                    (a plain reshape: the same memory); the w2v-BERT 2.0 trunk (w2vbert.h) on the caller's stream
 //     -> speech_down_or_up (down_gemm) -> mix (B, T3, SE)
+//          frame_level_gsp ("CAM++_frame_level_gsp_fc", magicdata model.py:543-563, 1275-1287; variant 0's trunk): frame
+//          mean / std over the channels + gsp_fc + the conv as one folded gsp_down launch instead
 //          variants 0, 1: conv + BN + ReLU                    model.py:385-395 / 406-416
 //          variant 2: SpeechFeatUpsample2 transposed conv + BN + ReLU (model.py:114-134)
 //          variants 3, 4: conv k5 stride 4 pad 2 + BN + ReLU (model.py:641-654; magicdata :703-715)
@@ -58,6 +60,13 @@ void TsvadModel::validate(const TsvadConfig& c) {
   if (c.backend == 4 || c.backend == 5)   // d_state / expand are not read
     SD_CHECK(c.variant == 0, kErrInvalid,
              "backend 4 / 5 (conformer back ends) is built for variant 0 (speech_encoder_type CAM++) only");
+  if (c.frame_level_gsp) {   // any of variant 0's back ends
+    SD_CHECK(c.variant == 0, kErrInvalid,
+             "frame_level_gsp (speech_encoder_type CAM++_frame_level_gsp_fc) is built on variant 0 (the CAM++ trunk with "
+             "the transformer, Mamba2 or conformer back ends) only");
+    SD_CHECK(c.speaker_embed_dim % 32 == 0, kErrInvalid,
+             "frame_level_gsp: speaker_embed_dim must be a multiple of 32");
+  }
   if (c.variant == 5 || c.variant == 6) {
     SD_CHECK(c.backend == 0, kErrInvalid,
              "the WavLM speech encoders (variants 5 / 6) are built with the transformer back end only (backend 0)");
@@ -251,6 +260,25 @@ void TsvadModel::build() {
              "speech_down_or_up.0.weight must be (speaker_embed_dim, " + std::to_string(cin) + ", 5)");
     SD_CHECK(ps_.get("speech_down_or_up.0.bias").numel() == cfg_.speaker_embed_dim, kErrParam,
              "speech_down_or_up.0.bias size");
+    down_bn_ = bn_only("speech_down_or_up.1.bn");
+  } else if (cfg_.frame_level_gsp) {
+    // gsp_fc = Linear(2, 256) on the per-frame (mean, std), then Conv1d(256 -> SE, k5, stride 2, pad 2) (magicdata
+    // model.py:550-563): rank 2 in (mean, std), so the pair folds to 15 coefficients per output channel (gsp_down)
+    const int SE = cfg_.speaker_embed_dim;
+    const HostTensor& gw = ps_.get("gsp_fc.weight");
+    const HostTensor& gb = ps_.get("gsp_fc.bias");
+    const HostTensor& w = ps_.get("speech_down_or_up.0.weight");
+    const HostTensor& cb = ps_.get("speech_down_or_up.0.bias");
+    SD_CHECK(gw.shape.size() == 2 && gw.shape[0] == kGspFcDim && gw.shape[1] == 2, kErrParam,
+             "gsp_fc.weight must be (256, 2)");
+    SD_CHECK(gb.numel() == kGspFcDim, kErrParam, "gsp_fc.bias size");
+    SD_CHECK(w.shape.size() == 3 && w.shape[0] == SE && w.shape[1] == kGspFcDim && w.shape[2] == 5, kErrParam,
+             "speech_down_or_up.0.weight must be (speaker_embed_dim, 256, 5)");
+    SD_CHECK(cb.numel() == SE, kErrParam, "speech_down_or_up.0.bias size");
+    std::vector<float> coef;
+    gsp_down_fold(gw.data.data(), gb.data.data(), w.data.data(), SE, coef);
+    gsp_coef_ = arena_.upload(coef);
+    gsp_cb_ = arena_.upload(cb.data);
     down_bn_ = bn_only("speech_down_or_up.1.bn");
   } else {
     down_ = conv_bn("speech_down_or_up.0.weight", "", "speech_down_or_up.0.bias");
@@ -724,6 +752,13 @@ void TsvadModel::forward(const float* ref, const float* ts, int B, int Tf, int T
       const Tens x4 = trunk_forward(ref, Bh, Tf, s, b0);
       conv_gemm(down_gemm(x4, Bh, Tf, mix_ + (int64_t)b0 * T3 * SE), bf, s);
       conformer_slice(ts, T3, b0, Bh, Tl, s, sd_bn);
+    });
+  } else if (cfg_.frame_level_gsp) {
+    // per window, so inside the trunk's slice: out_nonlinear + frame stats + the folded gsp_fc / conv in one launch
+    const int T2 = CamTrunk::out_frames(Tf);
+    run_sliced(B, two, st, [&](int b0, int Bh, hipStream_t s) {
+      const Tens x = trunk_forward(ref, Bh, Tf, s, b0);   // the slice's own map: windows [b0, b0 + Bh)
+      gsp_down(x.p, x.bf, Bh, T2, cam_->out_s(), cam_->out_h(), gsp_coef_, gsp_cb_, SE, mix_ + (int64_t)b0 * T3 * SE, s);
     });
   } else {
     // the trunk alone runs sliced; the speech_down_or_up GEMM covers the whole batch after the join

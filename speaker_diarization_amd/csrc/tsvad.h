@@ -53,6 +53,11 @@ struct TsvadConfig {
   // ALONG THE WINDOWS of a reference forward call (forward's forward_batch groups), as the reference's seq-first call
   // of a batch-first module does (model.py:1366-1367, 1393; mamba2.h)
   int backend = 0;
+  // speech_encoder_type "CAM++_frame_level_gsp_fc" (egs/magicdata-ramc/ts_vad2/model.py:543-563, 1275-1287): variant 0's
+  // trunk and back ends (any of 0, 1, 2, 4, 5) with the stage in between replaced: per-frame mean / unbiased std over the
+  // 512 channels of the CAM++ time output, gsp_fc = Linear(2, 256), then Conv1d(256 -> speaker_embed_dim, k5, stride 2,
+  // pad 2), run folded as one gsp_down launch (kernels.h).  variant 0 only.
+  bool frame_level_gsp = false;
   int d_state = 64;
   int expand = 4;
   // variants 5 / 6: the WavLM geometry (the checkpoint's cfg) and the longest window; ref_speech is (B, n_samples)
@@ -159,6 +164,8 @@ class TsvadModel : public ModelCore {
   // ConvTranspose1d(2560 -> D, k5, stride 2, pad 2, output_padding 1) as ONE k-3 pad-1 conv with 2 D outputs per
   // input frame j, [even phase y[2j] | odd phase y[2j+1]] = two consecutive rows of the (B, 2 T', D) output.
   ConvL down_;
+  // frame_level_gsp: no down_ GEMM; gsp_fc and the conv folded to (5, 3, SE) coefficients + the conv bias (gsp_down)
+  const float *gsp_coef_ = nullptr, *gsp_cb_ = nullptr;
   // variant 6: `weights` (L), wavlmproj (SE, D) + wavlmlnorm; acc_ (B T, D) fp32 takes the layer-weighted sum as the
   // layers run, z_ (B T, SE) the projected and normalised map (bf16 in bf16 mode), the conv's A operand
   std::vector<float> mix_w_;

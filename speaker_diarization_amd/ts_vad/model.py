@@ -71,7 +71,7 @@ class TSVADModel(_lib.Handle):
                 n_mels=w.n_mels, n_audio_ctx=w.n_audio_ctx, n_audio_state=w.n_audio_state,
                 n_audio_head=w.n_audio_head, n_audio_layer=w.n_audio_layer, layer_st=w.layer_st, layer_ed=w.layer_ed,
                 precision=_lib.PRECISION[precision], max_batch=self.max_batch, max_samples=self.max_samples)
-        conf = _lib.TsvadConfig(
+        conf = (_lib.TsvadConfigEx if c.frame_level_gsp else _lib.TsvadConfig)(
             variant=c.variant, max_num_speaker=c.max_num_speaker, rs_len=c.rs_len, max_batch=self.max_batch,
             max_fbank_frames=self.max_fbank, precision=_lib.PRECISION[precision],
             num_transformer_layer=c.num_transformer_layer, num_attention_head=c.num_attention_head,
@@ -79,7 +79,14 @@ class TSVADModel(_lib.Handle):
             transformer_ffn_embed_dim=c.transformer_ffn_embed_dim, speaker_embed_dim=c.speaker_embed_dim,
             backend=c.backend, d_state=c.d_state if c.mamba2_backend else 0,
             expand=c.expand if c.mamba2_backend else 0, **wav)
-        if wcfg is None:
+        if c.frame_level_gsp:
+            # "CAM++_frame_level_gsp_fc": variant 0 with the gsp_fc stage, a field past sd_tsvad_config's own
+            import ctypes
+            conf.frame_level_gsp = 1
+            h = ctypes.c_void_p()
+            _lib.call("sd_tsvad_create_ex", ctypes.byref(conf), ctypes.byref(h))
+            self._h = h
+        elif wcfg is None:
             self._create(conf)
         else:
             import ctypes

@@ -22,12 +22,20 @@ Shape = Tuple[int, ...]
 # ----------------------------------------------------------------------------- TS-VAD
 # (speech_encoder_type, single_backend_type, multi_backend_type) -> sd_tsvad_config.backend of the Mamba2 back ends.
 # Mamba v1 ("mamba", "mamba_v2"), "mamba2_unidirectional" and mamba2 behind another speech encoder are not built.
-_MAMBA2_BACKENDS = {("CAM++", "mamba2", "transformer"): 1, ("CAM++", "mamba2", "mamba2"): 2}
+_MAMBA2_BACKENDS = {("CAM++", "mamba2", "transformer"): 1, ("CAM++", "mamba2", "mamba2"): 2,
+                    ("CAM++_frame_level_gsp_fc", "mamba2", "transformer"): 1,
+                    ("CAM++_frame_level_gsp_fc", "mamba2", "mamba2"): 2}
 MAMBA2_HEADDIM = 64   # mamba_ssm Mamba2's headdim default
 # The conformer back ends (egs/magicdata-ramc/ts_vad2/model.py:290-313, 451-463): torchaudio.models.Conformer with a
 # BatchNorm conv module, along time.  The reference's recipes pair them with CAM++ only and never run a transformer
 # single back end in front of a conformer multi one.
-_CONFORMER_BACKENDS = {("CAM++", "conformer", "transformer"): 4, ("CAM++", "conformer", "conformer"): 5}
+_CONFORMER_BACKENDS = {("CAM++", "conformer", "transformer"): 4, ("CAM++", "conformer", "conformer"): 5,
+                       ("CAM++_frame_level_gsp_fc", "conformer", "transformer"): 4,
+                       ("CAM++_frame_level_gsp_fc", "conformer", "conformer"): 5}
+# "CAM++_frame_level_gsp_fc" (egs/magicdata-ramc/ts_vad2/model.py:543-563, 1275-1287): the CAM++ trunk and every back end
+# built behind it, with frame-level statistics + gsp_fc = Linear(2, GSP_FC_DIM) in front of speech_down_or_up's conv
+FRAME_LEVEL_GSP = "CAM++_frame_level_gsp_fc"
+GSP_FC_DIM = 256
 CONFORMER_BACKEND_KERNEL = 31   # depthwise_conv_kernel_size the reference passes
 
 
@@ -185,13 +193,16 @@ class TSVADConfig:
         if not self.ots_vad_style and (self.speech_encoder_type, self.single_backend_type,
                                        self.multi_backend_type) in _CONFORMER_BACKENDS:
             return 0   # CAM++ with conformer back ends: variant 0 plus `backend`
+        if not self.ots_vad_style and (self.speech_encoder_type, self.single_backend_type,
+                                       self.multi_backend_type) == (FRAME_LEVEL_GSP, "transformer", "transformer"):
+            return 0   # variant 0's trunk and back end around the gsp_fc stage (`frame_level_gsp`)
         if (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type) != (
                 "CAM++", "transformer", "transformer"):
             raise ValueError(
                 f"unsupported TS-VAD configuration {self.speech_encoder_type}/"
                 f"{self.single_backend_type}/{self.multi_backend_type} (MI355X backend builds CAM++ "
 "with transformer, mamba2 + transformer, mamba2 + mamba2, conformer + transformer, conformer + conformer or "
-                "conformer_ots_vad/lstm_ots_vad, "
+                "conformer_ots_vad/lstm_ots_vad, CAM++_frame_level_gsp_fc with the same five back-end pairs, "
                 "resnet34_wespeaker, ecapa_channel_1024_wespeaker and ReDimNetB2 with transformer, WavLM / "
                 "WavLM_weight_sum with transformer given wavlm_cfg, w2v-bert2 with transformer, whisper with transformer)")
         return 0
@@ -205,6 +216,13 @@ class TSVADConfig:
         self.variant
         key = (self.speech_encoder_type, self.single_backend_type, self.multi_backend_type)
         return _MAMBA2_BACKENDS.get(key, _CONFORMER_BACKENDS.get(key, 0))
+
+    @property
+    def frame_level_gsp(self) -> bool:
+        """speech_encoder_type "CAM++_frame_level_gsp_fc": variant 0 with per-frame (mean, std) + gsp_fc in front of
+        speech_down_or_up (sd_tsvad_config_ex.frame_level_gsp).  Raises like `variant`."""
+        self.variant
+        return self.speech_encoder_type == FRAME_LEVEL_GSP
 
     @property
     def mamba2_backend(self) -> bool:
@@ -568,7 +586,10 @@ def tsvad_layout(cfg: TSVADConfig) -> list:
         if cfg.variant == 1:
             k.append(("gsp_fc.weight", (se, 2), "linear"))
             k.append(("gsp_fc.bias", (se,), "small"))
-        k.append(("speech_down_or_up.0.weight", (se, 512, 5), "conv1d"))
+        if cfg.frame_level_gsp:   # Linear(2, 256) on the frame statistics, then the conv on its 256 features
+            k.append(("gsp_fc.weight", (GSP_FC_DIM, 2), "linear"))
+            k.append(("gsp_fc.bias", (GSP_FC_DIM,), "small"))
+        k.append(("speech_down_or_up.0.weight", (se, GSP_FC_DIM if cfg.frame_level_gsp else 512, 5), "conv1d"))
         k.append(("speech_down_or_up.0.bias", (se,), "small"))
         _bn(k, "speech_down_or_up.1.bn", se)
     if se * 2 != e:
